@@ -24,6 +24,9 @@ kernel's own launch time.  Barriers bracket the region; the slowest rank's time 
 process, one engine set, one HIP stream set per device; no data-path collective): weak scaling.
 `--gpus N` without WORLD_SIZE in the environment starts the N rank processes itself (before anything
 touches the GPU); under torch.distributed.run it checks N against WORLD_SIZE.
+`--dump-outputs DIR` writes, after the timed steps, what one engine batch of the timed path returns to the search
+(p3hip_result fields over a fixed seeded batch of leaf positions) as DIR/<field>.npy, so that two builds can be
+compared output for output.
 
 Secondary figures in the same JSON line:
   engine_only  — forward pass alone over a resident batch (no host, no PCIe), with the shader clock and socket power
@@ -69,6 +72,37 @@ def make_positions(n, seed):
     base = features.random_positions(64, seed=seed, n_games=16)
     reps = (n + len(base) - 1) // len(base)
     return np.tile(base, reps)[:n].copy()
+
+
+DUMP_SEED = 4242        # --dump-outputs: the leaf positions of the dumped batch
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(directory, path, batch, rank, device):
+    """--dump-outputs: one engine batch exactly as the timed path runs it (an engine of `batch` slots opened with
+    P3HIP_FLAG_SHARED_DEVICE like the self-play host's, p3hip_load_slot x batch -> p3hip_run -> p3hip_get_slot x batch),
+    over a fixed seeded batch of leaf positions instead of the search's own leaves (those depend on every earlier
+    result, so two builds would not see the same inputs).  Writes the fields of p3hip_result the search receives as
+    float32 [rows, n] arrays, DIR/<field>.npy; rows = the whole batch, or its first slots if it exceeds 64 MB."""
+    from p3achygo_amd import engine, features
+    pos = features.random_positions(batch, seed=DUMP_SEED + rank, n_games=64)
+    eng = engine.create_engine(engine.kind_from_engine_path(path), path, batch, 1, device=device,
+                               flags=engine.FLAG_SHARED_DEVICE)
+    try:
+        for i in range(batch):
+            eng.LoadBatch(i, pos[i:i + 1])
+        eng.RunInference()
+        res = [eng.GetBatch(i) for i in range(batch)]
+    finally:
+        eng.close()
+    arrays = {f: np.array([np.ctypeslib.as_array(getattr(r, f)) for r in res], np.float32)
+              for f in ("move_logits", "move_probs", "value_probs", "score_probs", "opt_move_probs")}
+    arrays["err2_outcome"] = np.array([[r.err2_outcome] for r in res], np.float32)
+    rows = min(batch, DUMP_MAX_BYTES // sum(a[0].nbytes for a in arrays.values()))
+    os.makedirs(directory, exist_ok=True)
+    for f, a in arrays.items():
+        np.save(os.path.join(directory, f"{f}.npy"), a[:rows])
+    return {"dir": os.path.abspath(directory), "rows": rows, "fields": list(arrays), "seed": DUMP_SEED + rank}
 
 
 def cpu_baseline(path, pos, model, budget_s=10.0):
@@ -236,7 +270,13 @@ def main():
     ap.add_argument("--null-engine", action="store_true",
                     help="plumbing rehearsal without a GPU: the host over its NullEvaluator (uniform policy); "
                          "the line it prints is marked as not a measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what one engine batch of the timed path returns to its caller "
+                         "(p3hip_result fields over a fixed seeded batch of leaf positions) as DIR/<field>.npy, float32; "
+                         "rank 0 only")
     args = ap.parse_args()
+    if args.dump_outputs and args.null_engine:
+        sys.exit("bench.py: --dump-outputs needs the HIP engine (the NullEvaluator computes nothing to compare)")
 
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
@@ -312,6 +352,9 @@ def main():
     totals = sharding.sum_over_ranks(shard, [st.positions, st.moves, st.games, st.batches, st.cache_hits,
                                              ladder1[0] - ladder0[0], ladder1[3] - ladder0[3],
                                              st.games_past_opening, st.advance_batches])
+    dumped = None
+    if use_gpu and args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, path, args.batch, rank, local_rank)
 
     def headline():
         pps = totals[0] / dt
@@ -512,6 +555,8 @@ def main():
                               # cap, and the clock the chip grants under it (2.0-2.2 GHz of 2.4) is in every number of this line
                               "chip_during_loop": power}
         out.update(extras)
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         # self-check: a step cannot be shorter than the ONE trunk launch every batch must execute
         if roof and roof.get("launch_ms") and roof.get("kernel", "").startswith("k_block"):
             out["window_artifact"] = bool(out["ms_per_batch"] < 0.98 * roof["launch_ms"])

@@ -911,16 +911,19 @@ def test_launch_graph_with_the_nn_cache_never_replays_the_other_feature_buffer(b
     eng.close()
 
 
-def test_bench_line_keeps_its_contract_and_its_self_checks(built):
+def test_bench_line_keeps_its_contract_and_its_self_checks(built, tmp_path):
     """bench.py's one JSON line on the GPU (a short run: 8 rounds, no CPU baseline, no counter passes): the driver's keys,
     a steady-state headline (per-batch time not below the trunk launch's own time, value not above what the forward pass
-    alone does by more than the streams' overlap allows), the roofline object, and the chip's state beside the engine-only leg."""
+    alone does by more than the streams' overlap allows), the roofline object, and the chip's state beside the engine-only leg.
+    `--dump-outputs`: one batch of the timed path's results over fixed seeded leaves, float32 and well formed."""
     import json
     import subprocess
     import sys
     from conftest import ROOT
+    dump = tmp_path / "dump"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "2", "--no-cpu-baseline",
-                        "--no-pmc", "--no-extras", "--engine-steps", "60"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--no-pmc", "--no-extras", "--engine-steps", "60", "--dump-outputs", str(dump)],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -939,3 +942,13 @@ def test_bench_line_keeps_its_contract_and_its_self_checks(built):
     chip = d["engine_only"]["chip_during_loop"]
     if chip is not None:                                            # amdsmi present: clock, power and limiter residencies
         assert 500 < chip["gfx_clock_mhz_mean"] < 3000 and chip["socket_power_w_mean"] > 100
+    assert d["dumped_outputs"]["rows"] == 1024
+    shapes = {"move_logits": 362, "move_probs": 362, "value_probs": 2, "score_probs": 800, "opt_move_probs": 362,
+              "err2_outcome": 1}
+    got = {f: np.load(dump / f"{f}.npy") for f in shapes}
+    assert sorted(p.name for p in dump.iterdir()) == sorted(f"{f}.npy" for f in shapes)
+    for f, n in shapes.items():
+        assert got[f].dtype == np.float32 and got[f].shape == (1024, n) and np.isfinite(got[f]).all(), f
+    for f in ("move_probs", "value_probs", "score_probs"):
+        assert np.allclose(got[f].sum(axis=1), 1.0, atol=1e-3), f
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20

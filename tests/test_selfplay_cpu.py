@@ -491,7 +491,9 @@ def test_round_anchored_window_counts_whole_rounds(built):
         host_api.set_step_rounds(0)
         host_api.set_step_limit(0)
         host_api.set_groups(2)
-    assert st.rounds == 6 and 6 + 3 * 3 <= st.batches <= 6 + 3 * 12
+    # the anchor's 6 are fixed; how many batches of the three unpaced groups fall inside its window is a race (totals
+    # from 9 to 46 over 120 runs), so the total is bounded below by the anchor's own and the solo run below is exact
+    assert st.rounds == 6 and st.batches >= 6
     assert st.positions == 16 * st.batches and st.seconds > 0
     assert 0.5 * st.seconds < st.seconds_fit < 2.0 * st.seconds      # the anchor's 7 completion instants, fitted
     assert solo.rounds == solo.batches == 6 and solo.positions == 6 * 16
