@@ -171,7 +171,8 @@ int p3hip_get_raw(p3hip_engine* e, int slot, float* out);
  * returns the average milliseconds per launch (<0 on error; also <0 for layer-wise trunks,
  * which have no fused block kernel); writes the
  * algorithmic FLOPs of the convs one launch executes (inner 3x3s + 1x1 reduce/expand,
- * unpadded 361 points). */
+ * unpadded 361 points).  Transformer trunks: times the attention kernel k_tfm_attn and writes the FLOPs of its
+ * q.k^T and p.v products over 361 x 361 tokens. */
 double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
                                double* flops_per_launch, const char** kernel_name);
 /* P3HIP_FLAG_LAUNCH_GRAPH: 1 once the full-batch forward pass has been captured and is being replayed,
@@ -182,10 +183,14 @@ int p3hip_graph_state(const p3hip_engine* e);
  * forward pass, [workgroup 0..7][block 0..15][wave 0..3][24], to out.  Returns 0, or 1 when there are none. */
 int p3hip_blockw_stamps(p3hip_engine* e, unsigned long long* out, int n);
 /* Debugging aid: the residual stream x after the last forward pass (stopped early by P3HIP_DEBUG_STOP_BLOCK in the
- * environment, if set), n_positions x C x 361 values in the device layout [pos][C / 8][361][8], as floats. */
+ * environment, if set), n_positions x C x 361 values in the device layout [pos][C / 8][361][8], as floats.
+ * Transformer trunks: C is the stream's padded width 128 (the model's 96 channels, then 32 that stay zero). */
 int p3hip_debug_x(p3hip_engine* e, float* out, int n_positions);
 /* Algorithmic FLOPs (2*MAC) of one position: total, and 3x3 trunk convs only. */
 void p3hip_flops_per_position(const p3hip_engine* e, double* total, double* conv3x3);
+/* The spiral RoPE tables the transformer trunk uses (python/model_transformer.py, head_dim 32, 4 rotations, theta
+ * 100), [361 tokens][32] each, in double precision.  Needs no device. */
+void p3hip_rope_table(double* cos_out, double* sin_out);
 
 #ifdef __cplusplus
 }

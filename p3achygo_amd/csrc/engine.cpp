@@ -27,6 +27,7 @@
 #include "../../include/p3hip.h"
 #include "kernels.h"
 #include "slot_state.h"
+#include "transformer.h"
 
 namespace {
 
@@ -50,6 +51,11 @@ struct Tensor {
 
 struct WeightFile {
   int version = 0, nblocks = 0, C = 0, Cb = 0, H = 0, V = 0, bint = 0, inner = 0, btype = 0;
+  // Transformer trunks (btype 3): model_C is the file's C (96); C becomes the residual stream's width 128, and the
+  // tensors of the stem and the heads are zero-padded to it (pad_transformer_io), so that k_init<128> and the C = 128
+  // heads serve the trunk unchanged.  model_C == C for every other architecture.
+  int model_C = 0;
+  std::vector<std::vector<float>> padded;
   std::vector<float> data;
   std::map<std::string, Tensor> tensors;
 
@@ -64,7 +70,7 @@ struct WeightFile {
     version = hdr[0]; nblocks = hdr[1]; C = hdr[2]; Cb = hdr[3]; H = hdr[4]; V = hdr[5];
     bint = hdr[6]; inner = hdr[7]; btype = hdr[8];
     int nt = hdr[9];
-    if (nt < 1 || nt > 8192 || nblocks < 1 || nblocks > 256 || bint < 1) {
+    if (nt < 1 || nt > 8192 || nblocks < 1 || nblocks > 256 || (btype == 3 ? bint != 0 : bint < 1)) {
       err = "implausible .p3w header"; fclose(f); return false;
     }
     struct Ent { char name[48]; int ndim; int dims[4]; long long off; };
@@ -97,7 +103,35 @@ struct WeightFile {
       t.data = data.data() + e.off;
       tensors[std::string(e.name, strnlen(e.name, sizeof e.name))] = t;
     }
+    model_C = C;
+    if (btype == 3 && C == p3::kTfmC) pad_transformer_io();
     return true;
+  }
+  // [..][C] -> [..][128] (init conv, game dense) and [C][32] -> [128][32] (the head convs), zeros in the new channels
+  void pad_transformer_io() {
+    const int Cp = 128;
+    auto pad = [&](const std::string& n, size_t rows, bool out_channels) {
+      auto it = tensors.find(n);
+      const size_t want = out_channels ? rows * C : (size_t)C * 32;
+      if (it == tensors.end() || it->second.size() != want) return;   // build_plan reports it as missing
+      std::vector<float> w(out_channels ? rows * Cp : (size_t)Cp * 32, 0.0f);
+      for (size_t i = 0; i < want; ++i) {
+        const size_t r = out_channels ? i / C : 0, c = out_channels ? i % C : i;
+        w[out_channels ? r * Cp + c : c] = it->second.data[i];
+      }
+      padded.push_back(std::move(w));
+      Tensor t;
+      t.dims = it->second.dims;
+      t.dims.back() = out_channels ? Cp : t.dims.back();
+      if (!out_channels) t.dims[t.dims.size() - 2] = Cp;
+      t.data = padded.back().data();
+      it->second = t;
+    };
+    pad("init_conv.w", 25 * 15, true);
+    pad("init_game.w", 8, true);
+    pad("init_game.b", 1, true);
+    for (const char* n : {"policy.conv_p.w", "policy.conv_g.w", "value.conv.w"}) pad(n, 0, false);
+    C = Cp;
   }
   // A missing or mis-shaped tensor (truncated / foreign file) is recorded and answered with a
   // zero tensor of the expected size; build_plan checks `missing` once at the end and
@@ -117,7 +151,7 @@ struct WeightFile {
     t.data = zeros.back().data();
     return stand_ins[n] = t;
   }
-  bool is_broadcast(int i) const { return i % bint == bint - 1; }  // model.py:1002
+  bool is_broadcast(int i) const { return bint > 0 && i % bint == bint - 1; }  // model.py:1002
 };
 
 // ---- device arena -----------------------------------------------------------------
@@ -187,6 +221,40 @@ void pack_granule(std::vector<_Float16>& dst, const float* W, int cin_total, int
 
 struct FoldedBN { size_t scale_off, shift_off; };
 
+// A Keras (in, out) matrix W[K][N] as MFMA 16x16x32 A fragments [N / 16][K / 32][64 lanes][8] (transformer.h).
+// `col0` / `ld`: the matrix is columns col0 .. col0 + N of a row-major [K][ld] tensor.
+void pack_afrag(std::vector<_Float16>& dst, const float* W, int K, int N, int ld, int col0) {
+  for (int ct = 0; ct < N / 16; ++ct)
+    for (int st = 0; st < K / 32; ++st)
+      for (int lane = 0; lane < 64; ++lane)
+        for (int el = 0; el < 8; ++el)
+          dst.push_back((_Float16)W[(size_t)(32 * st + 8 * (lane >> 4) + el) * ld + col0 + 16 * ct + (lane & 15)]);
+}
+
+// The spiral RoPE tables of python/model_transformer.py spiral_rope_cos_sin_table(num_rotations = 4, embed_dim = 32,
+// grid_len = 19), ROPE_THETA = 100, restated: [361 tokens][32] each, token s = 19 row + col (meshgrid indexing "ij":
+// the first coordinate is the row).  Channel i belongs to rotation partition k = i / 8 (direction k pi / 4) and takes
+// the frequency theta^(-t / 8), t = min(7, 2 (k % 2) + 4 ((i % 8) / 4) + (i % 8) / 2 % 2): both channels of a pair
+// share it.
+void spiral_rope_table(double* cos_out, double* sin_out) {
+  const int D = p3::kTfmD, K = 4, per = D / K, nth = D / 4;
+  const double kPi = 3.14159265358979323846;
+  double theta[p3::kTfmD];
+  for (int i = 0; i < D; ++i) {
+    const int k = i / per, r = (i % per) / 2;
+    int t = 2 * (k % (K / 2)) + (r / 2) * K + (r % 2);
+    if (t > nth - 1) t = nth - 1;
+    theta[i] = std::pow(100.0, -(double)t / nth);
+  }
+  for (int s = 0; s < kNLoc; ++s)
+    for (int i = 0; i < D; ++i) {
+      const double ang = (i / per) * (kPi / K);
+      const double proj = (s / 19) * std::cos(ang) + (s % 19) * std::sin(ang);
+      cos_out[s * D + i] = std::cos(theta[i] * proj);
+      sin_out[s * D + i] = std::sin(theta[i] * proj);
+    }
+}
+
 // One conv launch of a layer-wise block (kind 4).  Regions: 0 = x; 1, 2 = the two C_b-channel
 // halves of the scratch buffer t; 3, 4 = those of u (3 also names u as a whole C-channel buffer).
 struct LayerPlan {
@@ -198,8 +266,12 @@ struct LayerPlan {
   int nms = 0;
 };
 
+// One transformer block (kind 5): arena offsets of its tensors, the GEMM weights as MFMA A fragments (transformer.h)
+struct TfmPlan { size_t rms_in = 0, rms_out = 0, wqkv = 0, wo = 0, wgu = 0, wdown = 0; };
+
 struct BlockPlan {
-  int kind;  // 0 btl, 1 nbt, 3 broadcast, 4 layer-wise (btl/nbt at widths the fused kernel lacks)
+  int kind;  // 0 btl, 1 nbt, 3 broadcast, 4 layer-wise (btl/nbt at widths the fused kernel lacks), 5 transformer
+  TfmPlan tfm;
   std::vector<LayerPlan> layers;
   size_t stream_off = 0;
   int nms = 0;
@@ -257,6 +329,8 @@ struct p3hip_engine {
   size_t game_w_off = 0, game_b_off = 0;
   size_t heads_stream_off = 0; int heads_nms = 0;
   size_t heads_conv_a_off = 0, heads_image_off = 0;
+  bool tfm = false;                     // transformer trunk (blocks of kind 5)
+  size_t rope_cos_off = 0, rope_sin_off = 0;
   bool heads_fused = false;   // k_headsx: the head convs inside the heads kernel (C <= 256; P3HIP_NO_HFUSE clears it)
   std::map<std::string, size_t> head_off;
 
@@ -265,6 +339,7 @@ struct p3hip_engine {
   unsigned char* h_feats_compact = nullptr;  // pinned, dense
   unsigned char* d_feats = nullptr;
   _Float16 *d_x = nullptr, *d_t = nullptr, *d_u = nullptr;
+  _Float16* d_qkv = nullptr;   // transformer trunks: q, k, v [3][batch][head][384][32] (rows 361.. zeroed once)
 #ifdef P3_DIAG
   unsigned long long* d_stamps = nullptr;   // diagnostic build: k_block phase stamps of one launch (P3DIAG_LAUNCH)
   unsigned long long* d_spans = nullptr;    // and every workgroup's entry / per-position / exit times of that launch
@@ -357,13 +432,17 @@ bool build_plan(p3hip_engine* e, Arena& ar) {
   const bool bottleneck_ok = wf.btype == 1 || (wf.btype == 0 && wf.inner >= 1 && wf.inner <= 3);
   const bool layerwise = (C == 384 && Cb == 192 && bottleneck_ok) || classic;
   const bool v_ok = wf.V == 32 || wf.V == 48 || wf.V == 64 || wf.V == 80;
-  if (!((fused && bottleneck_ok) || layerwise) || wf.H != 32 || !v_ok) {
+  // transformer trunk: C = 96 and 3 heads in the file (Cb holds the head count), the stream padded to C = 128
+  const bool tfm = wf.btype == 3 && wf.model_C == p3::kTfmC && C == 128 && Cb == p3::kTfmHeads && p3::heads_fusable(C, wf.V);
+  if ((!((fused && bottleneck_ok) || layerwise) && !tfm) || wf.H != 32 || !v_ok) {
     e->err = "unsupported architecture for the HIP engine (need (C, Cb) in {(128,64), (256,128), (384,192)} with "
-             "btl (1-3 inner layers) or nbt blocks, or C=192 classic blocks of two convs; H=32, V in {32,48,64,80})";
+             "btl (1-3 inner layers) or nbt blocks, or C=192 classic blocks of two convs, or the transformer trunk "
+             "C=96 with 3 heads; H=32, V in {32,48,64,80} (transformer: V in {32,48,64}))";
     return false;
   }
+  e->tfm = tfm;
   // slice width of the per-position kernels that stage C channels (k_conv1x1 family)
-  const int CB = classic ? 64 : (layerwise ? 128 : Cb);
+  const int CB = classic ? 64 : ((layerwise || tfm) ? 128 : Cb);
   const int CPI = classic ? 64 : 128;   // output pass width of the init conv
   // init conv
   {
@@ -426,7 +505,37 @@ bool build_plan(p3hip_engine* e, Arena& ar) {
     tail_stream.clear();
     head_of = tail_of = -1;
   };
-  for (int i = 0; i < wf.nblocks; ++i) {
+  if (tfm) {
+    std::vector<double> cd(kNLoc * p3::kTfmD), sd(kNLoc * p3::kTfmD);
+    spiral_rope_table(cd.data(), sd.data());
+    const std::vector<float> cf(cd.begin(), cd.end()), sf(sd.begin(), sd.end());
+    e->rope_cos_off = ar.add(cf.data(), cf.size() * 4);
+    e->rope_sin_off = ar.add(sf.data(), sf.size() * 4);
+  }
+  for (int i = 0; tfm && i < wf.nblocks; ++i) {
+    const std::string p = "blocks." + std::to_string(i);
+    const int c = p3::kTfmC, f = p3::kTfmF;
+    auto T = [&](const char* n, size_t sz) { return wf.get(p + "." + n, sz).data; };
+    BlockPlan bp;
+    bp.kind = 5;
+    bp.tfm.rms_in = ar.add(T("rms_in.scale", c), c * 4);
+    bp.tfm.rms_out = ar.add(T("rms_out.scale", c), c * 4);
+    std::vector<_Float16> w;
+    for (const char* n : {"q.w", "k.w", "v.w"}) pack_afrag(w, T(n, (size_t)c * c), c, c, c, 0);
+    bp.tfm.wqkv = ar.add(w.data(), w.size() * 2);
+    w.clear();
+    pack_afrag(w, T("o.w", (size_t)c * c), c, c, c, 0);
+    bp.tfm.wo = ar.add(w.data(), w.size() * 2);
+    w.clear();
+    pack_afrag(w, T("ffn_gate.w", (size_t)c * f), c, f, f, 0);
+    pack_afrag(w, T("ffn_up.w", (size_t)c * f), c, f, f, 0);
+    bp.tfm.wgu = ar.add(w.data(), w.size() * 2);
+    w.clear();
+    pack_afrag(w, T("ffn_down.w", (size_t)f * c), f, c, c, 0);
+    bp.tfm.wdown = ar.add(w.data(), w.size() * 2);
+    e->blocks.push_back(bp);
+  }
+  for (int i = 0; !tfm && i < wf.nblocks; ++i) {
     BlockPlan bp;
     if (layerwise) flush_run();
     const std::string p = "blocks." + std::to_string(i);
@@ -935,7 +1044,21 @@ bool enqueue_forward(p3hip_engine* e, int npos) {
   for (size_t bi = 0; bi < e->blocks.size(); ++bi) {
     if (stop_block >= 0 && (int)bi >= stop_block) return true;
     const BlockPlan& bp = e->blocks[bi];
-    if (bp.kind == 3) {
+    if (bp.kind == 5) {
+      const size_t per = (size_t)e->batch * p3::kTfmHeads * p3::kTfmLPad * p3::kTfmD;   // one of q, k, v
+      _Float16 *q = e->d_qkv, *k = q + per, *v = k + per, *o = e->d_t;
+      p3::TfmQkvArgs a{e->d_x, q, k, v, npos, e->dev<float>(bp.tfm.rms_in), e->d_arena + bp.tfm.wqkv,
+                       e->dev<float>(e->rope_cos_off), e->dev<float>(e->rope_sin_off)};
+      if (!e->check(p3::launch_tfm_qkv(a, s), "launch k_tfm_qkv")) return false;
+      const p3::TfmAttnArgs b{q, k, v, o, npos};
+      const bool timed = e->time_blocks && 2 * e->timed_blocks + 1 < (int)e->blk_ev.size();
+      if (timed) hipEventRecord(e->blk_ev[2 * e->timed_blocks], s);
+      if (!e->check(p3::launch_tfm_attn(b, s), "launch k_tfm_attn")) return false;
+      if (timed) hipEventRecord(e->blk_ev[2 * e->timed_blocks++ + 1], s);
+      const p3::TfmFfnArgs f{o, e->d_x, npos, e->d_arena + bp.tfm.wo, e->dev<float>(bp.tfm.rms_out),
+                             e->d_arena + bp.tfm.wgu, e->d_arena + bp.tfm.wdown};
+      if (!e->check(p3::launch_tfm_ffn(f, s), "launch k_tfm_ffn")) return false;
+    } else if (bp.kind == 3) {
       p3::Conv1x1Args c0{};
       c0.in = e->d_x; c0.out16 = e->d_t; c0.npos = npos;
       c0.wstream = e->d_arena + bp.stream_off; c0.nms_total = bp.nms;
@@ -1116,6 +1239,7 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
   e->n_cu = prop.multiProcessorCount;
   const int C = e->wf.C;
   const size_t B = batch_size;
+  const size_t qkv_bytes = 3 * B * p3::kTfmHeads * p3::kTfmLPad * p3::kTfmD * 2;
   bool ok = e->check(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking), "hipStreamCreate") &&
             e->check(hipEventCreate(&e->ev0), "hipEventCreate") &&
             e->check(hipEventCreate(&e->ev1), "hipEventCreate") &&
@@ -1132,11 +1256,13 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
             e->check(hipMalloc((void**)&e->d_t, B * C * kNLoc * 2), "hipMalloc t") &&
             e->check(hipMalloc((void**)&e->d_u, B * C * kNLoc * 2), "hipMalloc u") &&
             (e->wf.btype != 1 || e->check(hipMalloc((void**)&e->d_s, B * e->wf.Cb * kNLoc * 2), "hipMalloc s")) &&
+            (!e->tfm || e->check(hipMalloc((void**)&e->d_qkv, qkv_bytes), "hipMalloc qkv")) &&
             e->check(hipMalloc((void**)&e->d_hp, B * 96 * kNLoc * 4), "hipMalloc hp") &&
             e->check(hipMalloc((void**)&e->d_out, B * p3::kOutStride * 4), "hipMalloc out");
   if (!ok) return fail(e->err);
   memset(e->h_feats, 0, B * kFeatBytes);
   if (!e->check(hipMemsetAsync(e->d_feats, 0, B * kFeatBytes, e->stream), "hipMemset feats") ||
+      (e->tfm && !e->check(hipMemsetAsync(e->d_qkv, 0, qkv_bytes, e->stream), "hipMemset qkv")) ||
       !e->check(hipMemsetAsync(e->d_out, 0, B * p3::kOutStride * 4, e->stream), "hipMemset out") ||
       !e->check(hipStreamSynchronize(e->stream), "upload sync")) return fail(e->err);
   e->slots = p3::SlotStates((int)B);
@@ -1150,7 +1276,7 @@ void p3hip_destroy(p3hip_engine* e) {
   if (e->stream || e->d_arena) (void)hipSetDevice(e->device);
   if (e->stream) hipStreamSynchronize(e->stream);
   hipFree(e->d_arena); hipFree(e->d_feats); hipFree(e->d_x); hipFree(e->d_t); hipFree(e->d_u); hipFree(e->d_s);
-  hipFree(e->d_hp); hipFree(e->d_out); hipFree(e->d_res);
+  hipFree(e->d_hp); hipFree(e->d_out); hipFree(e->d_res); hipFree(e->d_qkv);
   hipFree(e->d_bw_stamps);
   if (e->bw_mod) hipModuleUnload(e->bw_mod);
   {
@@ -1472,10 +1598,11 @@ int p3hip_get_raw(p3hip_engine* e, int slot, float* out) {
 
 void p3hip_flops_per_position(const p3hip_engine* e, double* total, double* conv3x3) {
   const WeightFile& w = e->wf;
-  const double C = w.C, Cb = w.Cb, H = w.H, V = w.V, L = kNLoc;
+  const double C = w.model_C, Cb = w.Cb, H = w.H, V = w.V, L = kNLoc;
   double mac = L * 25 * 15 * C + 8 * C, mac3 = 0;
   for (int i = 0; i < w.nblocks; ++i) {
-    if (w.is_broadcast(i)) mac += L * 2 * C * C + C * L * L;
+    if (e->tfm) mac += L * 4 * C * C + 2 * L * L * C + L * 3 * C * 2 * C;   // q k v o, q.k^T and p.v, SwiGLU
+    else if (w.is_broadcast(i)) mac += L * 2 * C * C + C * L * L;
     else if (w.btype == 0) { mac += L * 2 * C * Cb; mac3 += L * w.inner * 9 * Cb * Cb; }
     else if (w.btype == 1) { mac += L * 2 * C * Cb; mac3 += L * 4 * 9 * Cb * Cb; }
     else { mac3 += L * w.inner * 9 * C * C; }
@@ -1498,6 +1625,34 @@ double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
         if (lp.kw == 3) { ++n3x3; c3 = lp.cin; }
   }
   if (n_positions < 1 || n_positions > e->batch || iters < 1 || !e->bind()) return -1.0;
+  if (e->tfm) {
+    // transformer trunks: the attention kernel (enqueue_forward records an event pair around each k_tfm_attn)
+    while ((int)e->blk_ev.size() < 2 * wf.nblocks) {
+      hipEvent_t ev;
+      if (!e->check(hipEventCreate(&ev), "hipEventCreate")) return -1.0;
+      e->blk_ev.push_back(ev);
+    }
+    if (!enqueue_forward(e, n_positions)) return -1.0;   // warm-up
+    double total_ms = 0.0;
+    long launches = 0;
+    for (int i = 0; i < iters; ++i) {
+      e->time_blocks = true;
+      e->timed_blocks = 0;
+      const bool ok = enqueue_forward(e, n_positions);
+      e->time_blocks = false;
+      if (!ok || !e->check(hipStreamSynchronize(e->stream), "sync")) return -1.0;
+      for (int b = 0; b < e->timed_blocks; ++b) {
+        float ms = 0;
+        hipEventElapsedTime(&ms, e->blk_ev[2 * b], e->blk_ev[2 * b + 1]);
+        total_ms += ms;
+        ++launches;
+      }
+    }
+    // q.k^T and p.v over the 361 x 361 tokens of every head (algorithmic, not the padded 384 keys)
+    if (flops_per_launch) *flops_per_launch = 2.0 * n_positions * 2.0 * kNLoc * kNLoc * p3::kTfmC;
+    if (kernel_name) *kernel_name = "k_tfm_attn";
+    return launches ? total_ms / launches : -1.0;
+  }
   if (!bp && n3x3 > 0) {
     // layer-wise trunks (C = 384, classic): the dominant kernel is the 3x3 layer conv, k_lconv<3, ..>
     while ((int)e->blk_ev.size() < 2 * n3x3) {
@@ -1582,6 +1737,8 @@ int p3hip_debug_x(p3hip_engine* e, float* out, int n_positions) {
   for (size_t i = 0; i < n; ++i) out[i] = (float)h[i];
   return 0;
 }
+
+void p3hip_rope_table(double* cos_out, double* sin_out) { spiral_rope_table(cos_out, sin_out); }
 
 int p3hip_blockw_stamps(p3hip_engine* e, unsigned long long* out, int n) {
   if (!e->bind() || !e->d_bw_stamps) return 1;

@@ -29,7 +29,7 @@ EXPORTS = [
     "p3hip_last_error", "p3hip_forward_resident", "p3hip_upload", "p3hip_sync", "p3hip_get_raw",
     "p3hip_time_trunk_kernel", "p3hip_flops_per_position", "p3hip_graph_state",
     "p3hip_cache_enable", "p3hip_load_slot_keyed", "p3hip_get_slot_keyed", "p3hip_cache_stats",
-    "p3hip_blockw_stamps", "p3hip_debug_x",
+    "p3hip_blockw_stamps", "p3hip_debug_x", "p3hip_rope_table",
 ]
 
 FLAG_RUN_ALL_SLOTS = 2
@@ -245,6 +245,17 @@ class HipEngine:
     def _ck(self, rc: int, what: str) -> None:
         if rc != 0:
             raise EngineError(f"{what} failed (rc={rc}): " + self._L.p3hip_last_error(self._h).decode())
+
+
+def rope_table():
+    """The engine's spiral RoPE tables of the transformer trunk, (cos, sin) as [361][32] float64 (no device needed)."""
+    cos = np.zeros((361, 32), np.float64)
+    sin = np.zeros((361, 32), np.float64)
+    L = lib()
+    L.p3hip_rope_table.argtypes = [C.c_void_p, C.c_void_p]
+    L.p3hip_rope_table.restype = None
+    L.p3hip_rope_table(cos.ctypes.data, sin.ctypes.data)
+    return cos, sin
 
 
 def create_engine(kind: Kind, path: str, batch_size: int, version: int, device: int = 0,

@@ -32,7 +32,7 @@ SCORE_RANGE = 800
 NUM_V_BUCKETS = 51
 BN_EPS = 1e-3  # model.py:231 BatchNormalization(momentum=0.99, epsilon=1e-3)
 
-BLOCK_TYPES = {"btl": 0, "nbt": 1, "classic": 2}
+BLOCK_TYPES = {"btl": 0, "nbt": 1, "classic": 2, "transformer": 3}
 WEIGHT_SEED = 0x70336163  # "p3ac" 
 
 
@@ -49,7 +49,10 @@ class NetConfig:
     block_type: str
 
     def block_kind(self, i: int) -> str:
-        """model.py:1002-1011: block i is a broadcast block iff i % interval == interval-1."""
+        """model.py:1002-1011: block i is a broadcast block iff i % interval == interval-1.
+        A transformer trunk (generic_arch, model.py:1048-1058) has no broadcast blocks."""
+        if self.block_type == "transformer":
+            return "transformer"
         if i % self.broadcast_interval == self.broadcast_interval - 1:
             return "broadcast"
         return self.block_type
@@ -93,6 +96,26 @@ CONFIGS: Dict[str, NetConfig] = {
         NetConfig("test_b10c256btl1_i2", 10, 256, 128, 32, 32, 2, 1, "btl"),
     ]
 }
+
+
+# Transformer trunks (python/model_transformer.py TransformerBlock, model_config.py b14d96h3_transformer): kept out of
+# CONFIGS, whose users (the CPU oracle, keras_map) know only the convolutional blocks.  In these configs
+# bottleneck_channels holds the head count (the .p3w header's Cb field), broadcast_interval and inner_layers are 0; the
+# FFN width is 2 C and the head width C / heads.  H = 32, V = 64 are ModelConfig's defaults (the reference passes only
+# channels=96).
+TRANSFORMER_CONFIGS: Dict[str, NetConfig] = {
+    c.name: c
+    for c in [
+        NetConfig("b14d96h3_transformer", 14, 96, 3, 32, 64, 0, 0, "transformer"),
+        # not in the reference: two blocks of the same width for fast tests
+        NetConfig("test_b2d96h3_tfm", 2, 96, 3, 32, 64, 0, 0, "transformer"),
+    ]
+}
+
+
+def get_config(name: str) -> NetConfig:
+    """A config of CONFIGS or TRANSFORMER_CONFIGS by name."""
+    return CONFIGS[name] if name in CONFIGS else TRANSFORMER_CONFIGS[name]
 
 
 def tensor_specs(cfg: NetConfig) -> List[Tuple[str, Tuple[int, ...], str]]:
@@ -143,6 +166,14 @@ def tensor_specs(cfg: NetConfig) -> List[Tuple[str, Tuple[int, ...], str]]:
             for j in range(2):
                 bn(f"{p}.bn{j}", C)
                 conv(f"{p}.conv{j}", 3, C, C)
+        elif kind == "transformer":  # model_transformer.py TransformerBlock: Dense layers without bias, (in, out)
+            t.append((p + ".rms_in.scale", (C,), "rms_scale"))
+            for n in ("q", "k", "v", "o"):
+                t.append((f"{p}.{n}.w", (C, C), "glorot"))
+            t.append((p + ".rms_out.scale", (C,), "rms_scale"))
+            t.append((p + ".ffn_gate.w", (C, 2 * C), "glorot"))
+            t.append((p + ".ffn_up.w", (C, 2 * C), "glorot"))
+            t.append((p + ".ffn_down.w", (2 * C, C), "glorot"))
         else:
             raise ValueError(kind)
     # policy head, model.py:725-812
@@ -213,6 +244,8 @@ def generate_weights(cfg: NetConfig, seed: int = WEIGHT_SEED, randomize: bool = 
             w = rng.normal(0.0, 0.1, size=shape) if randomize else np.zeros(shape)
         elif init == "bn_var":
             w = rng.uniform(0.5, 2.0, size=shape) if randomize else np.ones(shape)
+        elif init == "rms_scale":   # RMSNormalization's scale starts at ones
+            w = rng.uniform(0.5, 1.5, size=shape) if randomize else np.ones(shape)
         else:
             raise ValueError(init)
         out[name] = np.ascontiguousarray(w, dtype=np.float32)
@@ -289,7 +322,10 @@ def flops_per_position(cfg: NetConfig) -> Tuple[float, float]:
     mac3 = 0
     for i in range(cfg.blocks):
         kind = cfg.block_kind(i)
-        if kind == "broadcast":
+        if kind == "transformer":
+            # q, k, v and o projections, q.k^T and p.v over all 361 keys (every head together: C), the SwiGLU FFN
+            mac += NUM_LOCS * 4 * C * C + 2 * NUM_LOCS * NUM_LOCS * C + NUM_LOCS * 3 * C * 2 * C
+        elif kind == "broadcast":
             mac += NUM_LOCS * 2 * C * C + C * NUM_LOCS * NUM_LOCS
         elif kind == "btl":
             mac += NUM_LOCS * 2 * C * Cb
