@@ -101,6 +101,10 @@ typedef struct p3hip_engine p3hip_engine;
 #define P3HIP_FLAG_LAUNCH_GRAPH 8u  /* a run over the full static batch replays ONE captured launch graph, as
                                        TrtEngineImpl::RunInference does (trt_engine.cc:260-303); runs over fewer slots
                                        (compaction, cache hits) are launched kernel by kernel.  Same kernels, same results */
+#define P3HIP_FLAG_INT8 16u         /* calibrated INT8 inference (TensorRT's INT8 engine with a MinMax calibrator,
+                                       python/trt_convert.py, cc/nn/engine/trt_calibrator.h): the convs of the layer-wise
+                                       blocks run on int8 inputs and weights.  Layer-wise trunks
+                                       only: p3hip_create returns NULL for any other trunk.  See p3hip_int8_* below */
 
 /* Creates an engine from a `.p3w` weight file (see p3achygo_amd/netspec.py) for a static
  * batch of `batch_size` slots on HIP device `device_ordinal`.  `version` is the model
@@ -153,6 +157,21 @@ int p3hip_load_slot_keyed(p3hip_engine* e, int slot, const p3hip_features* f, ui
 int p3hip_get_slot_keyed(p3hip_engine* e, int slot, p3hip_result* out, int* symmetry, int* from_cache);
 int p3hip_cache_stats(const p3hip_engine* e, uint64_t out[4]);
 
+/* ---- calibrated INT8 (P3HIP_FLAG_INT8) ----------------------------------------------------------------
+ * The quantized tensors are the inputs of every conv of the layer-wise blocks, numbered block by block, conv by conv
+ * (the order of the block's .p3w convs).  Each has one symmetric activation scale s_a = max |v| / 127.
+ *   p3hip_int8_calibrate   one p3hip_run on the fp16 plan (results fetched with p3hip_get_slot as usual) that also
+ *                          folds max |v| of every quantized tensor into the engine's running maxima and sets
+ *                          s_a = max / 127 from everything observed so far: the MinMax calibrator, called once per
+ *                          calibration batch.  With the NN cache on it evaluates every slot and stores nothing.
+ *   p3hip_run              on an INT8 engine runs the int8 plan; it fails before any calibration or p3hip_int8_set_scales.
+ *   p3hip_int8_scales      returns the number of quantized tensors (-1 without the flag) and copies up to n scales.
+ *   p3hip_int8_set_scales  loads a saved calibration (the calibration cache); n must equal that number.
+ * New scales take effect in the next run, graph replay (P3HIP_FLAG_LAUNCH_GRAPH) included. */
+int p3hip_int8_calibrate(p3hip_engine* e);
+int p3hip_int8_scales(const p3hip_engine* e, float* out, int n);
+int p3hip_int8_set_scales(p3hip_engine* e, const float* scales, int n);
+
 /* ---- measurement / test hooks (not part of the reference surface) ------------------ */
 
 /* Device-resident benchmark step: runs the forward pass on whatever is already staged in
@@ -172,7 +191,8 @@ int p3hip_get_raw(p3hip_engine* e, int slot, float* out);
  * which have no fused block kernel); writes the
  * algorithmic FLOPs of the convs one launch executes (inner 3x3s + 1x1 reduce/expand,
  * unpadded 361 points).  Transformer trunks: times the attention kernel k_tfm_attn and writes the FLOPs of its
- * q.k^T and p.v products over 361 x 361 tokens. */
+ * q.k^T and p.v products over 361 x 361 tokens.  Layer-wise trunks: times the 3x3 layer conv, k_lconv<3,..>, or on an
+ * INT8 engine k_lconv_i8<3,..>, and writes the FLOPs of one 3x3 conv. */
 double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
                                double* flops_per_launch, const char** kernel_name);
 /* P3HIP_FLAG_LAUNCH_GRAPH: 1 once the full-batch forward pass has been captured and is being replayed,

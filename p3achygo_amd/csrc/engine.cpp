@@ -26,6 +26,7 @@
 
 #include "../../include/p3hip.h"
 #include "kernels.h"
+#include "lconv_i8.h"
 #include "slot_state.h"
 #include "transformer.h"
 
@@ -264,6 +265,10 @@ struct LayerPlan {
   int in_buf, out_buf, out2_buf;
   size_t stream_off = 0;
   int nms = 0;
+  // P3HIP_FLAG_INT8: the quantized weights (lconv_i8.h pack_lconv_i8), their per-output-channel scales, and the index of
+  // this layer's input among the engine's quantized tensors (its output, when quantized, is the next one: its consumer)
+  size_t q_off = 0, qs_off = 0;
+  int qidx = -1;
 };
 
 // One transformer block (kind 5): arena offsets of its tensors, the GEMM weights as MFMA A fragments (transformer.h)
@@ -331,6 +336,14 @@ struct p3hip_engine {
   size_t heads_conv_a_off = 0, heads_image_off = 0;
   bool tfm = false;                     // transformer trunk (blocks of kind 5)
   size_t rope_cos_off = 0, rope_sin_off = 0;
+  // P3HIP_FLAG_INT8: the layer-wise blocks' convs run on int8 inputs with per-tensor activation
+  // scales.  amax: running per-tensor maxima of the calibration runs (float bits, atomicMax); scale: the s_a = max / 127
+  // the int8 kernels read at launch time, so that a replayed graph sees new scales.
+  bool int8 = false, calibrating = false, have_scales = false;
+  int n_q = 0;
+  unsigned* d_amax = nullptr;
+  float* d_ascale = nullptr;
+  std::vector<float> h_scale;
   bool heads_fused = false;   // k_headsx: the head convs inside the heads kernel (C <= 256; P3HIP_NO_HFUSE clears it)
   std::map<std::string, size_t> head_off;
 
@@ -441,6 +454,11 @@ bool build_plan(p3hip_engine* e, Arena& ar) {
     return false;
   }
   e->tfm = tfm;
+  if (e->int8 && !layerwise) {
+    e->err = "INT8 is available only for layer-wise trunks (C = 384 / C_b = 192 btl or nbt blocks, C = 192 classic "
+             "blocks); this trunk runs fused block kernels or the transformer";
+    return false;
+  }
   // slice width of the per-position kernels that stage C channels (k_conv1x1 family)
   const int CB = classic ? 64 : ((layerwise || tfm) ? 128 : Cb);
   const int CPI = classic ? 64 : 128;   // output pass width of the init conv
@@ -636,6 +654,14 @@ bool build_plan(p3hip_engine* e, Arena& ar) {
         for (int cp = 0; cp < cout / 64; ++cp)
           for (int ip = 0; ip < cin / 64; ++ip) pack_segment(s, W(j, kw, cin, cout), kw * kw, kw * kw, cin, cout, ip * 64, 64, cp * 64, 64);
         lp.stream_off = add_stream(ar, s, lp.nms, 64);
+        if (e->int8) {
+          std::vector<int8_t> q;
+          std::vector<float> sw;
+          p3::pack_lconv_i8(q, sw, W(j, kw, cin, cout), kw * kw, cin, cout);
+          lp.q_off = ar.add(q.data(), q.size());
+          lp.qs_off = ar.add(sw.data(), sw.size() * 4);
+          lp.qidx = e->n_q++;
+        }
         bp.layers.push_back(lp);
       };
       const bool from_xa = have_xa;          // first layer input: activated copy in u, or raw x with pre
@@ -1078,7 +1104,38 @@ bool enqueue_forward(p3hip_engine* e, int npos) {
     } else if (bp.kind == 4) {
       const size_t half = (size_t)e->batch * wf.Cb * kNLoc;   // elements of one C_b-channel tensor
       _Float16* bufs[5] = {e->d_x, e->d_t, e->d_t + half, e->d_u, e->d_u + half};
+      if (e->int8 && !e->calibrating) {
+        // the int8 plan: the same regions, an int8 tensor where the fp16 plan stores an activated one
+        if (!e->have_scales) {
+          e->err = "INT8 engine has no activation scales: run p3hip_int8_calibrate on calibration batches or load a "
+                   "saved calibration with p3hip_int8_set_scales first";
+          return false;
+        }
+        for (const LayerPlan& lp : bp.layers) {
+          p3::LConvI8Args a{};
+          a.in = bufs[lp.in_buf]; a.out = bufs[lp.out_buf]; a.npos = npos;
+          a.out2 = lp.out2_buf >= 0 ? (int8_t*)bufs[lp.out2_buf] : nullptr;
+          a.w = e->dev<int8_t>(lp.q_off); a.w_scale = e->dev<float>(lp.qs_off);
+          a.act_scale = e->d_ascale; a.in_scale = lp.qidx; a.out_scale = lp.qidx + 1;
+          a.pre = lp.pre; a.act = lp.act; a.res = lp.res; a.dual = lp.dual;
+          if (a.pre) { a.scale_in = e->dev<float>(lp.pre_bn.scale_off); a.shift_in = e->dev<float>(lp.pre_bn.shift_off); }
+          if (a.act || a.dual) { a.scale_out = e->dev<float>(lp.out_bn.scale_off); a.shift_out = e->dev<float>(lp.out_bn.shift_off); }
+          const bool timed = e->time_blocks && lp.kw == 3 && 2 * e->timed_blocks + 1 < (int)e->blk_ev.size();
+          if (timed) hipEventRecord(e->blk_ev[2 * e->timed_blocks], s);
+          if (!e->check(p3::launch_lconv_i8(lp.kw, lp.cin, lp.cout, a, s), "launch k_lconv_i8")) return false;
+          if (timed) hipEventRecord(e->blk_ev[2 * e->timed_blocks++ + 1], s);
+        }
+        continue;
+      }
       for (const LayerPlan& lp : bp.layers) {
+        if (e->calibrating) {
+          // MinMax calibration: the absmax of this conv's quantized input, the activated tensor (pre: mish(bn0(x)),
+          // which the fp16 plan never stores) folded into the running maximum
+          p3::AbsmaxArgs m{};
+          m.in = bufs[lp.in_buf]; m.npos = npos; m.C = lp.cin; m.amax = e->d_amax + lp.qidx;
+          if (lp.pre) { m.scale = e->dev<float>(lp.pre_bn.scale_off); m.shift = e->dev<float>(lp.pre_bn.shift_off); }
+          if (!e->check(p3::launch_absmax(m, e->n_cu, s), "launch k_absmax")) return false;
+        }
         p3::LConvArgs a{};
         a.in = bufs[lp.in_buf]; a.out = bufs[lp.out_buf]; a.npos = npos;
         a.out2 = lp.out2_buf >= 0 ? bufs[lp.out2_buf] : nullptr;
@@ -1166,7 +1223,8 @@ bool enqueue_forward(p3hip_engine* e, int npos) {
 // kernel by kernel (the launchers set their kernels' LDS attributes on first use, which a capture must not see),
 // the second is captured, the rest replay.  A capture that fails falls back to the launches for good.
 bool run_forward(p3hip_engine* e, int npos) {
-  const bool want = (e->flags & P3HIP_FLAG_LAUNCH_GRAPH) && npos == e->batch && !e->time_blocks && !e->graph_failed;
+  const bool want = (e->flags & P3HIP_FLAG_LAUNCH_GRAPH) && npos == e->batch && !e->time_blocks && !e->graph_failed &&
+                    !e->calibrating;   // calibration runs (the fp16 plan + absmax) go kernel by kernel
   if (!want) return enqueue_forward(e, npos);
   // The capture bakes every kernel argument in, k_init's feature pointer among them, and run_cached points
   // e->d_feats at the cache's gathered copy around its forward pass: a graph captured for one buffer must never be
@@ -1219,6 +1277,7 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
   e->flags = flags;
   e->c128_wg8 = getenv("P3HIP_C128_WG8") != nullptr;
   e->bcast_fuse = getenv("P3HIP_NO_BFUSE") == nullptr;
+  e->int8 = (flags & P3HIP_FLAG_INT8) != 0;
   auto fail = [&](const std::string& m) {
     g_create_error = m;
     p3hip_destroy(e);
@@ -1258,8 +1317,13 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
             (e->wf.btype != 1 || e->check(hipMalloc((void**)&e->d_s, B * e->wf.Cb * kNLoc * 2), "hipMalloc s")) &&
             (!e->tfm || e->check(hipMalloc((void**)&e->d_qkv, qkv_bytes), "hipMalloc qkv")) &&
             e->check(hipMalloc((void**)&e->d_hp, B * 96 * kNLoc * 4), "hipMalloc hp") &&
-            e->check(hipMalloc((void**)&e->d_out, B * p3::kOutStride * 4), "hipMalloc out");
+            e->check(hipMalloc((void**)&e->d_out, B * p3::kOutStride * 4), "hipMalloc out") &&
+            (!e->int8 || (e->check(hipMalloc((void**)&e->d_amax, (size_t)e->n_q * 4), "hipMalloc amax") &&
+                          e->check(hipMalloc((void**)&e->d_ascale, (size_t)e->n_q * 4), "hipMalloc scales") &&
+                          e->check(hipMemsetAsync(e->d_amax, 0, (size_t)e->n_q * 4, e->stream), "hipMemset amax") &&
+                          e->check(hipMemsetAsync(e->d_ascale, 0, (size_t)e->n_q * 4, e->stream), "hipMemset scales")));
   if (!ok) return fail(e->err);
+  e->h_scale.assign(e->n_q, 0.0f);
   memset(e->h_feats, 0, B * kFeatBytes);
   if (!e->check(hipMemsetAsync(e->d_feats, 0, B * kFeatBytes, e->stream), "hipMemset feats") ||
       (e->tfm && !e->check(hipMemsetAsync(e->d_qkv, 0, qkv_bytes, e->stream), "hipMemset qkv")) ||
@@ -1278,6 +1342,7 @@ void p3hip_destroy(p3hip_engine* e) {
   hipFree(e->d_arena); hipFree(e->d_feats); hipFree(e->d_x); hipFree(e->d_t); hipFree(e->d_u); hipFree(e->d_s);
   hipFree(e->d_hp); hipFree(e->d_out); hipFree(e->d_res); hipFree(e->d_qkv);
   hipFree(e->d_bw_stamps);
+  hipFree(e->d_amax); hipFree(e->d_ascale);
   if (e->bw_mod) hipModuleUnload(e->bw_mod);
   {
     auto& c = e->cache;
@@ -1405,6 +1470,63 @@ static int gather_loaded(p3hip_engine* e) {
   return n;
 }
 
+// An INT8 engine runs only once it has activation scales (the reference refuses --use_int8 without a calibration set)
+static bool int8_ready(p3hip_engine* e) {
+  if (!e->int8 || e->calibrating || e->have_scales) return true;
+  e->err = "INT8 engine has no activation scales: run p3hip_int8_calibrate on calibration batches or load a saved "
+           "calibration with p3hip_int8_set_scales first";
+  return false;
+}
+
+int p3hip_int8_calibrate(p3hip_engine* e) {
+  if (!e->int8) { e->err = "p3hip_int8_calibrate: the engine was not created with P3HIP_FLAG_INT8"; return 1; }
+  if (!e->bind()) return 1;
+  e->calibrating = true;
+  e->last_n = 0;
+  const int rc = p3hip_run(e);
+  e->calibrating = false;
+  if (rc != 0) return rc;
+  if (e->last_n <= 0) { e->err = "p3hip_int8_calibrate: no loaded positions to calibrate on"; return 1; }
+  std::vector<unsigned> bits(e->n_q);
+  if (!e->check(hipMemcpyAsync(bits.data(), e->d_amax, (size_t)e->n_q * 4, hipMemcpyDeviceToHost, e->stream), "D2H amax") ||
+      !e->check(hipStreamSynchronize(e->stream), "sync")) return 1;
+  for (int i = 0; i < e->n_q; ++i) {
+    float m;
+    memcpy(&m, &bits[i], 4);
+    e->h_scale[i] = m / 127.0f;
+  }
+  if (!e->check(hipMemcpyAsync(e->d_ascale, e->h_scale.data(), (size_t)e->n_q * 4, hipMemcpyHostToDevice, e->stream), "H2D scales") ||
+      !e->check(hipStreamSynchronize(e->stream), "sync")) return 1;
+  e->have_scales = true;
+  return 0;
+}
+
+int p3hip_int8_scales(const p3hip_engine* e, float* out, int n) {
+  if (!e->int8) return -1;
+  for (int i = 0; i < n && i < e->n_q; ++i) out[i] = e->h_scale[i];
+  return e->n_q;
+}
+
+int p3hip_int8_set_scales(p3hip_engine* e, const float* scales, int n) {
+  if (!e->int8) { e->err = "p3hip_int8_set_scales: the engine was not created with P3HIP_FLAG_INT8"; return 1; }
+  if (n != e->n_q) {
+    e->err = "p3hip_int8_set_scales: " + std::to_string(n) + " scales given, the engine has " + std::to_string(e->n_q) +
+             " quantized tensors";
+    return 1;
+  }
+  for (int i = 0; i < n; ++i)
+    if (!(scales[i] >= 0.0f) || !std::isfinite(scales[i])) { e->err = "p3hip_int8_set_scales: bad scale"; return 1; }
+  if (!e->bind()) return 1;
+  // the running maxima restart from the loaded calibration: a later p3hip_int8_calibrate widens it
+  std::vector<float> amax(n);
+  for (int i = 0; i < n; ++i) { e->h_scale[i] = scales[i]; amax[i] = scales[i] * 127.0f; }
+  if (!e->check(hipMemcpyAsync(e->d_ascale, e->h_scale.data(), (size_t)n * 4, hipMemcpyHostToDevice, e->stream), "H2D scales") ||
+      !e->check(hipMemcpyAsync(e->d_amax, amax.data(), (size_t)n * 4, hipMemcpyHostToDevice, e->stream), "H2D amax") ||
+      !e->check(hipStreamSynchronize(e->stream), "sync")) return 1;
+  e->have_scales = true;
+  return 0;
+}
+
 int p3hip_upload(p3hip_engine* e) {
   if (!e->bind()) return 1;
   int n = gather_loaded(e);
@@ -1415,7 +1537,7 @@ int p3hip_upload(p3hip_engine* e) {
 }
 
 int p3hip_forward_resident(p3hip_engine* e, int n_positions) {
-  if (n_positions < 1 || n_positions > e->batch || !e->bind()) return 1;
+  if (n_positions < 1 || n_positions > e->batch || !e->bind() || !int8_ready(e)) return 1;
   return run_forward(e, n_positions) ? 0 : 1;
 }
 
@@ -1495,10 +1617,10 @@ static int run_cached(p3hip_engine* e, int n) {
 }
 
 int p3hip_run(p3hip_engine* e) {
-  if (!e->bind()) return 1;
+  if (!e->bind() || !int8_ready(e)) return 1;
   int n = gather_loaded(e);
   if (n == 0) return 0;
-  if (e->cache.on) return run_cached(e, n);
+  if (e->cache.on && !e->calibrating) return run_cached(e, n);   // calibration evaluates every slot, stores nothing
   if (!e->check(hipMemcpyAsync(e->d_feats, e->feats_identity ? e->h_feats : e->h_feats_compact, (size_t)n * kFeatBytes,
                                hipMemcpyHostToDevice, e->stream), "H2D features")) return 1;
   // The heads kernel writes the result records (the first kResultFloats of an output row) a second time into a dense
@@ -1677,7 +1799,7 @@ double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
       }
     }
     if (flops_per_launch) *flops_per_launch = 2.0 * n_positions * kNLoc * 9.0 * c3 * c3;
-    if (kernel_name) *kernel_name = c3 == 192 ? "k_lconv<3,192,192>" : "k_lconv<3,64,64>";
+    if (kernel_name) *kernel_name = e->int8 ? p3::lconv_i8_kernel_name(3, c3, c3) : (c3 == 192 ? "k_lconv<3,192,192>" : "k_lconv<3,64,64>");
     return launches ? total_ms / launches : -1.0;
   }
   if (!bp) return -1.0;

@@ -30,11 +30,13 @@ EXPORTS = [
     "p3hip_time_trunk_kernel", "p3hip_flops_per_position", "p3hip_graph_state",
     "p3hip_cache_enable", "p3hip_load_slot_keyed", "p3hip_get_slot_keyed", "p3hip_cache_stats",
     "p3hip_blockw_stamps", "p3hip_debug_x", "p3hip_rope_table",
+    "p3hip_int8_calibrate", "p3hip_int8_scales", "p3hip_int8_set_scales",
 ]
 
 FLAG_RUN_ALL_SLOTS = 2
 FLAG_SHARED_DEVICE = 4
 FLAG_LAUNCH_GRAPH = 8
+FLAG_INT8 = 16   # calibrated INT8 convs in the layer-wise blocks (include/p3hip.h)
 
 
 class EngineError(RuntimeError):
@@ -85,6 +87,9 @@ def lib():
         L.p3hip_load_slot_keyed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int]
         L.p3hip_get_slot_keyed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.p3hip_cache_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        L.p3hip_int8_calibrate.argtypes = [C.c_void_p]
+        L.p3hip_int8_scales.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.p3hip_int8_set_scales.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.p3hip_time_trunk_kernel.restype = C.c_double
         L.p3hip_time_trunk_kernel.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double),
                                               C.POINTER(C.c_char_p)]
@@ -176,6 +181,26 @@ class HipEngine:
         out = (C.c_uint64 * 4)()
         self._L.p3hip_cache_stats(self._h, out)
         return {"lookups": out[0], "hits": out[1], "stored": out[2], "entries": out[3]}
+
+    # -- calibrated INT8 (FLAG_INT8) -----------------------------------------------------
+    def int8_calibrate(self) -> None:
+        """RunInference on the fp16 plan that also folds every quantized tensor's max |v| into the engine's running
+        maxima (MinMax calibration): load a calibration batch, call this, fetch results as usual if wanted."""
+        self._ck(self._L.p3hip_int8_calibrate(self._h), "int8_calibrate")
+
+    def int8_scales(self) -> np.ndarray:
+        """The activation scales s_a = max / 127, block by block, conv by conv (the calibration cache)."""
+        n = self._L.p3hip_int8_scales(self._h, None, 0)
+        if n < 0:
+            raise EngineError("int8_scales: the engine was not created with FLAG_INT8")
+        out = np.zeros(n, np.float32)
+        self._L.p3hip_int8_scales(self._h, out.ctypes.data, n)
+        return out
+
+    def set_int8_scales(self, scales) -> None:
+        """Loads a saved calibration (what int8_scales returned)."""
+        s = np.ascontiguousarray(scales, np.float32)
+        self._ck(self._L.p3hip_int8_set_scales(self._h, s.ctypes.data, len(s)), "set_int8_scales")
 
     # -- measurement / test hooks -------------------------------------------------------
     def load_all(self, feats_rec: np.ndarray) -> None:
