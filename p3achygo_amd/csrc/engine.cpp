@@ -308,6 +308,7 @@ struct p3hip_engine {
   bool c128_wg8 = false;   // P3HIP_C128_WG8: C = 128 blocks as one 8-wave workgroup per CU (A/B timing)
   bool runs_contiguous = false;   // build_plan laid every run's streams back to back (joined launches possible)
   bool bcast_fuse = true;  // P3HIP_NO_BFUSE clears it: broadcast 1x1 convs as their own launches (A/B, tests)
+  int stop_block = -1;     // P3HIP_DEBUG_STOP_BLOCK at create: the forward pass ends in front of plan block n (debugging, tests)
   // k_blockw (csrc/asm/blockw_gen.py): the runs of C = 256 btl blocks by the hand-scheduled one-wave-per-SIMD kernel
   bool blockw = false;
   struct BlockwRun { size_t first; int nblk; size_t stream_off, prm_off; };
@@ -1065,8 +1066,9 @@ bool enqueue_forward(p3hip_engine* e, int npos) {
 #ifdef P3_DIAG
   e->launch_index = 0;
 #endif
-  // debugging aid (tools/gpu_blockw_ab.py xdiff): stop the forward pass in front of plan block P3HIP_DEBUG_STOP_BLOCK
-  static const int stop_block = getenv("P3HIP_DEBUG_STOP_BLOCK") ? atoi(getenv("P3HIP_DEBUG_STOP_BLOCK")) : -1;
+  // debugging aid (tools/gpu_blockw_ab.py xdiff, tests/test_trunk_blocks_gpu.py): stop the forward pass in front of
+  // plan block e->stop_block (P3HIP_DEBUG_STOP_BLOCK when the engine was created)
+  const int stop_block = e->stop_block;
   for (size_t bi = 0; bi < e->blocks.size(); ++bi) {
     if (stop_block >= 0 && (int)bi >= stop_block) return true;
     const BlockPlan& bp = e->blocks[bi];
@@ -1277,6 +1279,7 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
   e->flags = flags;
   e->c128_wg8 = getenv("P3HIP_C128_WG8") != nullptr;
   e->bcast_fuse = getenv("P3HIP_NO_BFUSE") == nullptr;
+  e->stop_block = getenv("P3HIP_DEBUG_STOP_BLOCK") ? atoi(getenv("P3HIP_DEBUG_STOP_BLOCK")) : -1;
   e->int8 = (flags & P3HIP_FLAG_INT8) != 0;
   auto fail = [&](const std::string& m) {
     g_create_error = m;

@@ -302,7 +302,8 @@ import sys, hashlib, tempfile, os
 sys.path.insert(0, %r)
 import numpy as np
 from p3achygo_amd import engine, features, netspec
-for name, batch in (("b12c256btl3", 300), ("b8c128nbt", 70), ("b12c256btl3", 5)):
+for name, batch in (("b12c256btl3", 300), ("b8c128nbt", 70), ("b12c256btl3", 5), ("test_b3c128btl2", 37),
+                    ("test_b3c256nbt", 37), ("test_b5c128btl1_i2", 37), ("test_b5c256btl2_i2", 37)):
     cfg = netspec.CONFIGS[name]
     path = os.path.join(tempfile.mkdtemp(), "n.p3w")
     netspec.save_p3w(path, cfg, netspec.generate_weights(cfg, randomize=True))
@@ -321,7 +322,8 @@ def test_fused_block_launches_equal_one_launch_per_block(built):
     positions, so there is no grid-wide dependency between blocks).  Same arithmetic, same
     order: the outputs must be bit-identical to one launch per block (P3HIP_NO_FUSE), with
     several positions per workgroup (300), with two per workgroup slot (C=128, 70) and with
-    fewer positions than workgroups (5)."""
+    fewer positions than workgroups (5); every fused-trunk family (C = 128 and 256, btl and nbt, _i2), which ties the
+    shipping launches to the per-block path tests/test_trunk_blocks_gpu.py checks."""
     import subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     outs = []
@@ -333,7 +335,7 @@ def test_fused_block_launches_equal_one_launch_per_block(built):
         r = subprocess.run([sys.executable, "-c", _FUSE_CHILD % root], env=env, capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stderr[-2000:]
         outs.append(r.stdout)
-    assert outs[0] == outs[1] and outs[0].count("\n") == 3
+    assert outs[0] == outs[1] and outs[0].count("\n") == 7
 
 
 _BFUSE_CHILD = r"""
