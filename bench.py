@@ -19,8 +19,8 @@ group each).  Then exactly K rounds are timed inside the host: the window opens 
 last warm-up batch — that group is the ANCHOR — and closes at the completion of the anchor's K-th batch
 after it (its own steady clock; every engine run ends with its stream drained), so both ends sit at the
 same phase of the groups' cycle; every batch of any group that completes inside is counted (K per group in
-steady state).  The line flags itself (`window_artifact`) if its per-batch time is below the dominant
-kernel's own launch time.  Barriers bracket the region; the slowest rank's time is the job's time.  Games shard embarrassingly across GPUs (one
+steady state).  Under `--full` the line flags itself (`window_artifact`) if its per-batch time is below the
+dominant kernel's own launch time.  Barriers bracket the region; the slowest rank's time is the job's time.  Games shard embarrassingly across GPUs (one
 process, one engine set, one HIP stream set per device; no data-path collective): weak scaling.
 `--gpus N` without WORLD_SIZE in the environment starts the N rank processes itself (before anything
 touches the GPU); under torch.distributed.run it checks N against WORLD_SIZE.
@@ -28,7 +28,9 @@ touches the GPU); under torch.distributed.run it checks N against WORLD_SIZE.
 (p3hip_result fields over a fixed seeded batch of leaf positions) as DIR/<field>.npy, so that two builds can be
 compared output for output.
 
-Secondary figures in the same JSON line:
+A plain run does only what the headline needs: set-up, the advance phase, the warm-up, the K timed rounds,
+`--dump-outputs` if given, and the JSON line (`roofline` and `cpu_baseline` null).  `--full` adds the secondary
+figures to the same line, each a run of its own after the timed rounds:
   engine_only  — forward pass alone over a resident batch (no host, no PCIe), with the shader clock and socket power
                  amdsmi reports while it loops (`chip_during_loop`);
   engine_benchmark — the reference's nn::Benchmark loop (benchmark_engine.cc:77-108) from C++ over the C ABI;
@@ -58,7 +60,7 @@ DEFAULT_GROUPS = GROUPS = 8          # game groups per GPU: forward passes of th
                                      # (round 4: ONE group filling two engine batches in turn — `--groups 1 --lanes 2`, the stated 1024 games
                                      # — measures 219-225 k where eight one-lane groups measure 220-228 k on the same box; the headline stays
                                      # at eight groups because one slow game (an exact ladder read-out) stalls a lone group's pipeline and a
-                                     # 20-round window is then 0.2 s long; both are in every line)
+                                     # 20-round window is then 0.2 s long; both are in every --full line)
                                      # (round 2: 4 / 6 / 8 / 12 groups 217 / 222 / 220 / 220 k positions/s on one box; round 3, the forward
                                      # pass one long launch: 4 / 6 / 8 groups 225 / 237 / 241 k with 241 k engine-only, and the driver's
                                      # 20-step window steadier with eight: 239-242 k against 209-242 k)
@@ -253,20 +255,24 @@ def main():
     ap.add_argument("--lanes", type=int, default=1,
                     help="engine instances (HIP streams) per game group, filled in turn by the group's games; 1 (default) = "
                          "host and GPU alternate within a group and the other groups keep the GPU busy; `--groups 1 --lanes 2` "
-                         "is BASELINE configs[2] as stated, the `as_stated_c3` leg of the default run")
+                         "is BASELINE configs[2] as stated, the `as_stated_c3` leg of a --full run")
     ap.add_argument("--inflight", type=int, default=4,
                     help="playouts of one game's search that may wait for results at once when --lanes > 1")
     ap.add_argument("--model", default=MODEL)
     ap.add_argument("--advance-limit", type=int, default=64,
                     help="untimed batches per group, at most, that play every game past its raw-policy opening "
                          "before the warm-up (0 = start timing inside the openings, as rounds 1-2 did)")
-    ap.add_argument("--engine-steps", type=int, default=200, help="timed steps of the engine-only leg")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the live HBM-traffic measurement (two rocprofv3 --pmc child runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed rounds, also run the secondary legs (engine-only, roofline with live HBM traffic, "
+                         "engine_benchmark, as_stated_c3, CPU baseline) and add their figures to the line")
+    ap.add_argument("--engine-steps", type=int, default=200, help="timed steps of the engine-only leg (--full)")
+    ap.add_argument("--no-pmc", action="store_true",
+                    help="--full: skip the live HBM-traffic measurement (two rocprofv3 --pmc child runs)")
     ap.add_argument("--ladder-budget", type=int, default=LADDER_BUDGET,
                     help="ladder read-out work bound of the self-play host (0 = reference-exact, the default; "
                          "> 0 = the opt-in throughput mode, hits are reported)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the engine_benchmark and as_stated_c3 legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the engine_benchmark and as_stated_c3 legs")
     ap.add_argument("--null-engine", action="store_true",
                     help="plumbing rehearsal without a GPU: the host over its NullEvaluator (uniform policy); "
                          "the line it prints is marked as not a measurement")
@@ -389,16 +395,20 @@ def main():
             "value_fit": totals[0] / dt_fit, "seconds_timed_fit": dt_fit,
         }
 
-    if not use_gpu:
+    if not use_gpu or not args.full:
+        sharding.barrier(shard)
         if rank == 0:
             out = headline()
-            out["engine"] = "NullEvaluator (uniform policy): a plumbing rehearsal of the launch path, NOT a measurement"
+            if not use_gpu:
+                out["engine"] = "NullEvaluator (uniform policy): a plumbing rehearsal of the launch path, NOT a measurement"
+            if dumped is not None:
+                out["dumped_outputs"] = dumped
             out["roofline"] = out["cpu_baseline"] = None
             print(json.dumps(out), flush=True)
         sharding.finish(shard)
         return
 
-    # ---- secondary: the engine alone over a resident batch ----------------------------------
+    # ---- secondary (--full): the engine alone over a resident batch --------------------------
     eng = engine.create_engine(engine.kind_from_engine_path(path), path, args.batch, 1, device=local_rank)
     eng.load_all(pos)
     eng.upload()

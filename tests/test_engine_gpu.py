@@ -914,7 +914,7 @@ def test_launch_graph_with_the_nn_cache_never_replays_the_other_feature_buffer(b
 
 
 def test_bench_line_keeps_its_contract_and_its_self_checks(built, tmp_path):
-    """bench.py's one JSON line on the GPU (a short run: 8 rounds, no CPU baseline, no counter passes): the driver's keys,
+    """bench.py --full's one JSON line on the GPU (a short run: 8 rounds, no CPU baseline, no counter passes): the driver's keys,
     a steady-state headline (per-batch time not below the trunk launch's own time, value not above what the forward pass
     alone does by more than the streams' overlap allows), the roofline object, and the chip's state beside the engine-only leg.
     `--dump-outputs`: one batch of the timed path's results over fixed seeded leaves, float32 and well formed."""
@@ -923,8 +923,8 @@ def test_bench_line_keeps_its_contract_and_its_self_checks(built, tmp_path):
     import sys
     from conftest import ROOT
     dump = tmp_path / "dump"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "2", "--no-cpu-baseline",
-                        "--no-pmc", "--no-extras", "--engine-steps", "60", "--dump-outputs", str(dump)],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "8", "--warmup", "2",
+                        "--no-cpu-baseline", "--no-pmc", "--no-extras", "--engine-steps", "60", "--dump-outputs", str(dump)],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -954,3 +954,38 @@ def test_bench_line_keeps_its_contract_and_its_self_checks(built, tmp_path):
     for f in ("move_probs", "value_probs", "score_probs"):
         assert np.allclose(got[f].sum(axis=1), 1.0, atol=1e-3), f
     assert sum(a.nbytes for a in got.values()) <= 64 << 20
+
+
+def test_bench_plain_line_is_the_headline_alone(built, tmp_path):
+    """A plain bench.py run (no --full) sets up, warms up, times its rounds, dumps and prints the line, and nothing else:
+    the headline keys are there, the secondary legs are not, and the whole run spends at most 30 s outside its warm-up
+    and timed rounds."""
+    import json
+    import subprocess
+    import sys
+    import time
+    from conftest import ROOT
+    dump = tmp_path / "dump"
+    steps, warmup = 8, 2
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warmup),
+                        "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                "vs_baseline", "dtype", "data", "config"):
+        assert key in d, key
+    assert d["n_gpus"] == 1 and d["steps"] == steps and d["warmup"] == warmup and d["dtype"] == "f16"
+    assert d["higher_is_better"] is True and d["unit"] == "positions/s" and d["value"] > 0
+    assert d["ms_per_step"] == pytest.approx(d["seconds_timed"] / steps * 1e3)
+    assert d["engine_batches_completed"] >= 8 * steps - 8 and d["mean_batch_fill"] > 0.99
+    assert d["roofline"] is None and d["cpu_baseline"] is None
+    for key in ("engine_only", "engine_benchmark", "as_stated_c3", "window_artifact", "conv3x3_mfma_frac_end_to_end"):
+        assert key not in d, key
+    assert d["dumped_outputs"]["rows"] == 1024
+    assert sorted(p.name for p in dump.iterdir()) == sorted(f"{f}.npy" for f in d["dumped_outputs"]["fields"])
+    outside = wall - (steps + warmup) * d["ms_per_step"] * 1e-3
+    assert outside <= 30.0, f"{outside:.1f} s outside the warm-up and timed rounds"
