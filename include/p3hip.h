@@ -105,6 +105,10 @@ typedef struct p3hip_engine p3hip_engine;
                                        python/trt_convert.py, cc/nn/engine/trt_calibrator.h): the convs of the layer-wise
                                        blocks run on int8 inputs and weights.  Layer-wise trunks
                                        only: p3hip_create returns NULL for any other trunk.  See p3hip_int8_* below */
+#define P3HIP_FLAG_SYMMETRY_AVG 32u /* every slot a run evaluates is evaluated under each symmetry of the engine's set
+                                       (default: all eight) and the results averaged on the device, rotated back into the
+                                       orientation the slot was loaded in.  Needs 8 x batch_size <= 65536.  See
+                                       p3hip_set_symmetries below */
 
 /* Creates an engine from a `.p3w` weight file (see p3achygo_amd/netspec.py) for a static
  * batch of `batch_size` slots on HIP device `device_ordinal`.  `version` is the model
@@ -171,6 +175,22 @@ int p3hip_cache_stats(const p3hip_engine* e, uint64_t out[4]);
 int p3hip_int8_calibrate(p3hip_engine* e);
 int p3hip_int8_scales(const p3hip_engine* e, float* out, int n);
 int p3hip_int8_set_scales(p3hip_engine* e, const float* scales, int n);
+
+/* ---- symmetry-averaged evaluation (P3HIP_FLAG_SYMMETRY_AVG) --------------------------------------------------
+ * The copies of a slot are ordered by ascending symmetry index s (the enum order of cc/game/symmetry.h: identity, rot90,
+ * rot180, rot270, flip, flipRot90, flipRot180, flipRot270).  Copy j is the slot's features under symmetry s_j, as
+ * FillFeatures would have built them: the five grids moved by the forward map (out[fwd[s][i]] = in[i]), on-board last
+ * moves through the forward map, every other location (pass {19,0}, noop {-1,-1}) and colour, komi, bsize copied.
+ * After the forward pass the board-indexed outputs of every copy are rotated back with the inverse map (entries
+ * 0..360 of the move logits, move probabilities, opt-policy logits and opt-policy probabilities, and the ownership
+ * map; out[inv[s][i]] = in[i]); then every float of the output row is acc = v_0; acc += v_1; ...; acc / (float)k in
+ * fp32, correctly rounded.  p3hip_get_slot, p3hip_get_slot_keyed, p3hip_get_ownership and p3hip_get_raw return that
+ * average.  With one symmetry in the set the result is that copy itself.
+ *   p3hip_set_symmetries  bit s of mask selects symmetry s; 1..255.  Fails on 0, above 255, and on an engine created
+ *                         without the flag.  Applies from the next run.
+ *   p3hip_symmetry_maps   the forward and inverse index maps of the 19 x 19 board the kernels use.  Needs no device. */
+int p3hip_set_symmetries(p3hip_engine* e, uint32_t mask);
+void p3hip_symmetry_maps(uint16_t fwd[8][361], uint16_t inv[8][361]);
 
 /* ---- measurement / test hooks (not part of the reference surface) ------------------ */
 

@@ -28,6 +28,7 @@
 #include "kernels.h"
 #include "lconv_i8.h"
 #include "slot_state.h"
+#include "symmetry.h"
 #include "transformer.h"
 
 namespace {
@@ -345,6 +346,17 @@ struct p3hip_engine {
   unsigned* d_amax = nullptr;
   float* d_ascale = nullptr;
   std::vector<float> h_scale;
+  // P3HIP_FLAG_SYMMETRY_AVG: every slot is evaluated as k copies, one per symmetry of the mask,
+  // and the rows averaged back into d_out.  rows: the row capacity of the per-row device buffers (8 x batch with the
+  // flag, batch without).  The upload lands in d_sfeats, k_sym_expand writes the copies to d_feats, the heads write the
+  // copies' rows to d_cout, k_sym_reduce averages them into d_out (and d_res).
+  bool sym = false;
+  uint32_t sym_mask = 0xFF;
+  int sym_k = 8;
+  int sym_syms[p3::kNumSyms] = {0, 1, 2, 3, 4, 5, 6, 7};
+  int rows = 0;
+  unsigned char* d_sfeats = nullptr;
+  float* d_cout = nullptr;
   bool heads_fused = false;   // k_headsx: the head convs inside the heads kernel (C <= 256; P3HIP_NO_HFUSE clears it)
   std::map<std::string, size_t> head_off;
 
@@ -1073,7 +1085,7 @@ bool enqueue_forward(p3hip_engine* e, int npos) {
     if (stop_block >= 0 && (int)bi >= stop_block) return true;
     const BlockPlan& bp = e->blocks[bi];
     if (bp.kind == 5) {
-      const size_t per = (size_t)e->batch * p3::kTfmHeads * p3::kTfmLPad * p3::kTfmD;   // one of q, k, v
+      const size_t per = (size_t)e->rows * p3::kTfmHeads * p3::kTfmLPad * p3::kTfmD;   // one of q, k, v
       _Float16 *q = e->d_qkv, *k = q + per, *v = k + per, *o = e->d_t;
       p3::TfmQkvArgs a{e->d_x, q, k, v, npos, e->dev<float>(bp.tfm.rms_in), e->d_arena + bp.tfm.wqkv,
                        e->dev<float>(e->rope_cos_off), e->dev<float>(e->rope_sin_off)};
@@ -1104,7 +1116,7 @@ bool enqueue_forward(p3hip_engine* e, int npos) {
       c1.wstream = e->d_arena + bp.stream3_off; c1.nms_total = bp.nms3;
       if (!bp.last_fused && !e->check(p3::launch_conv1x1(C, 1, c1, e->n_cu, s), "launch conv_last")) return false;
     } else if (bp.kind == 4) {
-      const size_t half = (size_t)e->batch * wf.Cb * kNLoc;   // elements of one C_b-channel tensor
+      const size_t half = (size_t)e->rows * wf.Cb * kNLoc;   // elements of one C_b-channel tensor
       _Float16* bufs[5] = {e->d_x, e->d_t, e->d_t + half, e->d_u, e->d_u + half};
       if (e->int8 && !e->calibrating) {
         // the int8 plan: the same regions, an int8 tensor where the fp16 plan stores an activated one
@@ -1196,7 +1208,7 @@ bool enqueue_forward(p3hip_engine* e, int npos) {
     h.x = e->d_x;
     h.conv_a = e->d_arena + e->heads_conv_a_off;
     h.image = e->dev<float>(e->heads_image_off);
-    h.hp = e->d_hp; h.out = e->d_out; h.npos = npos; h.V = wf.V;
+    h.hp = e->d_hp; h.out = e->sym ? e->d_cout : e->d_out; h.npos = npos; h.V = wf.V;
     h.res = e->run_direct ? e->d_res : nullptr;
     auto F = [&](const char* n) { return e->dev<float>(e->head_off.at(n)); };
     h.gbn_scale = F("gbn_scale"); h.gbn_shift = F("gbn_shift");
@@ -1224,27 +1236,26 @@ bool enqueue_forward(p3hip_engine* e, int npos) {
 // kernel-by-kernel launches otherwise and for every other position count.  The first full-batch run goes out
 // kernel by kernel (the launchers set their kernels' LDS attributes on first use, which a capture must not see),
 // the second is captured, the rest replay.  A capture that fails falls back to the launches for good.
-bool run_forward(p3hip_engine* e, int npos) {
-  const bool want = (e->flags & P3HIP_FLAG_LAUNCH_GRAPH) && npos == e->batch && !e->time_blocks && !e->graph_failed &&
-                    !e->calibrating;   // calibration runs (the fp16 plan + absmax) go kernel by kernel
-  if (!want) return enqueue_forward(e, npos);
+// `enqueue` puts the whole pass on the stream; `feats` is the feature buffer it reads (kernel arguments are baked in).
+bool run_captured(p3hip_engine* e, bool want, const unsigned char* feats, const std::function<bool()>& enqueue) {
+  if (!want) return enqueue();
   // The capture bakes every kernel argument in, k_init's feature pointer among them, and run_cached points
   // e->d_feats at the cache's gathered copy around its forward pass: a graph captured for one buffer must never be
   // replayed for the other.  The graph serves the buffer it was captured on; the other goes out kernel by kernel.
   if (e->graph_exec) {
-    if (e->d_feats != e->graph_feats || e->run_direct != e->graph_direct) return enqueue_forward(e, npos);
+    if (feats != e->graph_feats || e->run_direct != e->graph_direct) return enqueue();
     return e->check(hipGraphLaunch(e->graph_exec, e->stream), "hipGraphLaunch");
   }
   if (!e->graph_warm) {
     e->graph_warm = true;
-    return enqueue_forward(e, npos);
+    return enqueue();
   }
   if (hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
     e->graph_failed = true;
     (void)hipGetLastError();
-    return enqueue_forward(e, npos);
+    return enqueue();
   }
-  const bool ok = enqueue_forward(e, npos);
+  const bool ok = enqueue();
   hipGraph_t g = nullptr;
   const hipError_t ce = hipStreamEndCapture(e->stream, &g);
   if (!ok || ce != hipSuccess || !g || hipGraphInstantiate(&e->graph_exec, g, nullptr, nullptr, 0) != hipSuccess) {
@@ -1252,13 +1263,49 @@ bool run_forward(p3hip_engine* e, int npos) {
     e->graph_exec = nullptr;
     e->graph_failed = true;
     (void)hipGetLastError();
-    return enqueue_forward(e, npos);   // nothing was executed by the capture
+    return enqueue();   // nothing was executed by the capture
   }
   e->graph = g;
-  e->graph_feats = e->d_feats;
+  e->graph_feats = feats;
   e->graph_direct = e->run_direct;
   return e->check(hipGraphLaunch(e->graph_exec, e->stream), "hipGraphLaunch");
 }
+
+bool run_forward(p3hip_engine* e, int npos) {
+  const bool want = (e->flags & P3HIP_FLAG_LAUNCH_GRAPH) && npos == e->batch && !e->time_blocks && !e->graph_failed &&
+                    !e->calibrating;   // calibration runs (the fp16 plan + absmax) go kernel by kernel
+  return run_captured(e, want, e->d_feats, [&] { return enqueue_forward(e, npos); });
+}
+
+// P3HIP_FLAG_SYMMETRY_AVG: `n` slots' records in `src` -> k copies each in d_feats -> the forward pass over n k rows
+// (the heads write d_cout) -> the averaged rows in d_out rows 0 .. n - 1, and the result records in d_res when
+// e->run_direct.  The heads never write d_res themselves here (no run_direct for the copy pass).
+bool enqueue_sym(p3hip_engine* e, int n, const unsigned char* src) {
+  p3::SymExpandArgs x{};
+  x.in = src; x.out = e->d_feats; x.n = n; x.k = e->sym_k;
+  for (int j = 0; j < p3::kNumSyms; ++j) x.syms[j] = e->sym_syms[j];
+  if (!e->check(p3::launch_sym_expand(x, e->stream), "launch k_sym_expand")) return false;
+  const bool direct = e->run_direct;
+  e->run_direct = false;
+  const bool ok = enqueue_forward(e, n * e->sym_k);
+  e->run_direct = direct;
+  if (!ok) return false;
+  p3::SymReduceArgs r{};
+  r.rows = e->d_cout; r.out = e->d_out; r.res = direct ? e->d_res : nullptr; r.n = n; r.k = e->sym_k;
+  for (int j = 0; j < p3::kNumSyms; ++j) r.syms[j] = e->sym_syms[j];
+  return e->check(p3::launch_sym_reduce(r, e->stream), "launch k_sym_reduce");
+}
+
+// The symmetry pass of a run: on a full static batch with P3HIP_FLAG_LAUNCH_GRAPH one captured graph holds expand,
+// forward and reduce (same warm-up / capture / replay rule as run_forward).
+bool run_sym(p3hip_engine* e, int n, const unsigned char* src) {
+  const bool want = (e->flags & P3HIP_FLAG_LAUNCH_GRAPH) && n == e->batch && !e->time_blocks && !e->graph_failed &&
+                    !e->calibrating;
+  return run_captured(e, want, src, [&] { return enqueue_sym(e, n, src); });
+}
+
+// where p3hip_run / p3hip_upload put the slots' records: the forward pass's input, or the expand's
+unsigned char* upload_buffer(p3hip_engine* e) { return e->sym ? e->d_sfeats : e->d_feats; }
 
 }  // namespace
 
@@ -1272,6 +1319,12 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
   g_create_error.clear();
   if (version != 1) { g_create_error = "only model version 1 (15 planes + 8 scalars) is supported"; return nullptr; }
   if (batch_size < 1 || batch_size > (1 << 16)) { g_create_error = "bad batch size"; return nullptr; }
+  const bool sym = (flags & P3HIP_FLAG_SYMMETRY_AVG) != 0;
+  if (sym && (size_t)p3::kNumSyms * batch_size > (1u << 16)) {
+    g_create_error = "P3HIP_FLAG_SYMMETRY_AVG evaluates 8 copies of every slot: 8 x batch size " +
+                     std::to_string(batch_size) + " exceeds the engine's row limit of 65536 (batch size at most 8192)";
+    return nullptr;
+  }
   p3hip_engine* e = new p3hip_engine();
   e->path = weights_path;
   e->batch = batch_size;
@@ -1281,6 +1334,8 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
   e->bcast_fuse = getenv("P3HIP_NO_BFUSE") == nullptr;
   e->stop_block = getenv("P3HIP_DEBUG_STOP_BLOCK") ? atoi(getenv("P3HIP_DEBUG_STOP_BLOCK")) : -1;
   e->int8 = (flags & P3HIP_FLAG_INT8) != 0;
+  e->sym = sym;
+  e->rows = sym ? p3::kNumSyms * batch_size : batch_size;
   auto fail = [&](const std::string& m) {
     g_create_error = m;
     p3hip_destroy(e);
@@ -1301,7 +1356,8 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
   e->n_cu = prop.multiProcessorCount;
   const int C = e->wf.C;
   const size_t B = batch_size;
-  const size_t qkv_bytes = 3 * B * p3::kTfmHeads * p3::kTfmLPad * p3::kTfmD * 2;
+  const size_t R = e->rows;   // the per-row device buffers: 8 x batch copies with P3HIP_FLAG_SYMMETRY_AVG
+  const size_t qkv_bytes = 3 * R * p3::kTfmHeads * p3::kTfmLPad * p3::kTfmD * 2;
   bool ok = e->check(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking), "hipStreamCreate") &&
             e->check(hipEventCreate(&e->ev0), "hipEventCreate") &&
             e->check(hipEventCreate(&e->ev1), "hipEventCreate") &&
@@ -1313,14 +1369,16 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
             e->check(hipHostMalloc((void**)&e->h_feats_compact, B * kFeatBytes, hipHostMallocDefault), "hipHostMalloc") &&
             e->check(hipHostMalloc((void**)&e->h_out, B * p3::kResultFloats * 4, hipHostMallocDefault), "hipHostMalloc") &&
             e->check(hipMalloc((void**)&e->d_res, B * p3::kResultFloats * 4), "hipMalloc results") &&
-            e->check(hipMalloc((void**)&e->d_feats, B * kFeatBytes), "hipMalloc feats") &&
-            e->check(hipMalloc((void**)&e->d_x, B * C * kNLoc * 2), "hipMalloc x") &&
-            e->check(hipMalloc((void**)&e->d_t, B * C * kNLoc * 2), "hipMalloc t") &&
-            e->check(hipMalloc((void**)&e->d_u, B * C * kNLoc * 2), "hipMalloc u") &&
-            (e->wf.btype != 1 || e->check(hipMalloc((void**)&e->d_s, B * e->wf.Cb * kNLoc * 2), "hipMalloc s")) &&
+            e->check(hipMalloc((void**)&e->d_feats, R * kFeatBytes), "hipMalloc feats") &&
+            e->check(hipMalloc((void**)&e->d_x, R * C * kNLoc * 2), "hipMalloc x") &&
+            e->check(hipMalloc((void**)&e->d_t, R * C * kNLoc * 2), "hipMalloc t") &&
+            e->check(hipMalloc((void**)&e->d_u, R * C * kNLoc * 2), "hipMalloc u") &&
+            (e->wf.btype != 1 || e->check(hipMalloc((void**)&e->d_s, R * e->wf.Cb * kNLoc * 2), "hipMalloc s")) &&
             (!e->tfm || e->check(hipMalloc((void**)&e->d_qkv, qkv_bytes), "hipMalloc qkv")) &&
-            e->check(hipMalloc((void**)&e->d_hp, B * 96 * kNLoc * 4), "hipMalloc hp") &&
+            e->check(hipMalloc((void**)&e->d_hp, R * 96 * kNLoc * 4), "hipMalloc hp") &&
             e->check(hipMalloc((void**)&e->d_out, B * p3::kOutStride * 4), "hipMalloc out") &&
+            (!sym || (e->check(hipMalloc((void**)&e->d_sfeats, B * kFeatBytes), "hipMalloc symmetry upload") &&
+                      e->check(hipMalloc((void**)&e->d_cout, R * p3::kOutStride * 4), "hipMalloc copy rows"))) &&
             (!e->int8 || (e->check(hipMalloc((void**)&e->d_amax, (size_t)e->n_q * 4), "hipMalloc amax") &&
                           e->check(hipMalloc((void**)&e->d_ascale, (size_t)e->n_q * 4), "hipMalloc scales") &&
                           e->check(hipMemsetAsync(e->d_amax, 0, (size_t)e->n_q * 4, e->stream), "hipMemset amax") &&
@@ -1328,7 +1386,9 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
   if (!ok) return fail(e->err);
   e->h_scale.assign(e->n_q, 0.0f);
   memset(e->h_feats, 0, B * kFeatBytes);
-  if (!e->check(hipMemsetAsync(e->d_feats, 0, B * kFeatBytes, e->stream), "hipMemset feats") ||
+  if (!e->check(hipMemsetAsync(e->d_feats, 0, R * kFeatBytes, e->stream), "hipMemset feats") ||
+      (sym && !e->check(hipMemsetAsync(e->d_sfeats, 0, B * kFeatBytes, e->stream), "hipMemset symmetry upload")) ||
+      (sym && !e->check(hipMemsetAsync(e->d_cout, 0, R * p3::kOutStride * 4, e->stream), "hipMemset copy rows")) ||
       (e->tfm && !e->check(hipMemsetAsync(e->d_qkv, 0, qkv_bytes, e->stream), "hipMemset qkv")) ||
       !e->check(hipMemsetAsync(e->d_out, 0, B * p3::kOutStride * 4, e->stream), "hipMemset out") ||
       !e->check(hipStreamSynchronize(e->stream), "upload sync")) return fail(e->err);
@@ -1344,6 +1404,7 @@ void p3hip_destroy(p3hip_engine* e) {
   if (e->stream) hipStreamSynchronize(e->stream);
   hipFree(e->d_arena); hipFree(e->d_feats); hipFree(e->d_x); hipFree(e->d_t); hipFree(e->d_u); hipFree(e->d_s);
   hipFree(e->d_hp); hipFree(e->d_out); hipFree(e->d_res); hipFree(e->d_qkv);
+  hipFree(e->d_sfeats); hipFree(e->d_cout);
   hipFree(e->d_bw_stamps);
   hipFree(e->d_amax); hipFree(e->d_ascale);
   if (e->bw_mod) hipModuleUnload(e->bw_mod);
@@ -1534,14 +1595,14 @@ int p3hip_upload(p3hip_engine* e) {
   if (!e->bind()) return 1;
   int n = gather_loaded(e);
   if (n == 0) return 0;
-  if (!e->check(hipMemcpyAsync(e->d_feats, e->feats_identity ? e->h_feats : e->h_feats_compact, (size_t)n * kFeatBytes,
+  if (!e->check(hipMemcpyAsync(upload_buffer(e), e->feats_identity ? e->h_feats : e->h_feats_compact, (size_t)n * kFeatBytes,
                                hipMemcpyHostToDevice, e->stream), "H2D features")) return 1;
   return e->check(hipStreamSynchronize(e->stream), "sync") ? 0 : 1;
 }
 
 int p3hip_forward_resident(p3hip_engine* e, int n_positions) {
   if (n_positions < 1 || n_positions > e->batch || !e->bind() || !int8_ready(e)) return 1;
-  return run_forward(e, n_positions) ? 0 : 1;
+  return (e->sym ? run_sym(e, n_positions, e->d_sfeats) : run_forward(e, n_positions)) ? 0 : 1;
 }
 
 int p3hip_sync(p3hip_engine* e) { return e->bind() && e->check(hipStreamSynchronize(e->stream), "sync") ? 0 : 1; }
@@ -1553,7 +1614,7 @@ static int run_cached(p3hip_engine* e, int n) {
   hipStream_t s = e->stream;
   const size_t B = (size_t)e->batch;
   ++c.run;
-  if (!e->check(hipMemcpyAsync(e->d_feats, e->h_feats_compact, (size_t)n * kFeatBytes, hipMemcpyHostToDevice, s), "H2D features") ||
+  if (!e->check(hipMemcpyAsync(upload_buffer(e), e->h_feats_compact, (size_t)n * kFeatBytes, hipMemcpyHostToDevice, s), "H2D features") ||
       !e->check(hipMemcpyAsync(c.d_keys, c.h_keys, (size_t)n * sizeof(p3::CacheKey), hipMemcpyHostToDevice, s), "H2D keys")) return 1;
   p3::CacheArgs a{};
   a.keys = c.d_keys; a.n = n; a.tkeys = c.d_tkeys; a.tmeta = c.d_tmeta; a.tvals = c.d_tvals; a.mask = c.mask; a.run = c.run;
@@ -1596,13 +1657,18 @@ static int run_cached(p3hip_engine* e, int n) {
   nh = hi;
   if (!e->check(hipMemcpyAsync(c.d_lists, c.h_lists, 5 * B * 4, hipMemcpyHostToDevice, s), "H2D lists")) return 1;
   if (nm > 0) {
-    a.rows = c.d_lists; a.m = nm; a.feats_in = e->d_feats; a.feats_out = c.d_feats2;
+    a.rows = c.d_lists; a.m = nm; a.feats_in = upload_buffer(e); a.feats_out = c.d_feats2;
     if (!e->check(p3::launch_cache_gather(a, s), "launch k_cache_gather")) return 1;
-    unsigned char* keep = e->d_feats;
-    e->d_feats = c.d_feats2;
-    const bool ok = run_forward(e, nm);
-    e->d_feats = keep;
-    if (!ok) return 1;
+    if (e->sym) {
+      // symmetry averaging: the misses are expanded, evaluated and reduced into their d_out rows 0 .. nm - 1
+      if (!run_sym(e, nm, c.d_feats2)) return 1;
+    } else {
+      unsigned char* keep = e->d_feats;
+      e->d_feats = c.d_feats2;
+      const bool ok = run_forward(e, nm);
+      e->d_feats = keep;
+      if (!ok) return 1;
+    }
   }
   if (nh > 0) {
     a.idx = c.d_lists + B; a.m = nh; a.out_row0 = nm;
@@ -1624,7 +1690,7 @@ int p3hip_run(p3hip_engine* e) {
   int n = gather_loaded(e);
   if (n == 0) return 0;
   if (e->cache.on && !e->calibrating) return run_cached(e, n);   // calibration evaluates every slot, stores nothing
-  if (!e->check(hipMemcpyAsync(e->d_feats, e->feats_identity ? e->h_feats : e->h_feats_compact, (size_t)n * kFeatBytes,
+  if (!e->check(hipMemcpyAsync(upload_buffer(e), e->feats_identity ? e->h_feats : e->h_feats_compact, (size_t)n * kFeatBytes,
                                hipMemcpyHostToDevice, e->stream), "H2D features")) return 1;
   // The heads kernel writes the result records (the first kResultFloats of an output row) a second time into a dense
   // device buffer (HeadsArgs::res), so the copy TrtEngineImpl::RunInference queues behind its graph (trt_engine.cc:283-297)
@@ -1643,7 +1709,7 @@ int p3hip_run(p3hip_engine* e) {
     t_start = now();
   }
   e->run_direct = e->d_res != nullptr && !no_direct;
-  const bool ok = run_forward(e, n);
+  const bool ok = e->sym ? run_sym(e, n, e->d_sfeats) : run_forward(e, n);   // k_sym_reduce fills d_res
   if (time_run) {
     hipStreamSynchronize(e->stream);
     e->t_fwd += std::chrono::duration<double>(now() - t_start).count();
@@ -1750,6 +1816,14 @@ double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
         if (lp.kw == 3) { ++n3x3; c3 = lp.cin; }
   }
   if (n_positions < 1 || n_positions > e->batch || iters < 1 || !e->bind()) return -1.0;
+  if (e->sym) {
+    // symmetry averaging: the trunk runs over the k copies of the resident slots (p3hip_upload put them in d_sfeats)
+    p3::SymExpandArgs x{};
+    x.in = e->d_sfeats; x.out = e->d_feats; x.n = n_positions; x.k = e->sym_k;
+    for (int j = 0; j < p3::kNumSyms; ++j) x.syms[j] = e->sym_syms[j];
+    if (!e->check(p3::launch_sym_expand(x, e->stream), "launch k_sym_expand")) return -1.0;
+    n_positions *= e->sym_k;
+  }
   if (e->tfm) {
     // transformer trunks: the attention kernel (enqueue_forward records an event pair around each k_tfm_attn)
     while ((int)e->blk_ev.size() < 2 * wf.nblocks) {
@@ -1854,6 +1928,7 @@ double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
 // debugging aid: the residual stream x of the last forward pass, n_positions x C x 361 fp16 in the device layout
 // [pos][C / 8][361][8], as floats
 int p3hip_debug_x(p3hip_engine* e, float* out, int n_positions) {
+  if (e->sym) { e->err = "p3hip_debug_x: not available on a P3HIP_FLAG_SYMMETRY_AVG engine"; return 1; }
   if (!e->bind() || n_positions < 1 || n_positions > e->batch) return 1;
   const size_t n = (size_t)n_positions * e->wf.C * kNLoc;
   std::vector<_Float16> h(n);
@@ -1864,6 +1939,29 @@ int p3hip_debug_x(p3hip_engine* e, float* out, int n_positions) {
 }
 
 void p3hip_rope_table(double* cos_out, double* sin_out) { spiral_rope_table(cos_out, sin_out); }
+
+void p3hip_symmetry_maps(uint16_t fwd[8][361], uint16_t inv[8][361]) { p3::sym_maps(fwd, inv); }
+
+int p3hip_set_symmetries(p3hip_engine* e, uint32_t mask) {
+  if (!e->sym) { e->err = "p3hip_set_symmetries: the engine was not created with P3HIP_FLAG_SYMMETRY_AVG"; return 1; }
+  if (mask < 1 || mask > 255) { e->err = "p3hip_set_symmetries: the mask must be 1 .. 255 (bit s = symmetry s)"; return 1; }
+  if (mask == e->sym_mask) return 0;
+  if (!e->bind()) return 1;
+  // the captured graph holds the old list in its kernel arguments: drop it.  The next full run goes out kernel by
+  // kernel (a new k means new row counts, whose launchers may meet kernels for the first time), the one after is captured
+  if (e->graph_exec || e->graph) {
+    if (!e->check(hipStreamSynchronize(e->stream), "sync")) return 1;
+    if (e->graph_exec) hipGraphExecDestroy(e->graph_exec);
+    if (e->graph) hipGraphDestroy(e->graph);
+    e->graph_exec = nullptr;
+    e->graph = nullptr;
+    e->graph_feats = nullptr;
+  }
+  e->graph_warm = false;
+  e->sym_mask = mask;
+  e->sym_k = p3::sym_list(mask, e->sym_syms);
+  return 0;
+}
 
 int p3hip_blockw_stamps(p3hip_engine* e, unsigned long long* out, int n) {
   if (!e->bind() || !e->d_bw_stamps) return 1;

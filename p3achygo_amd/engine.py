@@ -31,12 +31,14 @@ EXPORTS = [
     "p3hip_cache_enable", "p3hip_load_slot_keyed", "p3hip_get_slot_keyed", "p3hip_cache_stats",
     "p3hip_blockw_stamps", "p3hip_debug_x", "p3hip_rope_table",
     "p3hip_int8_calibrate", "p3hip_int8_scales", "p3hip_int8_set_scales",
+    "p3hip_set_symmetries", "p3hip_symmetry_maps",
 ]
 
 FLAG_RUN_ALL_SLOTS = 2
 FLAG_SHARED_DEVICE = 4
 FLAG_LAUNCH_GRAPH = 8
 FLAG_INT8 = 16   # calibrated INT8 convs in the layer-wise blocks (include/p3hip.h)
+FLAG_SYMMETRY_AVG = 32   # every slot averaged over a set of the eight symmetries on the device
 
 
 class EngineError(RuntimeError):
@@ -90,6 +92,9 @@ def lib():
         L.p3hip_int8_calibrate.argtypes = [C.c_void_p]
         L.p3hip_int8_scales.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.p3hip_int8_set_scales.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.p3hip_set_symmetries.argtypes = [C.c_void_p, C.c_uint32]
+        L.p3hip_symmetry_maps.argtypes = [C.c_void_p, C.c_void_p]
+        L.p3hip_symmetry_maps.restype = None
         L.p3hip_time_trunk_kernel.restype = C.c_double
         L.p3hip_time_trunk_kernel.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double),
                                               C.POINTER(C.c_char_p)]
@@ -202,6 +207,14 @@ class HipEngine:
         s = np.ascontiguousarray(scales, np.float32)
         self._ck(self._L.p3hip_int8_set_scales(self._h, s.ctypes.data, len(s)), "set_int8_scales")
 
+    # -- symmetry-averaged evaluation (FLAG_SYMMETRY_AVG) ----------------------------------
+    def set_symmetries(self, mask: int) -> None:
+        """Bit s selects symmetry s (identity, rot90, rot180, rot270, flip, flipRot90, flipRot180, flipRot270); 1..255.
+        Applies from the next run.  Fails on an engine created without FLAG_SYMMETRY_AVG."""
+        if not 0 <= int(mask) < 1 << 32:
+            raise EngineError(f"set_symmetries: mask {mask} is not a uint32")
+        self._ck(self._L.p3hip_set_symmetries(self._h, int(mask)), "set_symmetries")
+
     # -- measurement / test hooks -------------------------------------------------------
     def load_all(self, feats_rec: np.ndarray) -> None:
         feats_rec = np.ascontiguousarray(feats_rec)
@@ -281,6 +294,15 @@ def rope_table():
     L.p3hip_rope_table.restype = None
     L.p3hip_rope_table(cos.ctypes.data, sin.ctypes.data)
     return cos, sin
+
+
+def symmetry_maps():
+    """The engine's D4 index maps of the 19 x 19 board, (fwd, inv) as [8][361] uint16 (no device needed):
+    features move by out[fwd[s][i]] = in[i], outputs come back by out[inv[s][i]] = in[i]."""
+    fwd = np.zeros((8, 361), np.uint16)
+    inv = np.zeros((8, 361), np.uint16)
+    lib().p3hip_symmetry_maps(fwd.ctypes.data, inv.ctypes.data)
+    return fwd, inv
 
 
 def create_engine(kind: Kind, path: str, batch_size: int, version: int, device: int = 0,

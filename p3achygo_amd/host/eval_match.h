@@ -91,7 +91,30 @@ struct EvalPlayerConfig {   // PlayerSearchConfig (player_config.h:20-108), same
   SearchMode search_mode = SearchMode::kConcurrent;
   DescentPolicy descent_policy = DescentPolicy::kDeterministic;   // "deterministic" | "bu_uct"
   float max_o_ratio = 1.0f;
+  // extension: the player's engine averages every evaluation over these symmetries on the device
+  // (P3HIP_FLAG_SYMMETRY_AVG + p3hip_set_symmetries; bit s = symmetry s).  0 = off: one random symmetry per leaf.
+  uint32_t nn_symmetry_mask = 0;
 };
+
+// nn_symmetry_mask: decimal or 0x hex, 0 .. 255
+inline bool ParseSymmetryMask(const std::string& v, uint32_t* out) {
+  const bool hex = v.size() > 2 && v[0] == '0' && (v[1] == 'x' || v[1] == 'X');
+  const size_t from = hex ? 2 : 0;
+  if (v.size() <= from || v.size() - from > 8) return false;
+  uint32_t m = 0;
+  for (size_t i = from; i < v.size(); ++i) {
+    const char c = v[i];
+    int d = -1;
+    if (c >= '0' && c <= '9') d = c - '0';
+    else if (hex && c >= 'a' && c <= 'f') d = c - 'a' + 10;
+    else if (hex && c >= 'A' && c <= 'F') d = c - 'A' + 10;
+    if (d < 0) return false;
+    m = m * (hex ? 16 : 10) + (uint32_t)d;
+  }
+  if (m > 255) return false;
+  *out = m;
+  return true;
+}
 
 inline bool UsesParallelSearch(const EvalPlayerConfig& c) { return c.num_threads_per_game > 1 || c.time_ms > 0; }   // eval.cc:99-101
 
@@ -194,6 +217,12 @@ inline bool ParsePlayerConfigStream(std::istream& in, EvalPlayerConfig* cfg, std
       else if (key == "search_mode") cfg->search_mode = val == "batch" ? SearchMode::kBatch : SearchMode::kConcurrent;
       else if (key == "descent_policy") cfg->descent_policy = val == "bu_uct" ? DescentPolicy::kBuUct : DescentPolicy::kDeterministic;
       else if (key == "max_o_ratio") cfg->max_o_ratio = std::stof(val);
+      else if (key == "nn_symmetry_mask") {
+        if (!ParseSymmetryMask(val, &cfg->nn_symmetry_mask)) {
+          if (err) *err = "nn_symmetry_mask must be 0 .. 255, decimal or 0x hex: " + line;
+          return false;
+        }
+      }
       // unknown keys are ignored (player_config.h:243)
     }
   } catch (const std::exception& e) {   // the reference lets std::stoi / std::stof throw out of main

@@ -109,6 +109,7 @@ struct HipEvaluator final : Evaluator {
   decltype(&p3hip_load_slot_keyed) load_keyed = nullptr;
   decltype(&p3hip_get_slot_keyed) get_keyed = nullptr;
   decltype(&p3hip_cache_stats) cache_stats = nullptr;
+  decltype(&p3hip_set_symmetries) set_symmetries = nullptr;
   std::string err;
 
   bool Open(const char* lib_path, const char* weights, int batch, int device, uint32_t flags = 0) {
@@ -126,9 +127,17 @@ struct HipEvaluator final : Evaluator {
     load_keyed = (decltype(load_keyed))dlsym(lib, "p3hip_load_slot_keyed");
     get_keyed = (decltype(get_keyed))dlsym(lib, "p3hip_get_slot_keyed");
     cache_stats = (decltype(cache_stats))dlsym(lib, "p3hip_cache_stats");
+    set_symmetries = (decltype(set_symmetries))dlsym(lib, "p3hip_set_symmetries");
     if (!create || !destroy || !load || !run || !get) { err = "missing p3hip symbols"; return false; }
     eng = create(weights, batch, 1, device, flags);
     if (!eng) { err = create_error ? create_error() : "p3hip_create failed"; return false; }
+    return true;
+  }
+  // Symmetry averaging (an engine opened with P3HIP_FLAG_SYMMETRY_AVG): false with a message when the library lacks
+  // p3hip_set_symmetries or the engine refuses the mask.
+  bool SetSymmetries(uint32_t mask) {
+    if (!set_symmetries) { err = "the engine library has no p3hip_set_symmetries (symmetry-averaged evaluation)"; return false; }
+    if (set_symmetries(eng, mask) != 0) { err = std::string("p3hip_set_symmetries: ") + last_error(eng); return false; }
     return true;
   }
   ~HipEvaluator() override {

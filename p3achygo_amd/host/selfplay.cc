@@ -1627,7 +1627,10 @@ int p3host_eval_match(const char* engine_lib, const char* cur_weights, const cha
     } else {
       auto* h = new HipEvaluator();
       ev[e].reset(h);
-      if (!h->Open(engine_lib, e == 0 ? cur_weights : cand_weights, slots, device, P3HIP_FLAG_SHARED_DEVICE)) {   // the two players' passes run concurrently
+      const uint32_t sym_mask = pc[e].nn_symmetry_mask;
+      const uint32_t flags = P3HIP_FLAG_SHARED_DEVICE | (sym_mask ? P3HIP_FLAG_SYMMETRY_AVG : 0u);   // the two players' passes run concurrently
+      if (!h->Open(engine_lib, e == 0 ? cur_weights : cand_weights, slots, device, flags) ||
+          (sym_mask && !h->SetSymmetries(sym_mask))) {
         if (err) snprintf(err, 256, "%s", h->err.c_str());
         return 1;
       }
@@ -1791,7 +1794,12 @@ int p3host_eval_match_threads(const char* engine_lib, const char* cur_weights, c
     } else {
       auto* h = new HipEvaluator();
       ev.reset(h);
-      if (!h->Open(engine_lib, e == 0 ? cur_weights : cand_weights, batch, device, P3HIP_FLAG_SHARED_DEVICE)) {
+      // nn_symmetry_mask: the engine averages every evaluation over those symmetries; the host's random symmetry per
+      // leaf and its inverse stay, since the averaged result comes back in the orientation it was loaded in
+      const uint32_t sym_mask = pc[e].nn_symmetry_mask;
+      const uint32_t flags = P3HIP_FLAG_SHARED_DEVICE | (sym_mask ? P3HIP_FLAG_SYMMETRY_AVG : 0u);
+      if (!h->Open(engine_lib, e == 0 ? cur_weights : cand_weights, batch, device, flags) ||
+          (sym_mask && !h->SetSymmetries(sym_mask))) {
         if (err) snprintf(err, 256, "%s", h->err.c_str());
         return 1;
       }
@@ -1907,6 +1915,15 @@ int p3host_parse_player_config(const char* path, float* out, char* err) {
                        (float)(int)sp.kind, (float)(int)rp.kind, rp.c_puct_visit_scaling, rp.tau, (float)UsesParallelSearch(c),
                        c.bias_cache_alpha};
   std::memcpy(out, v, sizeof v);
+  return 0;
+}
+
+// the nn_symmetry_mask of a player config file (tests): 0 and the mask, or 1 with the parser's message
+int p3host_parse_player_symmetry_mask(const char* path, uint32_t* mask, char* err) {
+  EvalPlayerConfig c;
+  std::string e;
+  if (!ParsePlayerConfig(path, &c, &e)) { if (err) snprintf(err, 256, "%s", e.c_str()); return 1; }
+  *mask = c.nn_symmetry_mask;
   return 0;
 }
 
