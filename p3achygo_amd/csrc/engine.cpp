@@ -298,6 +298,15 @@ struct BlockPlan {
   size_t head_bytes = 0, tail_bytes = 0;
 };
 
+// One forward pass: everything it reads or writes that changes from call to call.
+struct Pass {
+  const unsigned char* feats = nullptr;   // the records k_init reads (a symmetry pass: the records k_sym_expand reads)
+  int npos = 0;
+  float* out = nullptr;   // the rows the heads write: d_out, or d_cout for the copies of a symmetry pass
+  float* res = nullptr;   // d_res: the result records a second time, dense (HeadsArgs::res); null: not written
+  int* timed = nullptr;   // p3hip_time_trunk_kernel: launches timed so far, event pairs e->blk_ev[2 i, 2 i + 1]
+};
+
 }  // namespace
 
 struct p3hip_engine {
@@ -310,25 +319,27 @@ struct p3hip_engine {
   bool runs_contiguous = false;   // build_plan laid every run's streams back to back (joined launches possible)
   bool bcast_fuse = true;  // P3HIP_NO_BFUSE clears it: broadcast 1x1 convs as their own launches (A/B, tests)
   int stop_block = -1;     // P3HIP_DEBUG_STOP_BLOCK at create: the forward pass ends in front of plan block n (debugging, tests)
+  bool fuse = true, join = true;   // P3HIP_NO_FUSE clears both: one k_block launch per block; P3HIP_NO_JOIN join: one per run
+  int stagger = -1;        // P3HIP_STAGGER: block launches' start-up stagger in cycles (-1: block_args decides)
+  bool pair_turns = true;  // P3HIP_NO_PAIR_TURNS clears it: C = 128 workgroup pairs leave the wave priorities alone
+  bool direct_results = true;   // P3HIP_NO_DIRECT_RESULTS clears it: p3hip_run copies the results strided from d_out
+  bool time_run = false;   // P3HIP_TIME_RUN: p3hip_run times its stages (a measurement aid)
   // k_blockw (csrc/asm/blockw_gen.py): the runs of C = 256 btl blocks by the hand-scheduled one-wave-per-SIMD kernel
   bool blockw = false;
+  bool blockw_diag = false;   // P3HIP_BLOCKW_DIAG: the _diag twin, which writes d_bw_stamps
   struct BlockwRun { size_t first; int nblk; size_t stream_off, prm_off; };
   std::vector<BlockwRun> bw_runs;
   hipModule_t bw_mod = nullptr;
   hipFunction_t bw_fn = nullptr;
   unsigned long long* d_bw_stamps = nullptr;   // P3HIP_BLOCKW_DIAG: s_memtime stamps of the _diag kernel
   hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // P3HIP_FLAG_LAUNCH_GRAPH: the forward pass over the full static batch, captured once (trt_engine.cc:260-303)
   hipGraph_t graph = nullptr;
   hipGraphExec_t graph_exec = nullptr;
   bool graph_failed = false, graph_warm = false;
-  const unsigned char* graph_feats = nullptr;   // the feature buffer the captured k_init reads (kernel arguments are baked in)
-  bool graph_direct = false;                    // ... and whether the captured heads kernel writes the host result buffer
-  // p3hip_time_trunk_kernel: event pairs around every fused-block launch of a forward pass
+  Pass graph_pass;   // the pass the graph was captured for (kernel arguments are baked in): its feats and res are the key
+  // p3hip_time_trunk_kernel: event pairs around the timed launches of a forward pass
   std::vector<hipEvent_t> blk_ev;
-  bool time_blocks = false;
-  int timed_blocks = 0;
 
   unsigned char* d_arena = nullptr;
   std::vector<BlockPlan> blocks;
@@ -376,8 +387,7 @@ struct p3hip_engine {
   float* d_out = nullptr;
   float* h_out = nullptr;  // pinned [batch][kResultFloats]
   float* d_res = nullptr;  // [batch][kResultFloats] dense: the heads kernel writes the result records a second time there
-                           // (run_direct), so that the D2H copy is ONE contiguous transfer instead of a strided one
-  bool run_direct = false; // this run's heads kernel fills d_res
+                           // (Pass::res), so that the D2H copy is ONE contiguous transfer instead of a strided one
   double t_h2d = 0, t_fwd = 0, t_d2h = 0;   // P3HIP_TIME_RUN
   long t_runs = 0;
   bool feats_identity = false;   // gather_loaded: every slot was dirty, row == slot: the upload comes straight from h_feats
@@ -911,17 +921,15 @@ p3::BlockArgs block_args(p3hip_engine* e, size_t first, int count, int npos) {
     // 10,000 cycles per step (seven steps across the CU slots of an XCD) measured -2 % on the forward
     // pass at four positions per workgroup (gpurun_out/stagger_ab.log); it costs its own length once
     // per launch, so short launches go without.  P3HIP_STAGGER overrides (0 = off).
-    static const int stagger_env = getenv("P3HIP_STAGGER") ? atoi(getenv("P3HIP_STAGGER")) : -1;
     const bool long_launch = npos >= 3 * e->n_cu * (e->wf.C == 256 || e->c128_wg8 ? 1 : 2);
     // (engines sharing the GPU with others: the spread costs its own length and another stream's kernels fill a
     // launch's tail anyway — 0.3-0.6 % of the self-play rate, gpurun_out/stagger_selfplay.log)
     const bool shared = (e->flags & P3HIP_FLAG_SHARED_DEVICE) != 0;
-    a.stagger = stagger_env >= 0 ? stagger_env : ((a.head || a.tail) && long_launch && !shared ? 10000 : 0);
+    a.stagger = e->stagger >= 0 ? e->stagger : ((a.head || a.tail) && long_launch && !shared ? 10000 : 0);
     // two 4-wave workgroups per CU and at least two positions each: they take turns at the higher wave
     // priority (kernels.h; b12c128btl3 forward -3.5 %, b8c128nbt -2.5 % at 1024 positions, nothing at 512 and
     // below; profiles/r02_c128_pair_turns.txt).  P3HIP_NO_PAIR_TURNS=1 leaves the priorities alone.
-    static const bool no_pair_turns = getenv("P3HIP_NO_PAIR_TURNS") != nullptr;
-    a.pair_turns = !no_pair_turns && e->wf.C == 128 && !e->c128_wg8 && npos >= 4 * e->n_cu;
+    a.pair_turns = e->pair_turns && e->wf.C == 128 && !e->c128_wg8 && npos >= 4 * e->n_cu;
   }
   for (int b = 0; b < count; ++b) {
     const BlockPlan& bp = e->blocks[first + b];
@@ -939,8 +947,7 @@ p3::BlockArgs block_args(p3hip_engine* e, size_t first, int count, int npos) {
 // neighbouring runs (then their streams lie back to back in the arena, build_plan).  Returns the number of plan
 // blocks covered (0: not joinable) and fills `a`.
 int joined_launch(p3hip_engine* e, size_t first, int npos, p3::BlockArgs* out) {
-  static const bool no_join = getenv("P3HIP_NO_JOIN") != nullptr || getenv("P3HIP_NO_FUSE") != nullptr;
-  if (no_join || !e->runs_contiguous) return 0;
+  if (!e->join || !e->runs_contiguous) return 0;
   std::vector<std::pair<size_t, int>> runs;   // (first block, count)
   size_t bi = first;
   int nb = 0;
@@ -1015,9 +1022,8 @@ int joined_launch(p3hip_engine* e, size_t first, int npos, p3::BlockArgs* out) {
 int fused_run(const p3hip_engine* e, size_t first) {
   const int kind = e->blocks[first].kind;
   if (kind != 0 && kind != 1) return 0;
-  static const bool no_fuse = getenv("P3HIP_NO_FUSE") != nullptr;
   int n = 1;
-  while (!no_fuse && n < p3::kMaxFuse && first + n < e->blocks.size() && e->blocks[first + n].kind == kind) ++n;
+  while (e->fuse && n < p3::kMaxFuse && first + n < e->blocks.size() && e->blocks[first + n].kind == kind) ++n;
   return n;
 }
 
@@ -1035,11 +1041,10 @@ static_assert(sizeof(BlockwArgs) == 64, "kernarg layout of k_blockw");
 
 bool load_blockw(p3hip_engine* e) {
   if (e->bw_fn) return true;
-  static const bool diag = getenv("P3HIP_BLOCKW_DIAG") != nullptr;
   if (!e->check(hipModuleLoadData(&e->bw_mod, p3_blockw_hsaco), "hipModuleLoadData k_blockw")) return false;
-  const std::string name = "k_blockw_L" + std::to_string(e->wf.inner) + (diag ? "_diag" : "");
+  const std::string name = "k_blockw_L" + std::to_string(e->wf.inner) + (e->blockw_diag ? "_diag" : "");
   if (!e->check(hipModuleGetFunction(&e->bw_fn, e->bw_mod, name.c_str()), "hipModuleGetFunction k_blockw")) return false;
-  if (diag) {
+  if (e->blockw_diag) {
     constexpr size_t bytes = 8 * 16 * 4 * 24 * 8;   // [workgroup 0..7][block][wave][stamp]
     if (!e->check(hipMalloc((void**)&e->d_bw_stamps, bytes), "hipMalloc stamps") ||
         !e->check(hipMemsetAsync(e->d_bw_stamps, 0, bytes, e->stream), "hipMemset stamps")) return false;
@@ -1062,15 +1067,25 @@ bool launch_blockw(p3hip_engine* e, const p3hip_engine::BlockwRun& run, int npos
   return e->check(hipModuleLaunchKernel(e->bw_fn, a.nwg, 1, 1, 256, 1, 1, 0, e->stream, nullptr, cfg), "launch k_blockw");
 }
 
-// Enqueues the whole forward pass for `npos` dense positions already in d_feats.
-bool enqueue_forward(p3hip_engine* e, int npos) {
+// Enqueues `launch`; `timed` (p3hip_time_trunk_kernel, null otherwise) counts the launches put between an event pair of
+// e->blk_ev, while events last.
+template <class Launch>
+bool timed_launch(p3hip_engine* e, int* timed, Launch&& launch) {
+  const bool on = timed && 2 * *timed + 1 < (int)e->blk_ev.size();
+  if (on) hipEventRecord(e->blk_ev[2 * *timed], e->stream);
+  if (!launch()) return false;
+  if (on) hipEventRecord(e->blk_ev[2 * (*timed)++ + 1], e->stream);
+  return true;
+}
+
+// Enqueues the whole forward pass `p`.
+bool enqueue_forward(p3hip_engine* e, const Pass& p) {
   const WeightFile& wf = e->wf;
-  const int C = wf.C;
-  const int npw = (C >= 256) ? 1 : 2;   // positions per workgroup of the k_conv1x1 family (CB = 64: two)
+  const int C = wf.C, npos = p.npos;
   hipStream_t s = e->stream;
   {
     p3::InitArgs a{};
-    a.feats = e->d_feats; a.x = e->d_x; a.npos = npos;
+    a.feats = p.feats; a.x = e->d_x; a.npos = npos;
     a.wstream = e->d_arena + e->init_stream_off; a.nms_total = e->init_nms;
     a.game_w = e->dev<float>(e->game_w_off); a.game_b = e->dev<float>(e->game_b_off);
     if (!e->check(p3::launch_init(C, a, grid_for(e, npos, 1), s), "launch k_init")) return false;
@@ -1091,10 +1106,7 @@ bool enqueue_forward(p3hip_engine* e, int npos) {
                        e->dev<float>(e->rope_cos_off), e->dev<float>(e->rope_sin_off)};
       if (!e->check(p3::launch_tfm_qkv(a, s), "launch k_tfm_qkv")) return false;
       const p3::TfmAttnArgs b{q, k, v, o, npos};
-      const bool timed = e->time_blocks && 2 * e->timed_blocks + 1 < (int)e->blk_ev.size();
-      if (timed) hipEventRecord(e->blk_ev[2 * e->timed_blocks], s);
-      if (!e->check(p3::launch_tfm_attn(b, s), "launch k_tfm_attn")) return false;
-      if (timed) hipEventRecord(e->blk_ev[2 * e->timed_blocks++ + 1], s);
+      if (!timed_launch(e, p.timed, [&] { return e->check(p3::launch_tfm_attn(b, s), "launch k_tfm_attn"); })) return false;
       const p3::TfmFfnArgs f{o, e->d_x, npos, e->d_arena + bp.tfm.wo, e->dev<float>(bp.tfm.rms_out),
                              e->d_arena + bp.tfm.wgu, e->d_arena + bp.tfm.wdown};
       if (!e->check(p3::launch_tfm_ffn(f, s), "launch k_tfm_ffn")) return false;
@@ -1118,26 +1130,23 @@ bool enqueue_forward(p3hip_engine* e, int npos) {
     } else if (bp.kind == 4) {
       const size_t half = (size_t)e->rows * wf.Cb * kNLoc;   // elements of one C_b-channel tensor
       _Float16* bufs[5] = {e->d_x, e->d_t, e->d_t + half, e->d_u, e->d_u + half};
+      // the fields p3::LConvArgs and p3::LConvI8Args share
+      auto fill = [&](auto& a, const LayerPlan& lp) {
+        a.in = bufs[lp.in_buf]; a.out = bufs[lp.out_buf]; a.npos = npos;
+        a.out2 = lp.out2_buf >= 0 ? reinterpret_cast<decltype(a.out2)>(bufs[lp.out2_buf]) : nullptr;
+        a.pre = lp.pre; a.act = lp.act; a.res = lp.res; a.dual = lp.dual;
+        if (a.pre) { a.scale_in = e->dev<float>(lp.pre_bn.scale_off); a.shift_in = e->dev<float>(lp.pre_bn.shift_off); }
+        if (a.act || a.dual) { a.scale_out = e->dev<float>(lp.out_bn.scale_off); a.shift_out = e->dev<float>(lp.out_bn.shift_off); }
+      };
       if (e->int8 && !e->calibrating) {
-        // the int8 plan: the same regions, an int8 tensor where the fp16 plan stores an activated one
-        if (!e->have_scales) {
-          e->err = "INT8 engine has no activation scales: run p3hip_int8_calibrate on calibration batches or load a "
-                   "saved calibration with p3hip_int8_set_scales first";
-          return false;
-        }
+        // the int8 plan (its callers check int8_ready): the same regions, an int8 tensor where the fp16 plan stores an activated one
         for (const LayerPlan& lp : bp.layers) {
           p3::LConvI8Args a{};
-          a.in = bufs[lp.in_buf]; a.out = bufs[lp.out_buf]; a.npos = npos;
-          a.out2 = lp.out2_buf >= 0 ? (int8_t*)bufs[lp.out2_buf] : nullptr;
+          fill(a, lp);
           a.w = e->dev<int8_t>(lp.q_off); a.w_scale = e->dev<float>(lp.qs_off);
           a.act_scale = e->d_ascale; a.in_scale = lp.qidx; a.out_scale = lp.qidx + 1;
-          a.pre = lp.pre; a.act = lp.act; a.res = lp.res; a.dual = lp.dual;
-          if (a.pre) { a.scale_in = e->dev<float>(lp.pre_bn.scale_off); a.shift_in = e->dev<float>(lp.pre_bn.shift_off); }
-          if (a.act || a.dual) { a.scale_out = e->dev<float>(lp.out_bn.scale_off); a.shift_out = e->dev<float>(lp.out_bn.shift_off); }
-          const bool timed = e->time_blocks && lp.kw == 3 && 2 * e->timed_blocks + 1 < (int)e->blk_ev.size();
-          if (timed) hipEventRecord(e->blk_ev[2 * e->timed_blocks], s);
-          if (!e->check(p3::launch_lconv_i8(lp.kw, lp.cin, lp.cout, a, s), "launch k_lconv_i8")) return false;
-          if (timed) hipEventRecord(e->blk_ev[2 * e->timed_blocks++ + 1], s);
+          auto launch = [&] { return e->check(p3::launch_lconv_i8(lp.kw, lp.cin, lp.cout, a, s), "launch k_lconv_i8"); };
+          if (!timed_launch(e, lp.kw == 3 ? p.timed : nullptr, launch)) return false;
         }
         continue;
       }
@@ -1151,25 +1160,16 @@ bool enqueue_forward(p3hip_engine* e, int npos) {
           if (!e->check(p3::launch_absmax(m, e->n_cu, s), "launch k_absmax")) return false;
         }
         p3::LConvArgs a{};
-        a.in = bufs[lp.in_buf]; a.out = bufs[lp.out_buf]; a.npos = npos;
-        a.out2 = lp.out2_buf >= 0 ? bufs[lp.out2_buf] : nullptr;
+        fill(a, lp);
         a.wstream = e->d_arena + lp.stream_off; a.nms_total = lp.nms;
-        a.pre = lp.pre; a.act = lp.act; a.res = lp.res; a.dual = lp.dual;
-        if (a.pre) { a.scale_in = e->dev<float>(lp.pre_bn.scale_off); a.shift_in = e->dev<float>(lp.pre_bn.shift_off); }
-        if (a.act || a.dual) { a.scale_out = e->dev<float>(lp.out_bn.scale_off); a.shift_out = e->dev<float>(lp.out_bn.shift_off); }
-        const bool timed = e->time_blocks && lp.kw == 3 && 2 * e->timed_blocks + 1 < (int)e->blk_ev.size();
-        if (timed) hipEventRecord(e->blk_ev[2 * e->timed_blocks], s);
-        if (!e->check(p3::launch_lconv(lp.kw, lp.cin, lp.cout, a, e->n_cu, s), "launch k_lconv")) return false;
-        if (timed) hipEventRecord(e->blk_ev[2 * e->timed_blocks++ + 1], s);
+        auto launch = [&] { return e->check(p3::launch_lconv(lp.kw, lp.cin, lp.cout, a, e->n_cu, s), "launch k_lconv"); };
+        if (!timed_launch(e, lp.kw == 3 ? p.timed : nullptr, launch)) return false;
       }
     } else if (e->blockw && bp.kind == 0) {
       const p3hip_engine::BlockwRun* run = nullptr;
       for (const auto& r : e->bw_runs) if (r.first == bi) run = &r;
       if (!run) { e->err = "internal error: no k_blockw run starts at this block"; return false; }
-      const bool timed = e->time_blocks && 2 * e->timed_blocks + 1 < (int)e->blk_ev.size();
-      if (timed) hipEventRecord(e->blk_ev[2 * e->timed_blocks], s);
-      if (!launch_blockw(e, *run, npos)) return false;
-      if (timed) hipEventRecord(e->blk_ev[2 * e->timed_blocks++ + 1], s);
+      if (!timed_launch(e, p.timed, [&] { return launch_blockw(e, *run, npos); })) return false;
       bi += run->nblk - 1;
     } else {
       int run = fused_run(e, bi);
@@ -1192,10 +1192,8 @@ bool enqueue_forward(p3hip_engine* e, int npos) {
         a.stamps = (e->launch_index++ == idx) ? e->d_stamps : nullptr;
       }
 #endif
-      const bool timed = e->time_blocks && 2 * e->timed_blocks + 1 < (int)e->blk_ev.size();
-      if (timed) hipEventRecord(e->blk_ev[2 * e->timed_blocks], s);
-      if (!e->check(p3::launch_block(C, bp.kind, wf.inner, e->c128_wg8, a, e->n_cu, s), "launch k_block")) return false;
-      if (timed) hipEventRecord(e->blk_ev[2 * e->timed_blocks++ + 1], s);
+      auto launch = [&] { return e->check(p3::launch_block(C, bp.kind, wf.inner, e->c128_wg8, a, e->n_cu, s), "launch k_block"); };
+      if (!timed_launch(e, p.timed, launch)) return false;
       bi += run - 1;
     }
   }
@@ -1208,8 +1206,8 @@ bool enqueue_forward(p3hip_engine* e, int npos) {
     h.x = e->d_x;
     h.conv_a = e->d_arena + e->heads_conv_a_off;
     h.image = e->dev<float>(e->heads_image_off);
-    h.hp = e->d_hp; h.out = e->sym ? e->d_cout : e->d_out; h.npos = npos; h.V = wf.V;
-    h.res = e->run_direct ? e->d_res : nullptr;
+    h.hp = e->d_hp; h.out = p.out; h.npos = npos; h.V = wf.V;
+    h.res = p.res;
     auto F = [&](const char* n) { return e->dev<float>(e->head_off.at(n)); };
     h.gbn_scale = F("gbn_scale"); h.gbn_shift = F("gbn_shift");
     h.gd_w = F("policy.gpool_dense.w"); h.gd_b = F("policy.gpool_dense.b");
@@ -1231,19 +1229,38 @@ bool enqueue_forward(p3hip_engine* e, int npos) {
   return true;
 }
 
-// The forward pass of a run: one captured graph for the full static batch when the engine was created with
-// P3HIP_FLAG_LAUNCH_GRAPH (the reference's TensorRT engine replays a captured graph, trt_engine.cc:260-303), the
-// kernel-by-kernel launches otherwise and for every other position count.  The first full-batch run goes out
-// kernel by kernel (the launchers set their kernels' LDS attributes on first use, which a capture must not see),
-// the second is captured, the rest replay.  A capture that fails falls back to the launches for good.
-// `enqueue` puts the whole pass on the stream; `feats` is the feature buffer it reads (kernel arguments are baked in).
-bool run_captured(p3hip_engine* e, bool want, const unsigned char* feats, const std::function<bool()>& enqueue) {
-  if (!want) return enqueue();
-  // The capture bakes every kernel argument in, k_init's feature pointer among them, and run_cached points
-  // e->d_feats at the cache's gathered copy around its forward pass: a graph captured for one buffer must never be
-  // replayed for the other.  The graph serves the buffer it was captured on; the other goes out kernel by kernel.
+// k_sym_expand: the `n` records at `src` -> their k copies in d_feats
+bool expand_sym(p3hip_engine* e, const unsigned char* src, int n) {
+  p3::SymExpandArgs x{};
+  x.in = src; x.out = e->d_feats; x.n = n; x.k = e->sym_k;
+  for (int j = 0; j < p3::kNumSyms; ++j) x.syms[j] = e->sym_syms[j];
+  return e->check(p3::launch_sym_expand(x, e->stream), "launch k_sym_expand");
+}
+
+// P3HIP_FLAG_SYMMETRY_AVG: the `p.npos` slots' records in p.feats -> k copies each in d_feats -> the forward pass over
+// n k rows (the heads write d_cout, never d_res) -> the averaged rows in p.out, and the result records in p.res.
+bool enqueue_sym(p3hip_engine* e, const Pass& p) {
+  if (!expand_sym(e, p.feats, p.npos) || !enqueue_forward(e, Pass{e->d_feats, p.npos * e->sym_k, e->d_cout})) return false;
+  p3::SymReduceArgs r{};
+  r.rows = e->d_cout; r.out = p.out; r.res = p.res; r.n = p.npos; r.k = e->sym_k;
+  for (int j = 0; j < p3::kNumSyms; ++j) r.syms[j] = e->sym_syms[j];
+  return e->check(p3::launch_sym_reduce(r, e->stream), "launch k_sym_reduce");
+}
+
+// The forward pass of a run (with P3HIP_FLAG_SYMMETRY_AVG: expand, forward and reduce): one captured graph for the full
+// static batch when the engine was created with P3HIP_FLAG_LAUNCH_GRAPH (the reference's TensorRT engine replays a
+// captured graph, trt_engine.cc:260-303), the kernel-by-kernel launches otherwise and for every other position count.
+// The first full-batch run goes out kernel by kernel (the launchers set their kernels' LDS attributes on first use,
+// which a capture must not see), the second is captured, the rest replay.  A capture that fails falls back to the
+// launches for good.  Calibration runs (the fp16 plan + absmax) go kernel by kernel.
+bool run_pass(p3hip_engine* e, const Pass& p) {
+  auto enqueue = [&] { return e->sym ? enqueue_sym(e, p) : enqueue_forward(e, p); };
+  if (!(e->flags & P3HIP_FLAG_LAUNCH_GRAPH) || p.npos != e->batch || e->graph_failed || e->calibrating) return enqueue();
+  // The capture bakes every kernel argument in: the feature buffer the pass reads (run_cached's passes read the cache's
+  // gathered copy) and whether it writes d_res.  The graph serves the pass it was captured for; any other goes out
+  // kernel by kernel.
   if (e->graph_exec) {
-    if (feats != e->graph_feats || e->run_direct != e->graph_direct) return enqueue();
+    if (p.feats != e->graph_pass.feats || p.res != e->graph_pass.res) return enqueue();
     return e->check(hipGraphLaunch(e->graph_exec, e->stream), "hipGraphLaunch");
   }
   if (!e->graph_warm) {
@@ -1266,46 +1283,46 @@ bool run_captured(p3hip_engine* e, bool want, const unsigned char* feats, const 
     return enqueue();   // nothing was executed by the capture
   }
   e->graph = g;
-  e->graph_feats = feats;
-  e->graph_direct = e->run_direct;
+  e->graph_pass = p;
   return e->check(hipGraphLaunch(e->graph_exec, e->stream), "hipGraphLaunch");
 }
 
-bool run_forward(p3hip_engine* e, int npos) {
-  const bool want = (e->flags & P3HIP_FLAG_LAUNCH_GRAPH) && npos == e->batch && !e->time_blocks && !e->graph_failed &&
-                    !e->calibrating;   // calibration runs (the fp16 plan + absmax) go kernel by kernel
-  return run_captured(e, want, e->d_feats, [&] { return enqueue_forward(e, npos); });
-}
-
-// P3HIP_FLAG_SYMMETRY_AVG: `n` slots' records in `src` -> k copies each in d_feats -> the forward pass over n k rows
-// (the heads write d_cout) -> the averaged rows in d_out rows 0 .. n - 1, and the result records in d_res when
-// e->run_direct.  The heads never write d_res themselves here (no run_direct for the copy pass).
-bool enqueue_sym(p3hip_engine* e, int n, const unsigned char* src) {
-  p3::SymExpandArgs x{};
-  x.in = src; x.out = e->d_feats; x.n = n; x.k = e->sym_k;
-  for (int j = 0; j < p3::kNumSyms; ++j) x.syms[j] = e->sym_syms[j];
-  if (!e->check(p3::launch_sym_expand(x, e->stream), "launch k_sym_expand")) return false;
-  const bool direct = e->run_direct;
-  e->run_direct = false;
-  const bool ok = enqueue_forward(e, n * e->sym_k);
-  e->run_direct = direct;
-  if (!ok) return false;
-  p3::SymReduceArgs r{};
-  r.rows = e->d_cout; r.out = e->d_out; r.res = direct ? e->d_res : nullptr; r.n = n; r.k = e->sym_k;
-  for (int j = 0; j < p3::kNumSyms; ++j) r.syms[j] = e->sym_syms[j];
-  return e->check(p3::launch_sym_reduce(r, e->stream), "launch k_sym_reduce");
-}
-
-// The symmetry pass of a run: on a full static batch with P3HIP_FLAG_LAUNCH_GRAPH one captured graph holds expand,
-// forward and reduce (same warm-up / capture / replay rule as run_forward).
-bool run_sym(p3hip_engine* e, int n, const unsigned char* src) {
-  const bool want = (e->flags & P3HIP_FLAG_LAUNCH_GRAPH) && n == e->batch && !e->time_blocks && !e->graph_failed &&
-                    !e->calibrating;
-  return run_captured(e, want, src, [&] { return enqueue_sym(e, n, src); });
+void drop_graph(p3hip_engine* e) {
+  if (e->graph_exec) hipGraphExecDestroy(e->graph_exec);
+  if (e->graph) hipGraphDestroy(e->graph);
+  e->graph_exec = nullptr;
+  e->graph = nullptr;
 }
 
 // where p3hip_run / p3hip_upload put the slots' records: the forward pass's input, or the expand's
 unsigned char* upload_buffer(p3hip_engine* e) { return e->sym ? e->d_sfeats : e->d_feats; }
+
+// H2D of the `n` records gather_loaded put in the dense upload
+bool upload(p3hip_engine* e, int n) {
+  return e->check(hipMemcpyAsync(upload_buffer(e), e->feats_identity ? e->h_feats : e->h_feats_compact,
+                                 (size_t)n * kFeatBytes, hipMemcpyHostToDevice, e->stream), "H2D features");
+}
+
+// D2H of the result records of rows 0 .. n - 1 into h_out: one contiguous copy from `res` (d_res), or strided from d_out
+bool download(p3hip_engine* e, int n, const float* res) {
+  const size_t rec = p3::kResultFloats * 4;
+  return e->check(res ? hipMemcpyAsync(e->h_out, res, n * rec, hipMemcpyDeviceToHost, e->stream)
+                      : hipMemcpy2DAsync(e->h_out, rec, e->d_out, p3::kOutStride * 4, rec, n, hipMemcpyDeviceToHost, e->stream),
+                  "D2H results");
+}
+
+// Frees the NN cache's buffers and leaves it off (p3hip_destroy; a p3hip_cache_enable that failed part-way)
+void free_cache(p3hip_engine::DeviceCache& c) {
+  hipFree(c.d_tkeys); hipFree(c.d_tmeta); hipFree(c.d_tvals); hipFree(c.d_keys); hipFree(c.d_hit); hipFree(c.d_victim);
+  hipFree(c.d_lists); hipFree(c.d_sym); hipFree(c.d_feats2);
+  if (c.h_keys) hipHostFree(c.h_keys);
+  if (c.h_hit) hipHostFree(c.h_hit);
+  if (c.h_victim) hipHostFree(c.h_victim);
+  if (c.h_lists) hipHostFree(c.h_lists);
+  if (c.h_sym) hipHostFree(c.h_sym);
+  delete[] c.h_slot_keys;
+  c = p3hip_engine::DeviceCache{};
+}
 
 }  // namespace
 
@@ -1333,6 +1350,13 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
   e->c128_wg8 = getenv("P3HIP_C128_WG8") != nullptr;
   e->bcast_fuse = getenv("P3HIP_NO_BFUSE") == nullptr;
   e->stop_block = getenv("P3HIP_DEBUG_STOP_BLOCK") ? atoi(getenv("P3HIP_DEBUG_STOP_BLOCK")) : -1;
+  e->fuse = getenv("P3HIP_NO_FUSE") == nullptr;
+  e->join = e->fuse && getenv("P3HIP_NO_JOIN") == nullptr;
+  e->stagger = getenv("P3HIP_STAGGER") ? atoi(getenv("P3HIP_STAGGER")) : -1;
+  e->pair_turns = getenv("P3HIP_NO_PAIR_TURNS") == nullptr;
+  e->direct_results = getenv("P3HIP_NO_DIRECT_RESULTS") == nullptr;
+  e->time_run = getenv("P3HIP_TIME_RUN") != nullptr;
+  e->blockw_diag = getenv("P3HIP_BLOCKW_DIAG") != nullptr;
   e->int8 = (flags & P3HIP_FLAG_INT8) != 0;
   e->sym = sym;
   e->rows = sym ? p3::kNumSyms * batch_size : batch_size;
@@ -1359,8 +1383,6 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
   const size_t R = e->rows;   // the per-row device buffers: 8 x batch copies with P3HIP_FLAG_SYMMETRY_AVG
   const size_t qkv_bytes = 3 * R * p3::kTfmHeads * p3::kTfmLPad * p3::kTfmD * 2;
   bool ok = e->check(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking), "hipStreamCreate") &&
-            e->check(hipEventCreate(&e->ev0), "hipEventCreate") &&
-            e->check(hipEventCreate(&e->ev1), "hipEventCreate") &&
             e->check(hipMalloc((void**)&e->d_arena, ar.host.size()), "hipMalloc arena") &&
             // on the engine's own stream: it is non-blocking (no implicit ordering with the null stream a plain
             // hipMemcpy / hipMemset runs on), and the first run must find the weights there
@@ -1408,25 +1430,12 @@ void p3hip_destroy(p3hip_engine* e) {
   hipFree(e->d_bw_stamps);
   hipFree(e->d_amax); hipFree(e->d_ascale);
   if (e->bw_mod) hipModuleUnload(e->bw_mod);
-  {
-    auto& c = e->cache;
-    hipFree(c.d_tkeys); hipFree(c.d_tmeta); hipFree(c.d_tvals); hipFree(c.d_keys); hipFree(c.d_hit); hipFree(c.d_victim);
-    hipFree(c.d_lists); hipFree(c.d_sym); hipFree(c.d_feats2);
-    if (c.h_keys) hipHostFree(c.h_keys);
-    if (c.h_hit) hipHostFree(c.h_hit);
-    if (c.h_victim) hipHostFree(c.h_victim);
-    if (c.h_lists) hipHostFree(c.h_lists);
-    if (c.h_sym) hipHostFree(c.h_sym);
-    delete[] c.h_slot_keys;
-  }
+  free_cache(e->cache);
   if (e->h_feats) hipHostFree(e->h_feats);
   if (e->h_feats_compact) hipHostFree(e->h_feats_compact);
   if (e->h_out) hipHostFree(e->h_out);
-  if (e->ev0) hipEventDestroy(e->ev0);
-  if (e->ev1) hipEventDestroy(e->ev1);
   for (hipEvent_t ev : e->blk_ev) hipEventDestroy(ev);
-  if (e->graph_exec) hipGraphExecDestroy(e->graph_exec);
-  if (e->graph) hipGraphDestroy(e->graph);
+  drop_graph(e);
   if (e->stream) hipStreamDestroy(e->stream);
   delete e;
 }
@@ -1480,16 +1489,7 @@ int p3hip_cache_enable(p3hip_engine* e, int log2_entries) {
   if (!ok) {
     // free what was allocated (an over-large table fails at the records): a later, smaller enable starts clean
     const std::string why = e->err;
-    hipFree(c.d_tkeys); hipFree(c.d_tmeta); hipFree(c.d_tvals); hipFree(c.d_keys); hipFree(c.d_hit); hipFree(c.d_victim);
-    hipFree(c.d_lists); hipFree(c.d_sym); hipFree(c.d_feats2);
-    if (c.h_keys) hipHostFree(c.h_keys);
-    if (c.h_hit) hipHostFree(c.h_hit);
-    if (c.h_victim) hipHostFree(c.h_victim);
-    if (c.h_lists) hipHostFree(c.h_lists);
-    if (c.h_sym) hipHostFree(c.h_sym);
-    c.d_tkeys = nullptr; c.d_tmeta = nullptr; c.d_tvals = nullptr; c.d_keys = nullptr; c.d_hit = nullptr; c.d_victim = nullptr;
-    c.d_lists = nullptr; c.d_sym = nullptr; c.d_feats2 = nullptr;
-    c.h_keys = nullptr; c.h_hit = nullptr; c.h_victim = nullptr; c.h_lists = nullptr; c.h_sym = nullptr;
+    free_cache(c);
     (void)hipGetLastError();   // the failed allocation's sticky error
     e->err = why;
     return 1;
@@ -1534,7 +1534,8 @@ static int gather_loaded(p3hip_engine* e) {
   return n;
 }
 
-// An INT8 engine runs only once it has activation scales (the reference refuses --use_int8 without a calibration set)
+// An INT8 engine runs only once it has activation scales (the reference refuses --use_int8 without a calibration set);
+// every entry point that enqueues a forward pass checks it
 static bool int8_ready(p3hip_engine* e) {
   if (!e->int8 || e->calibrating || e->have_scales) return true;
   e->err = "INT8 engine has no activation scales: run p3hip_int8_calibrate on calibration batches or load a saved "
@@ -1595,14 +1596,12 @@ int p3hip_upload(p3hip_engine* e) {
   if (!e->bind()) return 1;
   int n = gather_loaded(e);
   if (n == 0) return 0;
-  if (!e->check(hipMemcpyAsync(upload_buffer(e), e->feats_identity ? e->h_feats : e->h_feats_compact, (size_t)n * kFeatBytes,
-                               hipMemcpyHostToDevice, e->stream), "H2D features")) return 1;
-  return e->check(hipStreamSynchronize(e->stream), "sync") ? 0 : 1;
+  return upload(e, n) && e->check(hipStreamSynchronize(e->stream), "sync") ? 0 : 1;
 }
 
 int p3hip_forward_resident(p3hip_engine* e, int n_positions) {
   if (n_positions < 1 || n_positions > e->batch || !e->bind() || !int8_ready(e)) return 1;
-  return (e->sym ? run_sym(e, n_positions, e->d_sfeats) : run_forward(e, n_positions)) ? 0 : 1;
+  return run_pass(e, Pass{upload_buffer(e), n_positions, e->d_out}) ? 0 : 1;
 }
 
 int p3hip_sync(p3hip_engine* e) { return e->bind() && e->check(hipStreamSynchronize(e->stream), "sync") ? 0 : 1; }
@@ -1614,7 +1613,7 @@ static int run_cached(p3hip_engine* e, int n) {
   hipStream_t s = e->stream;
   const size_t B = (size_t)e->batch;
   ++c.run;
-  if (!e->check(hipMemcpyAsync(upload_buffer(e), e->h_feats_compact, (size_t)n * kFeatBytes, hipMemcpyHostToDevice, s), "H2D features") ||
+  if (!upload(e, n) ||   // (the cache's runs are never feats_identity: the upload comes from h_feats_compact)
       !e->check(hipMemcpyAsync(c.d_keys, c.h_keys, (size_t)n * sizeof(p3::CacheKey), hipMemcpyHostToDevice, s), "H2D keys")) return 1;
   p3::CacheArgs a{};
   a.keys = c.d_keys; a.n = n; a.tkeys = c.d_tkeys; a.tmeta = c.d_tmeta; a.tvals = c.d_tvals; a.mask = c.mask; a.run = c.run;
@@ -1658,17 +1657,9 @@ static int run_cached(p3hip_engine* e, int n) {
   if (!e->check(hipMemcpyAsync(c.d_lists, c.h_lists, 5 * B * 4, hipMemcpyHostToDevice, s), "H2D lists")) return 1;
   if (nm > 0) {
     a.rows = c.d_lists; a.m = nm; a.feats_in = upload_buffer(e); a.feats_out = c.d_feats2;
-    if (!e->check(p3::launch_cache_gather(a, s), "launch k_cache_gather")) return 1;
-    if (e->sym) {
-      // symmetry averaging: the misses are expanded, evaluated and reduced into their d_out rows 0 .. nm - 1
-      if (!run_sym(e, nm, c.d_feats2)) return 1;
-    } else {
-      unsigned char* keep = e->d_feats;
-      e->d_feats = c.d_feats2;
-      const bool ok = run_forward(e, nm);
-      e->d_feats = keep;
-      if (!ok) return 1;
-    }
+    // the misses are evaluated into their d_out rows 0 .. nm - 1 (symmetry averaging: expanded, evaluated and reduced)
+    if (!e->check(p3::launch_cache_gather(a, s), "launch k_cache_gather") || !run_pass(e, Pass{c.d_feats2, nm, e->d_out}))
+      return 1;
   }
   if (nh > 0) {
     a.idx = c.d_lists + B; a.m = nh; a.out_row0 = nm;
@@ -1679,8 +1670,7 @@ static int run_cached(p3hip_engine* e, int n) {
     if (!e->check(p3::launch_cache_insert(a, s), "launch k_cache_insert")) return 1;
     c.inserts += ni;
   }
-  if (!e->check(hipMemcpy2DAsync(e->h_out, p3::kResultFloats * 4, e->d_out, p3::kOutStride * 4,
-                                 p3::kResultFloats * 4, n, hipMemcpyDeviceToHost, s), "D2H results")) return 1;
+  if (!download(e, n, nullptr)) return 1;
   if (nh > 0 && !e->check(hipMemcpyAsync(c.h_sym + nm, c.d_sym + nm, (size_t)nh * 4, hipMemcpyDeviceToHost, s), "D2H symmetries")) return 1;
   return e->check(hipStreamSynchronize(s), "sync") ? 0 : 1;
 }
@@ -1690,40 +1680,31 @@ int p3hip_run(p3hip_engine* e) {
   int n = gather_loaded(e);
   if (n == 0) return 0;
   if (e->cache.on && !e->calibrating) return run_cached(e, n);   // calibration evaluates every slot, stores nothing
-  if (!e->check(hipMemcpyAsync(upload_buffer(e), e->feats_identity ? e->h_feats : e->h_feats_compact, (size_t)n * kFeatBytes,
-                               hipMemcpyHostToDevice, e->stream), "H2D features")) return 1;
+  if (!upload(e, n)) return 1;
   // The heads kernel writes the result records (the first kResultFloats of an output row) a second time into a dense
   // device buffer (HeadsArgs::res), so the copy TrtEngineImpl::RunInference queues behind its graph (trt_engine.cc:283-297)
   // is one contiguous 7.7 MB transfer at the link's rate; the strided copy of rounds 1-3 (1024 rows of 7,556 B out of a
   // 13,664 B pitch) took 0.45 ms, and 4-byte stores straight into host memory from the kernel took as long (round 4,
   // gpurun_out/r4d/breakdown.log).  P3HIP_NO_DIRECT_RESULTS=1: the strided copy (A/B, tests).
-  static const bool no_direct = getenv("P3HIP_NO_DIRECT_RESULTS") != nullptr;
   // P3HIP_TIME_RUN=1 (tools/gpu_run_breakdown.py): the stream is drained after every stage and the stages' wall times are
   // summed into the engine's error string on request — a measurement aid, never set in production
-  static const bool time_run = getenv("P3HIP_TIME_RUN") != nullptr;
   auto now = [] { return std::chrono::steady_clock::now(); };
   auto t_start = now();
-  if (time_run) {
+  if (e->time_run) {
     hipStreamSynchronize(e->stream);
     e->t_h2d += std::chrono::duration<double>(now() - t_start).count();
     t_start = now();
   }
-  e->run_direct = e->d_res != nullptr && !no_direct;
-  const bool ok = e->sym ? run_sym(e, n, e->d_sfeats) : run_forward(e, n);   // k_sym_reduce fills d_res
-  if (time_run) {
+  const Pass p{upload_buffer(e), n, e->d_out, e->direct_results ? e->d_res : nullptr};   // symmetry: k_sym_reduce fills d_res
+  const bool ok = run_pass(e, p);
+  if (e->time_run) {
     hipStreamSynchronize(e->stream);
     e->t_fwd += std::chrono::duration<double>(now() - t_start).count();
     t_start = now();
   }
-  const bool direct = e->run_direct;
-  e->run_direct = false;
-  if (!ok) return 1;
-  if (direct) {
-    if (!e->check(hipMemcpyAsync(e->h_out, e->d_res, (size_t)n * p3::kResultFloats * 4, hipMemcpyDeviceToHost, e->stream), "D2H results")) return 1;
-  } else if (!e->check(hipMemcpy2DAsync(e->h_out, p3::kResultFloats * 4, e->d_out, p3::kOutStride * 4,
-                                        p3::kResultFloats * 4, n, hipMemcpyDeviceToHost, e->stream), "D2H results")) return 1;
+  if (!ok || !download(e, n, p.res)) return 1;
   const bool sync_ok = e->check(hipStreamSynchronize(e->stream), "sync");
-  if (time_run) {
+  if (e->time_run) {
     e->t_d2h += std::chrono::duration<double>(now() - t_start).count();
     ++e->t_runs;
     char buf[200];
@@ -1815,113 +1796,69 @@ double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
       for (const LayerPlan& lp : b.layers)
         if (lp.kw == 3) { ++n3x3; c3 = lp.cin; }
   }
-  if (n_positions < 1 || n_positions > e->batch || iters < 1 || !e->bind()) return -1.0;
+  if (n_positions < 1 || n_positions > e->batch || iters < 1 || !e->bind() || !int8_ready(e)) return -1.0;
+  // The timed kernel (enqueue_forward records an event pair around each of its launches) and its launches per forward
+  // pass: the attention kernel k_tfm_attn of transformer trunks, the fused block kernel, or else the 3x3 layer conv
+  // k_lconv<3, ..> of layer-wise trunks (C = 384, classic)
+  const int per_pass = e->tfm ? wf.nblocks : (bp ? nfused : n3x3);
+  if (per_pass == 0) return -1.0;
   if (e->sym) {
     // symmetry averaging: the trunk runs over the k copies of the resident slots (p3hip_upload put them in d_sfeats)
-    p3::SymExpandArgs x{};
-    x.in = e->d_sfeats; x.out = e->d_feats; x.n = n_positions; x.k = e->sym_k;
-    for (int j = 0; j < p3::kNumSyms; ++j) x.syms[j] = e->sym_syms[j];
-    if (!e->check(p3::launch_sym_expand(x, e->stream), "launch k_sym_expand")) return -1.0;
+    if (!expand_sym(e, e->d_sfeats, n_positions)) return -1.0;
     n_positions *= e->sym_k;
   }
-  if (e->tfm) {
-    // transformer trunks: the attention kernel (enqueue_forward records an event pair around each k_tfm_attn)
-    while ((int)e->blk_ev.size() < 2 * wf.nblocks) {
-      hipEvent_t ev;
-      if (!e->check(hipEventCreate(&ev), "hipEventCreate")) return -1.0;
-      e->blk_ev.push_back(ev);
-    }
-    if (!enqueue_forward(e, n_positions)) return -1.0;   // warm-up
-    double total_ms = 0.0;
-    long launches = 0;
-    for (int i = 0; i < iters; ++i) {
-      e->time_blocks = true;
-      e->timed_blocks = 0;
-      const bool ok = enqueue_forward(e, n_positions);
-      e->time_blocks = false;
-      if (!ok || !e->check(hipStreamSynchronize(e->stream), "sync")) return -1.0;
-      for (int b = 0; b < e->timed_blocks; ++b) {
-        float ms = 0;
-        hipEventElapsedTime(&ms, e->blk_ev[2 * b], e->blk_ev[2 * b + 1]);
-        total_ms += ms;
-        ++launches;
-      }
-    }
-    // q.k^T and p.v over the 361 x 361 tokens of every head (algorithmic, not the padded 384 keys)
-    if (flops_per_launch) *flops_per_launch = 2.0 * n_positions * 2.0 * kNLoc * kNLoc * p3::kTfmC;
-    if (kernel_name) *kernel_name = "k_tfm_attn";
-    return launches ? total_ms / launches : -1.0;
-  }
-  if (!bp && n3x3 > 0) {
-    // layer-wise trunks (C = 384, classic): the dominant kernel is the 3x3 layer conv, k_lconv<3, ..>
-    while ((int)e->blk_ev.size() < 2 * n3x3) {
-      hipEvent_t ev;
-      if (!e->check(hipEventCreate(&ev), "hipEventCreate")) return -1.0;
-      e->blk_ev.push_back(ev);
-    }
-    if (!enqueue_forward(e, n_positions)) return -1.0;   // warm-up
-    double total_ms = 0.0;
-    long launches = 0;
-    for (int i = 0; i < iters; ++i) {
-      e->time_blocks = true;
-      e->timed_blocks = 0;
-      const bool ok = enqueue_forward(e, n_positions);
-      e->time_blocks = false;
-      if (!ok || !e->check(hipStreamSynchronize(e->stream), "sync")) return -1.0;
-      for (int b = 0; b < e->timed_blocks; ++b) {
-        float ms = 0;
-        hipEventElapsedTime(&ms, e->blk_ev[2 * b], e->blk_ev[2 * b + 1]);
-        total_ms += ms;
-        ++launches;
-      }
-    }
-    if (flops_per_launch) *flops_per_launch = 2.0 * n_positions * kNLoc * 9.0 * c3 * c3;
-    if (kernel_name) *kernel_name = e->int8 ? p3::lconv_i8_kernel_name(3, c3, c3) : (c3 == 192 ? "k_lconv<3,192,192>" : "k_lconv<3,64,64>");
-    return launches ? total_ms / launches : -1.0;
-  }
-  if (!bp) return -1.0;
-  // Time the kernel where it runs: whole forward passes over the resident batch, with a HIP
-  // event pair (on the engine's stream) around each fused-block launch.  The average over all
-  // launches is what rocprofv3 --kernel-trace --stats reports for the same run.
-  while ((int)e->blk_ev.size() < 2 * nfused) {
+  while ((int)e->blk_ev.size() < 2 * per_pass) {
     hipEvent_t ev;
     if (!e->check(hipEventCreate(&ev), "hipEventCreate")) return -1.0;
     e->blk_ev.push_back(ev);
   }
-  if (!enqueue_forward(e, n_positions)) return -1.0;   // warm-up
+  // Time the kernel where it runs: whole forward passes over the resident batch, with a HIP event pair (on the engine's
+  // stream) around each timed launch.  The average over all launches is what rocprofv3 --kernel-trace --stats reports
+  // for the same run.
+  Pass p{e->d_feats, n_positions, e->sym ? e->d_cout : e->d_out};
+  if (!enqueue_forward(e, p)) return -1.0;   // warm-up
   double total_ms = 0.0;
   long launches = 0;
   for (int i = 0; i < iters; ++i) {
-    e->time_blocks = true;
-    e->timed_blocks = 0;
-    const bool ok = enqueue_forward(e, n_positions);
-    e->time_blocks = false;
-    if (!ok || !e->check(hipStreamSynchronize(e->stream), "sync")) return -1.0;
-    for (int b = 0; b < e->timed_blocks; ++b) {
+    int timed = 0;
+    p.timed = &timed;
+    if (!enqueue_forward(e, p) || !e->check(hipStreamSynchronize(e->stream), "sync")) return -1.0;
+    for (int b = 0; b < timed; ++b, ++launches) {
       float ms = 0;
       hipEventElapsedTime(&ms, e->blk_ev[2 * b], e->blk_ev[2 * b + 1]);
       total_ms += ms;
-      ++launches;
     }
   }
-  const double n3 = (wf.btype == 0) ? wf.inner : 4;
-  // every conv the block kernel executes: the inner 3x3s plus the 1x1 reduce and expand
-  // a launch covers `nfused / launches-per-forward` blocks on average
-  const double blocks_per_launch = launches ? (double)nfused * iters / launches : 1.0;
-  // plus the broadcast blocks' C -> C convs that ride in the block launches
-  int nbconv = 0;
-  for (const BlockPlan& b : e->blocks) nbconv += (b.head_of >= 0) + (b.tail_of >= 0);
-  const double bconv_per_launch = launches ? (double)nbconv * iters / launches : 0.0;
-  // ... and their dense where it rides in the tail (algorithmic 361 x 361 per channel, not the padded K = 384)
-  int ndense = 0;
-  for (const BlockPlan& b : e->blocks) ndense += b.kind == 3 && b.first_fused && b.dense_fused;
-  const double dense_per_launch = launches ? (double)ndense * iters / launches : 0.0;
-  if (flops_per_launch)
-    *flops_per_launch = 2.0 * n_positions * kNLoc *
-                        (blocks_per_launch * (n3 * 9.0 * wf.Cb * wf.Cb + 2.0 * wf.C * wf.Cb) + bconv_per_launch * (double)wf.C * wf.C +
-                         dense_per_launch * (double)wf.C * kNLoc);
-  if (kernel_name) *kernel_name = e->blockw ? (wf.inner == 3 ? "k_blockw_L3" : wf.inner == 2 ? "k_blockw_L2" : "k_blockw_L1")
-                                            : p3::block_kernel_name(wf.C, bp->kind, wf.inner);
+  double flops = 0.0;
+  const char* name = nullptr;
+  if (e->tfm) {
+    // q.k^T and p.v over the 361 x 361 tokens of every head (algorithmic, not the padded 384 keys)
+    flops = 2.0 * n_positions * 2.0 * kNLoc * kNLoc * p3::kTfmC;
+    name = "k_tfm_attn";
+  } else if (!bp) {
+    flops = 2.0 * n_positions * kNLoc * 9.0 * c3 * c3;
+    name = e->int8 ? p3::lconv_i8_kernel_name(3, c3, c3) : (c3 == 192 ? "k_lconv<3,192,192>" : "k_lconv<3,64,64>");
+  } else {
+    const double n3 = (wf.btype == 0) ? wf.inner : 4;
+    // every conv the block kernel executes: the inner 3x3s plus the 1x1 reduce and expand
+    // a launch covers `nfused / launches-per-forward` blocks on average
+    const double blocks_per_launch = launches ? (double)nfused * iters / launches : 1.0;
+    // plus the broadcast blocks' C -> C convs that ride in the block launches
+    int nbconv = 0;
+    for (const BlockPlan& b : e->blocks) nbconv += (b.head_of >= 0) + (b.tail_of >= 0);
+    const double bconv_per_launch = launches ? (double)nbconv * iters / launches : 0.0;
+    // ... and their dense where it rides in the tail (algorithmic 361 x 361 per channel, not the padded K = 384)
+    int ndense = 0;
+    for (const BlockPlan& b : e->blocks) ndense += b.kind == 3 && b.first_fused && b.dense_fused;
+    const double dense_per_launch = launches ? (double)ndense * iters / launches : 0.0;
+    flops = 2.0 * n_positions * kNLoc *
+            (blocks_per_launch * (n3 * 9.0 * wf.Cb * wf.Cb + 2.0 * wf.C * wf.Cb) + bconv_per_launch * (double)wf.C * wf.C +
+             dense_per_launch * (double)wf.C * kNLoc);
+    name = e->blockw ? (wf.inner == 3 ? "k_blockw_L3" : wf.inner == 2 ? "k_blockw_L2" : "k_blockw_L1")
+                     : p3::block_kernel_name(wf.C, bp->kind, wf.inner);
+  }
+  if (flops_per_launch) *flops_per_launch = flops;
+  if (kernel_name) *kernel_name = name;
   return launches ? total_ms / launches : -1.0;
 }
 
@@ -1949,14 +1886,8 @@ int p3hip_set_symmetries(p3hip_engine* e, uint32_t mask) {
   if (!e->bind()) return 1;
   // the captured graph holds the old list in its kernel arguments: drop it.  The next full run goes out kernel by
   // kernel (a new k means new row counts, whose launchers may meet kernels for the first time), the one after is captured
-  if (e->graph_exec || e->graph) {
-    if (!e->check(hipStreamSynchronize(e->stream), "sync")) return 1;
-    if (e->graph_exec) hipGraphExecDestroy(e->graph_exec);
-    if (e->graph) hipGraphDestroy(e->graph);
-    e->graph_exec = nullptr;
-    e->graph = nullptr;
-    e->graph_feats = nullptr;
-  }
+  if ((e->graph_exec || e->graph) && !e->check(hipStreamSynchronize(e->stream), "sync")) return 1;
+  drop_graph(e);
   e->graph_warm = false;
   e->sym_mask = mask;
   e->sym_k = p3::sym_list(mask, e->sym_syms);
