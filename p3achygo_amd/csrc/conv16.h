@@ -400,8 +400,9 @@ template <int NTn>
 struct ResRegs16 {
   static constexpr int NB = NTn / 2;
   h8 rv[NB][4];         // the 16-byte piece of this lane's own row of tile pair b, cout tile ct
-  uint32_t base[NB];    // element offset of that piece for ct = 0
+  uint32_t base[NB];    // element offset of that piece for ct = 0, from the first element of position pos0
   bool ok[NB];
+  size_t pos_base;      // element offset of position pos0 (uniform: the 64-bit part of the address lives in SGPRs)
 };
 
 template <class G, int COUT_PASS, int NTn>
@@ -420,21 +421,22 @@ __device__ __forceinline__ void residual_addr16(ResRegs16<NTn>& rr, int C, int p
     int loc;
     rr.ok[b] = row_valid<G::S>(tt * 32 + 2 * n + (q & 1), loc) && (pos0 + p < npos) && (t < G::NT_TOTAL);
     if (!rr.ok[b]) loc = 0;
-    const int pp = (pos0 + p < npos) ? pos0 + p : npos - 1;
-    rr.base[b] = (uint32_t)((pp * (C / 8) + cblk) * (kNLoc * 8) + loc * 8);
+    const int pp = (pos0 + p < npos) ? pos0 + p : npos - 1;   // >= pos0: the callers' pos0 < npos
+    rr.base[b] = (uint32_t)(((pp - pos0) * (C / 8) + cblk) * (kNLoc * 8) + loc * 8);
   }
+  rr.pos_base = (size_t)pos0 * C * kNLoc;   // past 2^31 elements before 65536 positions: not in the 32-bit lane offset
 }
 
 // Issues exactly NTn*2 = 12 sixteen-byte loads per lane (invalid rows read a valid dummy
-// address).  Addresses are (uniform base of the cout tile's channel block) + (32-bit lane
-// offset), the SGPR-base form of global_load: three offset registers.
+// address).  Addresses are (uniform base of position pos0 and the cout tile's channel block) +
+// (32-bit lane offset), the SGPR-base form of global_load: three offset registers.
 constexpr int kResLoads = 12;
 template <int NTn>
 __device__ __forceinline__ void residual_load16(ResRegs16<NTn>& rr, const _Float16* __restrict__ x) {
   static_assert(NTn * 2 == kResLoads, "vmcnt bookkeeping of the callers");
 #pragma unroll
   for (int ct = 0; ct < 4; ++ct) {
-    const char* xc = (const char*)x + (size_t)ct * (2 * kNLoc * 8 * 2);   // channel block +2 per cout tile
+    const char* xc = (const char*)x + sgpr_offset(rr.pos_base * 2 + (size_t)ct * (2 * kNLoc * 8 * 2));   // channel block +2 per cout tile
 #pragma unroll
     for (int b = 0; b < NTn / 2; ++b) {
       rr.rv[b][ct] = *(const h8*)(xc + (uint32_t)(rr.base[b] * 2u));
@@ -567,7 +569,7 @@ __device__ __forceinline__ void epilogue_store16_act(f32x4 (&acc)[4][NTn], const
   }
 #pragma unroll
   for (int ct = 0; ct < 4; ++ct) {
-    char* xc = (char*)x + (size_t)ct * (2 * kNLoc * 8 * 2);
+    char* xc = (char*)x + sgpr_offset(rr.pos_base * 2 + (size_t)ct * (2 * kNLoc * 8 * 2));
     if (PF) {
       if (act && ct + 1 < 4) {
         nsc = *(const f32x4*)(scale + c0 + 16 * (ct + 1));
@@ -614,7 +616,7 @@ __device__ __forceinline__ void epilogue_store16_mish(f32x4 (&acc)[4][NTn], cons
                                                       _Float16* __restrict__ out) {
 #pragma unroll
   for (int ct = 0; ct < 4; ++ct) {
-    char* oc = (char*)out + (size_t)ct * (2 * kNLoc * 8 * 2);
+    char* oc = (char*)out + sgpr_offset(rr.pos_base * 2 + (size_t)ct * (2 * kNLoc * 8 * 2));
 #pragma unroll
     for (int b = 0; b < NTn / 2; ++b) {
       const f32x2 a0 = mish_f2(f32x2{acc[ct][2 * b][0], acc[ct][2 * b][1]}), a1 = mish_f2(f32x2{acc[ct][2 * b][2], acc[ct][2 * b][3]});
@@ -662,7 +664,7 @@ __device__ __forceinline__ void epilogue_store16(f32x4 (&acc)[4][NTn], const Res
                                                  _Float16* __restrict__ x) {
 #pragma unroll
   for (int ct = 0; ct < 4; ++ct) {
-    char* xc = (char*)x + (size_t)ct * (2 * kNLoc * 8 * 2);
+    char* xc = (char*)x + sgpr_offset(rr.pos_base * 2 + (size_t)ct * (2 * kNLoc * 8 * 2));
 #pragma unroll
     for (int b = 0; b < NTn / 2; ++b) {
       h4 r0 = {0, 0, 0, 0}, r1 = {0, 0, 0, 0};

@@ -84,6 +84,14 @@ __device__ __forceinline__ int launder(int v) {
   return v;
 }
 
+// A uniform byte offset, kept whole in an SGPR pair: the constant part of an address (a channel block's offset) is not
+// re-associated into the 32-bit lane offset, which would cost a 64-bit VGPR address per access instead of the
+// (SGPR base + 32-bit lane offset) form of global_load / global_store.
+__device__ __forceinline__ size_t sgpr_offset(size_t v) {
+  asm("" : "+s"(v));
+  return v;
+}
+
 
 // row (column-padded index) -> validity and plain location
 template <int S>
@@ -721,8 +729,9 @@ __device__ __forceinline__ void act_zero(char* smem) {
 template <class G, int COUT_PASS, int NTn>
 struct ResRegs {
   h8 rv[NTn][4];       // piece of this lane's row, channel block 2*kp + (lane >> 5)
-  uint32_t base[NTn];  // element offset of that piece for kp = 0
+  uint32_t base[NTn];  // element offset of that piece for kp = 0, from the first element of position pos0
   bool ok[NTn];
+  size_t pos_base;     // element offset of position pos0 (uniform: kept out of the 32-bit lane offset, see ResRegs16)
 };
 
 template <class G, int COUT_PASS, int NTn>
@@ -742,9 +751,10 @@ __device__ __forceinline__ void residual_addr(ResRegs<G, COUT_PASS, NTn>& rr, in
     int loc;
     rr.ok[j] = row_valid<G::S>(tt * 32 + lr, loc) && (pos0 + p < npos) && (t < G::NT_TOTAL);
     if (!rr.ok[j]) loc = 0;
-    const int pp = (pos0 + p < npos) ? pos0 + p : npos - 1;
-    rr.base[j] = (uint32_t)((pp * (C / 8) + cblk) * (kNLoc * 8) + loc * 8);
+    const int pp = (pos0 + p < npos) ? pos0 + p : npos - 1;   // >= pos0: the callers' pos0 < npos
+    rr.base[j] = (uint32_t)(((pp - pos0) * (C / 8) + cblk) * (kNLoc * 8) + loc * 8);
   }
+  rr.pos_base = (size_t)pos0 * C * kNLoc;
 }
 
 // Issues exactly NTn*4 sixteen-byte loads per lane (invalid rows read a valid dummy address).
@@ -755,7 +765,7 @@ __device__ __forceinline__ void residual_load(ResRegs<G, COUT_PASS, NTn>& rr,
   for (int j = 0; j < NTn; ++j)
 #pragma unroll
     for (int kp = 0; kp < 4; ++kp)   // channel blocks 2*kp, 2*kp + 1
-      rr.rv[j][kp] = *(const h8*)((const char*)x + (size_t)kp * (2 * kNLoc * 8 * 2) + (uint32_t)(rr.base[j] * 2u));
+      rr.rv[j][kp] = *(const h8*)((const char*)x + sgpr_offset(rr.pos_base * 2 + (size_t)kp * (2 * kNLoc * 8 * 2)) + (uint32_t)(rr.base[j] * 2u));
 }
 
 // (x = my half of block k, y = my half of block k+1)  <->  (low, high half of my own block's piece)
@@ -817,7 +827,7 @@ __device__ __forceinline__ void epilogue_store(f32x16 (&acc)[2][NTn],
       }
       half_swap32(o0, o1);   // every lane takes part
       const h8 piece = {o0[0], o0[1], o0[2], o0[3], o1[0], o1[1], o1[2], o1[3]};
-      if (rr.ok[j]) *(h8*)((char*)x + (size_t)kp * (2 * kNLoc * 8 * 2) + (uint32_t)(rr.base[j] * 2u)) = piece;
+      if (rr.ok[j]) *(h8*)((char*)x + sgpr_offset(rr.pos_base * 2 + (size_t)kp * (2 * kNLoc * 8 * 2)) + (uint32_t)(rr.base[j] * 2u)) = piece;
     }
 }
 
