@@ -110,6 +110,15 @@ typedef struct p3hip_engine p3hip_engine;
                                        orientation the slot was loaded in.  Needs 8 x batch_size <= 65536.  See
                                        p3hip_set_symmetries below */
 
+/* Transformer trunks (python/model_transformer.py TransformerBlock, a generic_arch of "transformer" blocks) the engine
+ * runs: every block has the same embed_dim d and num_heads h, d equals the stem's channels, d is a multiple of 32 with
+ * 64 <= d <= 384, the head width d / h is 32 or 64; any block count the .p3w header allows; H = 32 and V what the heads
+ * of the residual stream's width serve ({32, 48, 64}; also 80 where the stream is 384 wide, d > 256).  The residual
+ * stream is the smallest of 128, 256, 384 channels that holds d.  p3hip_create refuses every other transformer (and
+ * INT8 on any transformer), and p3achygo_amd/keras_import.py every other archive, with this wording: */
+#define P3HIP_TRANSFORMER_SET \
+  "transformer: d a multiple of 32 with 64 <= d <= 384, head width d / heads 32 or 64, every block alike"
+
 /* Creates an engine from a `.p3w` weight file (see p3achygo_amd/netspec.py) for a static
  * batch of `batch_size` slots on HIP device `device_ordinal`.  `version` is the model
  * feature version (engine_factory.cc:37-53; only 1 is supported: 15 planes + 8 scalars).
@@ -224,13 +233,17 @@ int p3hip_graph_state(const p3hip_engine* e);
 int p3hip_blockw_stamps(p3hip_engine* e, unsigned long long* out, int n);
 /* Debugging aid: the residual stream x after the last forward pass (stopped early by P3HIP_DEBUG_STOP_BLOCK in the
  * environment, if set), n_positions x C x 361 values in the device layout [pos][C / 8][361][8], as floats.
- * Transformer trunks: C is the stream's padded width 128 (the model's 96 channels, then 32 that stay zero). */
+ * Transformer trunks: C is the stream's padded width (the model's d channels, then the channels up to 128, 256 or 384
+ * that stay zero). */
 int p3hip_debug_x(p3hip_engine* e, float* out, int n_positions);
 /* Algorithmic FLOPs (2*MAC) of one position: total, and 3x3 trunk convs only. */
 void p3hip_flops_per_position(const p3hip_engine* e, double* total, double* conv3x3);
 /* The spiral RoPE tables the transformer trunk uses (python/model_transformer.py, head_dim 32, 4 rotations, theta
  * 100), [361 tokens][32] each, in double precision.  Needs no device. */
 void p3hip_rope_table(double* cos_out, double* sin_out);
+/* The same for head width head_dim (32 or 64): [361 tokens][head_dim] each.  Returns 0, or non-zero (tables untouched)
+ * for any other width.  Needs no device. */
+int p3hip_rope_table_dim(int head_dim, double* cos_out, double* sin_out);
 
 #ifdef __cplusplus
 }

@@ -53,9 +53,10 @@ struct Tensor {
 
 struct WeightFile {
   int version = 0, nblocks = 0, C = 0, Cb = 0, H = 0, V = 0, bint = 0, inner = 0, btype = 0;
-  // Transformer trunks (btype 3): model_C is the file's C (96); C becomes the residual stream's width 128, and the
-  // tensors of the stem and the heads are zero-padded to it (pad_transformer_io), so that k_init<128> and the C = 128
-  // heads serve the trunk unchanged.  model_C == C for every other architecture.
+  // Transformer trunks (btype 3): model_C is the file's C (the model width d); C becomes the residual stream's width
+  // p3::tfm_stream_width(d), the smallest of 128, 256 and 384 that holds d, and where that is wider than d the tensors
+  // of the stem and the heads are zero-padded to it (pad_transformer_io), so that k_init and the heads of that width
+  // serve the trunk unchanged.  model_C == C for every other architecture.
   int model_C = 0;
   std::vector<std::vector<float>> padded;
   std::vector<float> data;
@@ -106,12 +107,11 @@ struct WeightFile {
       tensors[std::string(e.name, strnlen(e.name, sizeof e.name))] = t;
     }
     model_C = C;
-    if (btype == 3 && C == p3::kTfmC) pad_transformer_io();
+    if (btype == 3 && p3::tfm_supported(C, Cb) && p3::tfm_stream_width(C) != C) pad_transformer_io(p3::tfm_stream_width(C));
     return true;
   }
-  // [..][C] -> [..][128] (init conv, game dense) and [C][32] -> [128][32] (the head convs), zeros in the new channels
-  void pad_transformer_io() {
-    const int Cp = 128;
+  // [..][C] -> [..][Cp] (init conv, game dense) and [C][32] -> [Cp][32] (the head convs), zeros in the new channels
+  void pad_transformer_io(int Cp) {
     auto pad = [&](const std::string& n, size_t rows, bool out_channels) {
       auto it = tensors.find(n);
       const size_t want = out_channels ? rows * C : (size_t)C * 32;
@@ -233,15 +233,16 @@ void pack_afrag(std::vector<_Float16>& dst, const float* W, int K, int N, int ld
           dst.push_back((_Float16)W[(size_t)(32 * st + 8 * (lane >> 4) + el) * ld + col0 + 16 * ct + (lane & 15)]);
 }
 
-// The spiral RoPE tables of python/model_transformer.py spiral_rope_cos_sin_table(num_rotations = 4, embed_dim = 32,
-// grid_len = 19), ROPE_THETA = 100, restated: [361 tokens][32] each, token s = 19 row + col (meshgrid indexing "ij":
-// the first coordinate is the row).  Channel i belongs to rotation partition k = i / 8 (direction k pi / 4) and takes
-// the frequency theta^(-t / 8), t = min(7, 2 (k % 2) + 4 ((i % 8) / 4) + (i % 8) / 2 % 2): both channels of a pair
-// share it.
-void spiral_rope_table(double* cos_out, double* sin_out) {
-  const int D = p3::kTfmD, K = 4, per = D / K, nth = D / 4;
+// The spiral RoPE tables of python/model_transformer.py spiral_rope_cos_sin_table(num_rotations = 4, embed_dim = D,
+// grid_len = 19), ROPE_THETA = 100, restated: [361 tokens][D] each, token s = 19 row + col (meshgrid indexing "ij":
+// the first coordinate is the row).  Channel i belongs to rotation partition k = i / per (direction k pi / 4), per = D / 4,
+// and takes the frequency theta^(-t / nth), nth = D / 4, t = min(nth - 1, 2 (k % 2) + 4 ((i % per) / 4) + (i % per) / 2 % 2):
+// both channels of a pair share it.  At D = 32: per = nth = 8.
+// Any head width D that is a multiple of 8 (the engine uses 32 and 64): per = nth = D / 4.
+void spiral_rope_table(int D, double* cos_out, double* sin_out) {
+  const int K = 4, per = D / K, nth = D / 4;
   const double kPi = 3.14159265358979323846;
-  double theta[p3::kTfmD];
+  std::vector<double> theta(D);
   for (int i = 0; i < D; ++i) {
     const int k = i / per, r = (i % per) / 2;
     int t = 2 * (k % (K / 2)) + (r / 2) * K + (r % 2);
@@ -348,6 +349,7 @@ struct p3hip_engine {
   size_t heads_stream_off = 0; int heads_nms = 0;
   size_t heads_conv_a_off = 0, heads_image_off = 0;
   bool tfm = false;                     // transformer trunk (blocks of kind 5)
+  int tfm_heads = 0, tfm_D = 0;         // its head count and head width (model width wf.model_C = heads x D)
   size_t rope_cos_off = 0, rope_sin_off = 0;
   // P3HIP_FLAG_INT8: the layer-wise blocks' convs run on int8 inputs with per-tensor activation
   // scales.  amax: running per-tensor maxima of the calibration runs (float bits, atomicMax); scale: the s_a = max / 127
@@ -376,7 +378,7 @@ struct p3hip_engine {
   unsigned char* h_feats_compact = nullptr;  // pinned, dense
   unsigned char* d_feats = nullptr;
   _Float16 *d_x = nullptr, *d_t = nullptr, *d_u = nullptr;
-  _Float16* d_qkv = nullptr;   // transformer trunks: q, k, v [3][batch][head][384][32] (rows 361.. zeroed once)
+  _Float16* d_qkv = nullptr;   // transformer trunks: q, k, v [3][rows][head][384][D] (rows 361.. zeroed once)
 #ifdef P3_DIAG
   unsigned long long* d_stamps = nullptr;   // diagnostic build: k_block phase stamps of one launch (P3DIAG_LAUNCH)
   unsigned long long* d_spans = nullptr;    // and every workgroup's entry / per-position / exit times of that launch
@@ -468,15 +470,22 @@ bool build_plan(p3hip_engine* e, Arena& ar) {
   const bool bottleneck_ok = wf.btype == 1 || (wf.btype == 0 && wf.inner >= 1 && wf.inner <= 3);
   const bool layerwise = (C == 384 && Cb == 192 && bottleneck_ok) || classic;
   const bool v_ok = wf.V == 32 || wf.V == 48 || wf.V == 64 || wf.V == 80;
-  // transformer trunk: C = 96 and 3 heads in the file (Cb holds the head count), the stream padded to C = 128
-  const bool tfm = wf.btype == 3 && wf.model_C == p3::kTfmC && C == 128 && Cb == p3::kTfmHeads && p3::heads_fusable(C, wf.V);
+  // transformer trunk: the file's C is the model width d and Cb the head count (include/p3hip.h: d a multiple of 32,
+  // 64 <= d <= 384, head width d / heads 32 or 64); the stream is padded to C = p3::tfm_stream_width(d), and V is what
+  // the heads of that width serve (the fused heads at C = 128 / 256: {32, 48, 64}; the C = 384 heads: v_ok)
+  const bool tfm = wf.btype == 3 && p3::tfm_supported(wf.model_C, Cb) && C == p3::tfm_stream_width(wf.model_C) &&
+                   (C == 384 || p3::heads_fusable(C, wf.V));
   if ((!((fused && bottleneck_ok) || layerwise) && !tfm) || wf.H != 32 || !v_ok) {
     e->err = "unsupported architecture for the HIP engine (need (C, Cb) in {(128,64), (256,128), (384,192)} with "
-             "btl (1-3 inner layers) or nbt blocks, or C=192 classic blocks of two convs, or the transformer trunk "
-             "C=96 with 3 heads; H=32, V in {32,48,64,80} (transformer: V in {32,48,64}))";
+             "btl (1-3 inner layers) or nbt blocks, or C=192 classic blocks of two convs, or a transformer trunk "
+             "(" P3HIP_TRANSFORMER_SET "); H=32, V in {32,48,64,80} (transformer: V in {32,48,64}, and 80 at d > 256))";
     return false;
   }
   e->tfm = tfm;
+  if (tfm) {
+    e->tfm_heads = Cb;
+    e->tfm_D = wf.model_C / Cb;
+  }
   if (e->int8 && !layerwise) {
     e->err = "INT8 is available only for layer-wise trunks (C = 384 / C_b = 192 btl or nbt blocks, C = 192 classic "
              "blocks); this trunk runs fused block kernels or the transformer";
@@ -547,15 +556,15 @@ bool build_plan(p3hip_engine* e, Arena& ar) {
     head_of = tail_of = -1;
   };
   if (tfm) {
-    std::vector<double> cd(kNLoc * p3::kTfmD), sd(kNLoc * p3::kTfmD);
-    spiral_rope_table(cd.data(), sd.data());
+    std::vector<double> cd(kNLoc * e->tfm_D), sd(kNLoc * e->tfm_D);
+    spiral_rope_table(e->tfm_D, cd.data(), sd.data());
     const std::vector<float> cf(cd.begin(), cd.end()), sf(sd.begin(), sd.end());
     e->rope_cos_off = ar.add(cf.data(), cf.size() * 4);
     e->rope_sin_off = ar.add(sf.data(), sf.size() * 4);
   }
   for (int i = 0; tfm && i < wf.nblocks; ++i) {
     const std::string p = "blocks." + std::to_string(i);
-    const int c = p3::kTfmC, f = p3::kTfmF;
+    const int c = wf.model_C, f = 2 * c;
     auto T = [&](const char* n, size_t sz) { return wf.get(p + "." + n, sz).data; };
     BlockPlan bp;
     bp.kind = 5;
@@ -1100,16 +1109,18 @@ bool enqueue_forward(p3hip_engine* e, const Pass& p) {
     if (stop_block >= 0 && (int)bi >= stop_block) return true;
     const BlockPlan& bp = e->blocks[bi];
     if (bp.kind == 5) {
-      const size_t per = (size_t)e->rows * p3::kTfmHeads * p3::kTfmLPad * p3::kTfmD;   // one of q, k, v
+      const int d = wf.model_C;
+      const size_t per = (size_t)e->rows * p3::kTfmLPad * d;   // one of q, k, v: [rows][head][384][D]
       _Float16 *q = e->d_qkv, *k = q + per, *v = k + per, *o = e->d_t;
       p3::TfmQkvArgs a{e->d_x, q, k, v, npos, e->dev<float>(bp.tfm.rms_in), e->d_arena + bp.tfm.wqkv,
                        e->dev<float>(e->rope_cos_off), e->dev<float>(e->rope_sin_off)};
-      if (!e->check(p3::launch_tfm_qkv(a, s), "launch k_tfm_qkv")) return false;
-      const p3::TfmAttnArgs b{q, k, v, o, npos};
-      if (!timed_launch(e, p.timed, [&] { return e->check(p3::launch_tfm_attn(b, s), "launch k_tfm_attn"); })) return false;
+      if (!e->check(p3::launch_tfm_qkv(d, e->tfm_D, a, s), "launch k_tfm_qkv")) return false;
+      const p3::TfmAttnArgs b{q, k, v, o, npos, e->tfm_heads};
+      if (!timed_launch(e, p.timed, [&] { return e->check(p3::launch_tfm_attn(e->tfm_D, b, s), "launch k_tfm_attn"); }))
+        return false;
       const p3::TfmFfnArgs f{o, e->d_x, npos, e->d_arena + bp.tfm.wo, e->dev<float>(bp.tfm.rms_out),
                              e->d_arena + bp.tfm.wgu, e->d_arena + bp.tfm.wdown};
-      if (!e->check(p3::launch_tfm_ffn(f, s), "launch k_tfm_ffn")) return false;
+      if (!e->check(p3::launch_tfm_ffn(d, f, s), "launch k_tfm_ffn")) return false;
     } else if (bp.kind == 3) {
       p3::Conv1x1Args c0{};
       c0.in = e->d_x; c0.out16 = e->d_t; c0.npos = npos;
@@ -1381,7 +1392,7 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
   const int C = e->wf.C;
   const size_t B = batch_size;
   const size_t R = e->rows;   // the per-row device buffers: 8 x batch copies with P3HIP_FLAG_SYMMETRY_AVG
-  const size_t qkv_bytes = 3 * R * p3::kTfmHeads * p3::kTfmLPad * p3::kTfmD * 2;
+  const size_t qkv_bytes = 3 * R * p3::kTfmLPad * (size_t)e->wf.model_C * 2;   // heads x head width = model width
   bool ok = e->check(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking), "hipStreamCreate") &&
             e->check(hipMalloc((void**)&e->d_arena, ar.host.size()), "hipMalloc arena") &&
             // on the engine's own stream: it is non-blocking (no implicit ordering with the null stream a plain
@@ -1833,7 +1844,7 @@ double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
   const char* name = nullptr;
   if (e->tfm) {
     // q.k^T and p.v over the 361 x 361 tokens of every head (algorithmic, not the padded 384 keys)
-    flops = 2.0 * n_positions * 2.0 * kNLoc * kNLoc * p3::kTfmC;
+    flops = 2.0 * n_positions * 2.0 * kNLoc * kNLoc * wf.model_C;
     name = "k_tfm_attn";
   } else if (!bp) {
     flops = 2.0 * n_positions * kNLoc * 9.0 * c3 * c3;
@@ -1875,7 +1886,13 @@ int p3hip_debug_x(p3hip_engine* e, float* out, int n_positions) {
   return 0;
 }
 
-void p3hip_rope_table(double* cos_out, double* sin_out) { spiral_rope_table(cos_out, sin_out); }
+void p3hip_rope_table(double* cos_out, double* sin_out) { spiral_rope_table(32, cos_out, sin_out); }
+
+int p3hip_rope_table_dim(int head_dim, double* cos_out, double* sin_out) {
+  if (head_dim != 32 && head_dim != 64) return 1;
+  spiral_rope_table(head_dim, cos_out, sin_out);
+  return 0;
+}
 
 void p3hip_symmetry_maps(uint16_t fwd[8][361], uint16_t inv[8][361]) { p3::sym_maps(fwd, inv); }
 

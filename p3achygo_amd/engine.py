@@ -29,7 +29,7 @@ EXPORTS = [
     "p3hip_last_error", "p3hip_forward_resident", "p3hip_upload", "p3hip_sync", "p3hip_get_raw",
     "p3hip_time_trunk_kernel", "p3hip_flops_per_position", "p3hip_graph_state",
     "p3hip_cache_enable", "p3hip_load_slot_keyed", "p3hip_get_slot_keyed", "p3hip_cache_stats",
-    "p3hip_blockw_stamps", "p3hip_debug_x", "p3hip_rope_table",
+    "p3hip_blockw_stamps", "p3hip_debug_x", "p3hip_rope_table", "p3hip_rope_table_dim",
     "p3hip_int8_calibrate", "p3hip_int8_scales", "p3hip_int8_set_scales",
     "p3hip_set_symmetries", "p3hip_symmetry_maps",
 ]
@@ -293,6 +293,19 @@ def rope_table():
     L.p3hip_rope_table.argtypes = [C.c_void_p, C.c_void_p]
     L.p3hip_rope_table.restype = None
     L.p3hip_rope_table(cos.ctypes.data, sin.ctypes.data)
+    return cos, sin
+
+
+def rope_table_dim(head_dim: int):
+    """The engine's spiral RoPE tables for head width `head_dim` (32 or 64), (cos, sin) as [361][head_dim] float64 (no
+    device needed); ValueError for a width the engine does not run."""
+    cos = np.zeros((361, head_dim), np.float64)
+    sin = np.zeros((361, head_dim), np.float64)
+    L = lib()
+    L.p3hip_rope_table_dim.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
+    L.p3hip_rope_table_dim.restype = C.c_int
+    if L.p3hip_rope_table_dim(int(head_dim), cos.ctypes.data, sin.ctypes.data) != 0:
+        raise ValueError(f"the engine has no RoPE table of head width {head_dim} (32 or 64)")
     return cos, sin
 
 

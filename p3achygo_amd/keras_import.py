@@ -18,6 +18,7 @@ reference's own Keras model exists in this environment.
 from __future__ import annotations
 
 import argparse
+import dataclasses
 import json
 import sys
 import zipfile
@@ -57,9 +58,44 @@ def model_arguments(config: Optional[dict]) -> Optional[dict]:
     return None
 
 
+def transformer_config_from_arch(args: dict, arch: dict) -> netspec.NetConfig:
+    """NetConfig of a generic_arch trunk (model.py:1048-1058): its "trunk" is a list of ["transformer", {"embed_dim": d,
+    "num_heads": h, ...}] entries (model_config.py:16-18; a saved config may also hold the pos_len and name the
+    constructor adds to each entry).  The block count is the list's length — num_blocks is ModelConfig's default 16
+    for b14d96h3_transformer (model_config.py:34, :166-172) — and every block must have the same (d, h), which a .p3w
+    header (one width C, one head count Cb) can express, with d the stem's num_channels."""
+    trunk = arch.get("trunk") if isinstance(arch, dict) else None
+    if not trunk:
+        raise ValueError("generic_arch holds no trunk list")
+    kinds = {str(e[0]) for e in trunk}
+    if kinds != {"transformer"}:
+        raise ValueError(f"generic_arch trunk of {sorted(kinds)} blocks: the engine runs transformer trunks only "
+                         f"({netspec.TRANSFORMER_SET})")
+    dims = sorted({(int(e[1]["embed_dim"]), int(e[1]["num_heads"])) for e in trunk})
+    if len(dims) > 1:
+        raise ValueError(f"transformer blocks of different (embed_dim, num_heads) {dims}: a .p3w holds one width and one "
+                         f"head count ({netspec.TRANSFORMER_SET})")
+    d, h = dims[0]
+    channels = int(args["num_channels"])
+    if d != channels:
+        raise ValueError(f"transformer embed_dim {d} differs from the stem's num_channels {channels} "
+                         f"({netspec.TRANSFORMER_SET})")
+    if not netspec.transformer_supported(d, h):
+        raise ValueError(f"unsupported architecture: transformer embed_dim {d} with {h} heads ({netspec.TRANSFORMER_SET})")
+    want = netspec.transformer_config(str(args.get("name") or "imported"), len(trunk), d, h,
+                                      int(args["num_head_channels"]), int(args["c_val"]))
+    for table in (netspec.TRANSFORMER_CONFIGS, netspec.WIDE_TRANSFORMER_CONFIGS):
+        for cfg in table.values():
+            if cfg == dataclasses.replace(want, name=cfg.name):
+                return cfg
+    return want
+
+
 def config_from_arguments(args: dict) -> netspec.NetConfig:
     """NetConfig of a checkpoint's constructor arguments (model.py:1128-1150; bottleneck_length counts the two
-    1x1 convs, model.py:403)."""
+    1x1 convs, model.py:403).  A generic_arch (model.py:1177-1178) replaces the legacy trunk arguments."""
+    if args.get("generic_arch"):
+        return transformer_config_from_arch(args, args["generic_arch"])
     block_type = args.get("trunk_block_type", "btl")
     inner = int(args["bottleneck_length"]) - 2 if block_type == "btl" else 2
     want = dict(blocks=int(args["num_blocks"]), channels=int(args["num_channels"]),
@@ -110,7 +146,7 @@ def convert(datasets: Dict[str, np.ndarray], cfg: netspec.NetConfig) -> Tuple[Di
 def import_checkpoint(src: str, dst: str, config_name: Optional[str] = None) -> Tuple[netspec.NetConfig, list]:
     datasets, config = read_archive(src)
     if config_name:
-        cfg = netspec.CONFIGS[config_name]
+        cfg = netspec.get_config(config_name)
     else:
         args = model_arguments(config)
         if not args:

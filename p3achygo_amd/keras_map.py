@@ -65,6 +65,10 @@ def name_map(cfg: netspec.NetConfig) -> List[Tuple[str, str]]:
             k = f"classic_res_{i}"
             for j in range(2):
                 _conv_block(rows, f"{k}/res_id_inner_{j}", b, j)
+        elif kind == "transformer":  # TransformerBlock, model_transformer.py:216-237; name model.py:1054
+            k = f"transformer_{i}"
+            for layer, var, p3w in _TFM_LAYERS:
+                rows.append((f"{k}/{layer}/{var}", f"{b}.{p3w}"))
         else:
             raise ValueError(kind)
     # PolicyHead, model.py:745-778; GlobalPoolBias :670-683
@@ -111,8 +115,16 @@ def name_map(cfg: netspec.NetConfig) -> List[Tuple[str, str]]:
 # No `.keras` file of the reference exists in this build's environment: the walk is restated from the Keras
 # sources' published behaviour and pinned only by that one documented key.
 BN_ORDER = ("gamma", "beta", "mean", "var")
+# TransformerBlock (python/model_transformer.py:216-237): attribute, layer name=, variable, .p3w tensor.  RMSNormalization
+# holds one variable, `scale`; the Dense layers have no bias (use_bias=False), so `kernel` is vars/0; the RoPE layer
+# (:217-222) holds tf.constant tables, no variables.
+_TFM = (("rms_in", "rms_in", "scale", "rms_in.scale"), ("Q", "query", "kernel", "q.w"), ("K", "key", "kernel", "k.w"),
+        ("V", "value", "kernel", "v.w"), ("O", "output", "kernel", "o.w"), ("rms_out", "rms_out", "scale", "rms_out.scale"),
+        ("ffn_gate", "swiglu_gate", "kernel", "ffn_gate.w"), ("ffn_up", "swiglu_up", "kernel", "ffn_up.w"),
+        ("ffn_down", "swiglu_down", "kernel", "ffn_down.w"))
+_TFM_LAYERS = tuple((layer, var, p3w) for _, layer, var, p3w in _TFM)
 _CLASS = {"btl": "bottleneck_residual_conv_block", "nbt": "nbt_residual_block", "classic": "classic_residual_block",
-          "broadcast": "broadcast_residual_block"}
+          "broadcast": "broadcast_residual_block", "transformer": "transformer_block"}
 
 
 class _Counter:
@@ -142,6 +154,14 @@ def object_path_map(cfg: netspec.NetConfig) -> List[Tuple[str, str]]:
     for i in range(cfg.blocks):
         b = f"blocks.{i}"
         kind = cfg.block_kind(i)
+        if kind == "transformer":
+            # a generic_arch trunk: P3achyGoModel.blocks is the list construct_trunk_from_generic_arch returns
+            # (model.py:1048-1058, :1177-1178), its members TransformerBlock layers whose sublayers are attributes
+            # (model_transformer.py:216-237): blocks/transformer_block[_n]/<attribute>/vars/0
+            k = "blocks/" + top(_CLASS[kind])
+            for attr, _, _, p3w in _TFM:
+                rows.append((f"{k}/{attr}/vars/0", f"{b}.{p3w}"))
+            continue
         k = "blocks/" + top(_CLASS[kind]) + "/blocks"
         inner = _Counter()
         if kind == "broadcast":

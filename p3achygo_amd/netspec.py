@@ -113,9 +113,42 @@ TRANSFORMER_CONFIGS: Dict[str, NetConfig] = {
 }
 
 
+# The transformer trunks the engine runs (include/p3hip.h P3HIP_TRANSFORMER_SET, same wording): every block of model
+# width d with h heads, d a multiple of 32 with 64 <= d <= 384, head width d / h of 32 or 64.
+TRANSFORMER_SET = "transformer: d a multiple of 32 with 64 <= d <= 384, head width d / heads 32 or 64, every block alike"
+
+
+def transformer_supported(d: int, heads: int) -> bool:
+    return 64 <= d <= 384 and d % 32 == 0 and heads >= 1 and d % heads == 0 and d // heads in (32, 64)
+
+
+def transformer_config(name: str, blocks: int, d: int, heads: int, head_channels: int = 32, c_val: int = 64) -> NetConfig:
+    """A transformer NetConfig: `blocks` blocks of model width d with `heads` heads (the .p3w header's C and Cb).
+    H = 32 and V = 64 are ModelConfig's defaults."""
+    return NetConfig(name, blocks, d, heads, head_channels, c_val, 0, 0, "transformer")
+
+
+# Not in the reference: two-block transformer nets of every residual-stream width (128, 256, 384, padded or not) and
+# both head widths, for tests.  Kept apart from TRANSFORMER_CONFIGS, whose entries all are the d = 96 / 3-head trunk.
+WIDE_TRANSFORMER_CONFIGS: Dict[str, NetConfig] = {
+    c.name: c
+    for c in [
+        transformer_config("test_b2d64h2_tfm", 2, 64, 2),
+        transformer_config("test_b2d128h2_tfm", 2, 128, 2),        # head width 64
+        transformer_config("test_b2d192h6_tfm", 2, 192, 6),
+        transformer_config("test_b2d256h4_tfm", 2, 256, 4),        # head width 64
+        transformer_config("test_b2d384h12_tfm", 2, 384, 12),
+        transformer_config("test_b2d384h6_tfm", 2, 384, 6, c_val=80),   # head width 64; V = 80 (the C = 384 heads)
+    ]
+}
+
+
 def get_config(name: str) -> NetConfig:
-    """A config of CONFIGS or TRANSFORMER_CONFIGS by name."""
-    return CONFIGS[name] if name in CONFIGS else TRANSFORMER_CONFIGS[name]
+    """A config of CONFIGS, TRANSFORMER_CONFIGS or WIDE_TRANSFORMER_CONFIGS by name."""
+    for table in (CONFIGS, TRANSFORMER_CONFIGS, WIDE_TRANSFORMER_CONFIGS):
+        if name in table:
+            return table[name]
+    raise KeyError(name)
 
 
 def tensor_specs(cfg: NetConfig) -> List[Tuple[str, Tuple[int, ...], str]]:
