@@ -236,6 +236,13 @@ int p3hip_blockw_stamps(p3hip_engine* e, unsigned long long* out, int n);
  * Transformer trunks: C is the stream's padded width (the model's d channels, then the channels up to 128, 256 or 384
  * that stay zero). */
 int p3hip_debug_x(p3hip_engine* e, float* out, int n_positions);
+/* Test hook of transformer trunks: what the last transformer block that ran left in device memory, as floats.
+ * which 0, 1, 2 = q, k, v as [pos][head][384][D], the 23 padding rows 361..383 of every head included; 3 = the
+ * attention output o as [pos][361][d].  It only reads buffers the forward pass owns.  The heads take o's buffer as
+ * scratch: o is the last block's only on an engine stopped in front of them (P3HIP_DEBUG_STOP_BLOCK = n ends the pass
+ * in front of block n; n = the block count ends it after the last block, in front of the heads).  Returns non-zero for
+ * an engine without a transformer trunk, for n_positions < 1 or beyond the last run's, and for any other `which`. */
+int p3hip_debug_tfm(p3hip_engine* e, int which, float* out, int n_positions);
 /* Algorithmic FLOPs (2*MAC) of one position: total, and 3x3 trunk convs only. */
 void p3hip_flops_per_position(const p3hip_engine* e, double* total, double* conv3x3);
 /* The spiral RoPE tables the transformer trunk uses (python/model_transformer.py, head_dim 32, 4 rotations, theta

@@ -320,6 +320,7 @@ struct p3hip_engine {
   bool runs_contiguous = false;   // build_plan laid every run's streams back to back (joined launches possible)
   bool bcast_fuse = true;  // P3HIP_NO_BFUSE clears it: broadcast 1x1 convs as their own launches (A/B, tests)
   int stop_block = -1;     // P3HIP_DEBUG_STOP_BLOCK at create: the forward pass ends in front of plan block n (debugging, tests)
+  int last_npos = 0;       // positions of the last forward pass enqueued or replayed (p3hip_debug_tfm)
   bool fuse = true, join = true;   // P3HIP_NO_FUSE clears both: one k_block launch per block; P3HIP_NO_JOIN join: one per run
   int stagger = -1;        // P3HIP_STAGGER: block launches' start-up stagger in cycles (-1: block_args decides)
   bool pair_turns = true;  // P3HIP_NO_PAIR_TURNS clears it: C = 128 workgroup pairs leave the wave priorities alone
@@ -1103,8 +1104,10 @@ bool enqueue_forward(p3hip_engine* e, const Pass& p) {
   e->launch_index = 0;
 #endif
   // debugging aid (tools/gpu_blockw_ab.py xdiff, tests/test_trunk_blocks_gpu.py): stop the forward pass in front of
-  // plan block e->stop_block (P3HIP_DEBUG_STOP_BLOCK when the engine was created)
+  // plan block e->stop_block (P3HIP_DEBUG_STOP_BLOCK when the engine was created); a value equal to the block count
+  // stops it after the last block, in front of the heads (which take d_t, the transformer's o, as scratch)
   const int stop_block = e->stop_block;
+  e->last_npos = npos;
   for (size_t bi = 0; bi < e->blocks.size(); ++bi) {
     if (stop_block >= 0 && (int)bi >= stop_block) return true;
     const BlockPlan& bp = e->blocks[bi];
@@ -1208,6 +1211,7 @@ bool enqueue_forward(p3hip_engine* e, const Pass& p) {
       bi += run - 1;
     }
   }
+  if (stop_block == (int)e->blocks.size()) return true;
   {
     p3::Conv1x1Args c{};
     c.in = e->d_x; c.out32 = e->d_hp; c.npos = npos;
@@ -1265,6 +1269,7 @@ bool enqueue_sym(p3hip_engine* e, const Pass& p) {
 // which a capture must not see), the second is captured, the rest replay.  A capture that fails falls back to the
 // launches for good.  Calibration runs (the fp16 plan + absmax) go kernel by kernel.
 bool run_pass(p3hip_engine* e, const Pass& p) {
+  e->last_npos = p.npos * (e->sym ? e->sym_k : 1);
   auto enqueue = [&] { return e->sym ? enqueue_sym(e, p) : enqueue_forward(e, p); };
   if (!(e->flags & P3HIP_FLAG_LAUNCH_GRAPH) || p.npos != e->batch || e->graph_failed || e->calibrating) return enqueue();
   // The capture bakes every kernel argument in: the feature buffer the pass reads (run_cached's passes read the cache's
@@ -1882,6 +1887,26 @@ int p3hip_debug_x(p3hip_engine* e, float* out, int n_positions) {
   std::vector<_Float16> h(n);
   hipStreamSynchronize(e->stream);
   if (hipMemcpy(h.data(), e->d_x, n * 2, hipMemcpyDeviceToHost) != hipSuccess) return 2;
+  for (size_t i = 0; i < n; ++i) out[i] = (float)h[i];
+  return 0;
+}
+
+// test hook: what the last transformer block that ran left in HBM, as floats.  which 0, 1, 2: q, k, v of d_qkv,
+// [pos][head][384][D] with the 23 padding rows; 3: o of d_t, [pos][361][d].  Only reads; no launch, no allocation on the
+// device.  The heads take d_t as scratch, so o is that of the last block only on an engine stopped in front of them
+// (P3HIP_DEBUG_STOP_BLOCK = the block count, or any earlier block).
+int p3hip_debug_tfm(p3hip_engine* e, int which, float* out, int n_positions) {
+  if (!e->tfm || e->sym) { e->err = "p3hip_debug_tfm: only on a transformer engine without P3HIP_FLAG_SYMMETRY_AVG"; return 1; }
+  if (which < 0 || which > 3) { e->err = "p3hip_debug_tfm: which must be 0 (q), 1 (k), 2 (v) or 3 (o)"; return 1; }
+  if (n_positions < 1 || n_positions > e->last_npos) { e->err = "p3hip_debug_tfm: more positions than the last run had"; return 1; }
+  if (!e->bind()) return 1;
+  const size_t d = (size_t)e->wf.model_C;
+  const size_t per = (size_t)e->rows * p3::kTfmLPad * d;
+  const size_t n = (size_t)n_positions * (which < 3 ? p3::kTfmLPad : kNLoc) * d;
+  const _Float16* src = which < 3 ? e->d_qkv + which * per : e->d_t;
+  std::vector<_Float16> h(n);
+  hipStreamSynchronize(e->stream);
+  if (hipMemcpy(h.data(), src, n * 2, hipMemcpyDeviceToHost) != hipSuccess) return 2;
   for (size_t i = 0; i < n; ++i) out[i] = (float)h[i];
   return 0;
 }

@@ -29,7 +29,7 @@ EXPORTS = [
     "p3hip_last_error", "p3hip_forward_resident", "p3hip_upload", "p3hip_sync", "p3hip_get_raw",
     "p3hip_time_trunk_kernel", "p3hip_flops_per_position", "p3hip_graph_state",
     "p3hip_cache_enable", "p3hip_load_slot_keyed", "p3hip_get_slot_keyed", "p3hip_cache_stats",
-    "p3hip_blockw_stamps", "p3hip_debug_x", "p3hip_rope_table", "p3hip_rope_table_dim",
+    "p3hip_blockw_stamps", "p3hip_debug_x", "p3hip_debug_tfm", "p3hip_rope_table", "p3hip_rope_table_dim",
     "p3hip_int8_calibrate", "p3hip_int8_scales", "p3hip_int8_set_scales",
     "p3hip_set_symmetries", "p3hip_symmetry_maps",
 ]
@@ -250,6 +250,15 @@ class HipEngine:
         self._L.p3hip_debug_x.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         self._ck(self._L.p3hip_debug_x(self._h, out.ctypes.data, n), "debug_x")
         return out.reshape(n, channels // 8, 361, 8).transpose(0, 1, 3, 2).reshape(n, channels, 361)
+
+    def debug_tfm(self, which: int, n: int, heads: int, head_dim: int) -> np.ndarray:
+        """what the last transformer block that ran left in device memory (p3hip.h p3hip_debug_tfm): which 0, 1, 2 = q,
+        k, v as [n][heads][384][head_dim] floats, padding rows included; 3 = o as [n][361][heads * head_dim]"""
+        shape = (n, heads, 384, head_dim) if which < 3 else (n, 361, heads * head_dim)
+        out = np.zeros(shape, np.float32)
+        self._L.p3hip_debug_tfm.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        self._ck(self._L.p3hip_debug_tfm(self._h, which, out.ctypes.data, n), "debug_tfm")
+        return out
 
     def blockw_stamps(self) -> np.ndarray:
         """s_memtime stamps of k_blockw's _diag twin (P3HIP_BLOCKW=1 P3HIP_BLOCKW_DIAG=1): [wg 8][block 16][wave 4][24]"""

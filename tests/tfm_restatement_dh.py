@@ -10,7 +10,10 @@ tfm_restatement performs, in the same order, so the outputs are bit for bit the 
 fp16=True rounds where transformer.hip stores fp16, as tfm_restatement does.  At head width 64 k_tfm_attn's softmax is
 online over blocks of 64 keys: a numerator is rounded to fp16 relative to the running maximum rather than the row's
 maximum; both make it at most 1, so exp(s - max) rounded once stands for it here (the same relative step, no storage
-point the emulation lacks).
+point the emulation lacks).  That holds to one rounding of o, which is enough for the output-level bounds this module
+serves; tests/tfm_emulation.py, which judges k_tfm_attn in fp16 ulps, emulates the online form itself and measures the
+difference.  The block is written as its three stages (qkv_stage, attn_stage, ffn_stage: the three kernels), which
+tfm_emulation.py calls one at a time.
 """
 from __future__ import annotations
 
@@ -44,33 +47,53 @@ def fixture_weights(name, qk_scale=None):
     return cfg, W
 
 
-def block(x, W, i, heads, fp16=False, attn_probe=None):
-    """TransformerBlock.call on token-major x [N][361][C] with `heads` heads (tfm_restatement.block, h free)."""
-    p = f"blocks.{i}"
-    t = lambda n: torch.from_numpy(np.asarray(W[f"{p}.{n}"], np.float64))
+def _wt(W, i, n):
+    return torch.from_numpy(np.asarray(W[f"blocks.{i}.{n}"], np.float64))
+
+
+def qkv_stage(x, W, i, heads, fp16=False):
+    """RMSNorm_in, the three projections and RoPE on q and k of block i: x [N][361][C] -> q, k, v [N][361][heads][D]."""
     N, L, C = x.shape
     D = C // heads
     cos, sin = (torch.from_numpy(a)[None, :, None, :] for a in tfm.rope_tables(head_dim=D))
-    res = x
-    h = tfm._rms(x, t("rms_in.scale"), fp16)
-    q, k, v = (h @ t(n + ".w") for n in ("q", "k", "v"))
+    h = tfm._rms(x, _wt(W, i, "rms_in.scale"), fp16)
+    q, k, v = (h @ _wt(W, i, n + ".w") for n in ("q", "k", "v"))
     q, k, v = (a.reshape(N, L, heads, D) for a in (q, k, v))
     q = tfm._r16(tfm._rope(q, cos, sin), fp16)
     k = tfm._r16(tfm._rope(k, cos, sin), fp16)
     v = tfm._r16(v, fp16)
-    s = torch.einsum("nqhd,nkhd->nhqk", q, k) / np.sqrt(D)    # dot_product_attention: no mask, scale 1/sqrt(D)
+    return q, k, v
+
+
+def attn_stage(q, k, v, fp16=False, attn_probe=None):
+    """dot_product_attention (no mask, scale 1 / sqrt(D)) on q, k, v [N][361][heads][D] -> o [N][361][C]; fp16: the
+    numerators rounded once, relative to the row's maximum."""
+    N, L, heads, D = q.shape
+    s = torch.einsum("nqhd,nkhd->nhqk", q, k) / np.sqrt(D)
     e = torch.exp(s - s.amax(-1, keepdim=True))
     pr = e / e.sum(-1, keepdim=True)
     if attn_probe is not None:
         attn_probe.append(pr)
     o = torch.einsum("nhqk,nkhd->nqhd", tfm._r16(e, fp16), v) / e.sum(-1).permute(0, 2, 1)[..., None]
-    o = tfm._r16(o.reshape(N, L, C), fp16)
-    x = res + o @ t("o.w")
+    return tfm._r16(o.reshape(N, L, heads * D), fp16)
+
+
+def ffn_stage(o, x, W, i, fp16=False):
+    """o . Wo + x, RMSNorm_out, SwiGLU, . Wdown + residual of block i: o, x [N][361][C] -> the next x."""
+    x = x + o @ _wt(W, i, "o.w")
     res = x
-    h = tfm._rms(x, t("rms_out.scale"), fp16)
-    g = h @ t("ffn_gate.w")
-    u = tfm._r16(F.silu(g) * (h @ t("ffn_up.w")), fp16)
-    return tfm._r16(res + u @ t("ffn_down.w"), fp16)
+    h = tfm._rms(x, _wt(W, i, "rms_out.scale"), fp16)
+    g = h @ _wt(W, i, "ffn_gate.w")
+    u = tfm._r16(F.silu(g) * (h @ _wt(W, i, "ffn_up.w")), fp16)
+    return tfm._r16(res + u @ _wt(W, i, "ffn_down.w"), fp16)
+
+
+def block(x, W, i, heads, fp16=False, attn_probe=None):
+    """TransformerBlock.call on token-major x [N][361][C] with `heads` heads (tfm_restatement.block, h free), in its
+    three stages: the three kernels of transformer.hip, which tests/tfm_emulation.py judges one at a time."""
+    q, k, v = qkv_stage(x, W, i, heads, fp16)
+    o = attn_stage(q, k, v, fp16, attn_probe)
+    return ffn_stage(o, x, W, i, fp16)
 
 
 def forward(cfg, W: Dict[str, np.ndarray], planes_nhwc, feats, fp16=False, attn_probe=None) -> Dict[str, np.ndarray]:

@@ -372,12 +372,13 @@ def bounds(cfg, k, hot=False):
     return BOUNDS["hot"] if hot else BOUNDS[kind_of(cfg, k)]
 
 
-def check_block(engine_x, emu_x, scale, block="?", slots=None, max_err=16.0, min_identical=0.0):
+def check_block(engine_x, emu_x, scale, block="?", slots=None, max_err=16.0, min_identical=0.0, head_width=None):
     """Compare the engine's x after one block ([n, C, 361] or [n, C, 19, 19]) with the emulation's from the same input.
-    Returns the statistics; on failure raises AssertionError naming the worst (block, slot, channel group, point)."""
+    Returns the statistics; on failure raises AssertionError naming the worst (block, slot, channel group, point).
+    head_width (tests/tfm_emulation.py): the channels are attention heads of that width, and the head is named too."""
     e = np.asarray(engine_x, np.float64).reshape(len(engine_x), -1, 361)
     m = np.asarray(emu_x, np.float64).reshape(e.shape)
-    slots = list(range(len(e))) if slots is None else list(slots)
+    slots = list(range(len(e))) if slots is None else [int(s) for s in slots]
     d = np.abs(e - m)
     err = d / (fp16_ulp(m) + FLOOR_REL * float(scale))
     err = np.where(np.isfinite(e), err, np.inf)
@@ -394,9 +395,13 @@ def check_block(engine_x, emu_x, scale, block="?", slots=None, max_err=16.0, min
         bad_g = [int(g) for g in np.nonzero(st["group"] > max_err)[0]]
         bad_s = [slots[int(s)] for s in np.nonzero(st["slot"] > max_err)[0]]
         bad_r = [k for k, v in st["region"].items() if v > max_err]
+        heads = "" if head_width is None else (
+            f"head {c // head_width} lane {c % head_width}, heads over the bound "
+            f"{[int(h) for h in np.nonzero(err.reshape(len(e), -1, head_width, 361).max(axis=(0, 2, 3)) > max_err)[0]]}, "
+            + (lambda t: f"tokens over the bound {t.min()}..{t.max()}, " if len(t) else "")(np.nonzero(err.max(axis=(0, 1)) > max_err)[0]))
         raise AssertionError(
             f"block {block}: max err {st['max_err']:.3g} (bound {max_err}) identical {st['identical']:.4f} "
-            f"(bound {min_identical}); worst at slot {slots[n]} channel {c} (group {c // 8}) point {p} "
+            f"(bound {min_identical}); worst at slot {slots[n]} channel {c} (group {c // 8}) {heads}point {p} "
             f"(row {p // 19} col {p % 19}, {REGION_NAMES[REGION[p]]}): engine {e[n, c, p]!r} emulation {m[n, c, p]!r}; "
             f"over the bound: regions {bad_r} groups {bad_g[:12]}{'...' if len(bad_g) > 12 else ''} "
             f"slots {bad_s[:12]}{'...' if len(bad_s) > 12 else ''}")
