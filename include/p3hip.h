@@ -104,7 +104,14 @@ typedef struct p3hip_engine p3hip_engine;
 #define P3HIP_FLAG_INT8 16u         /* calibrated INT8 inference (TensorRT's INT8 engine with a MinMax calibrator,
                                        python/trt_convert.py, cc/nn/engine/trt_calibrator.h): the convs of the layer-wise
                                        blocks run on int8 inputs and weights.  Layer-wise trunks
-                                       only: p3hip_create returns NULL for any other trunk.  See p3hip_int8_* below */
+                                       only: p3hip_create returns NULL for any other trunk (the C = 256 btl trunks have
+                                       P3HIP_FLAG_INT8_FUSED).  See p3hip_int8_* below */
+#define P3HIP_FLAG_INT8_FUSED 64u   /* calibrated INT8 inference of the trunks that run fused block kernels: C = 256 /
+                                       C_b = 128 trunks of btl blocks with 1, 2 or 3 inner layers (b12c256btl3), broadcast
+                                       blocks at any interval.  Every btl block is one launch of an int8 block kernel whose
+                                       activations stay in LDS ("Fused INT8 blocks"); p3hip_int8_* as
+                                       for P3HIP_FLAG_INT8, (inner layers + 2) quantized tensors per btl block.
+                                       p3hip_create returns NULL for any other trunk and for both INT8 flags together */
 #define P3HIP_FLAG_SYMMETRY_AVG 32u /* every slot a run evaluates is evaluated under each symmetry of the engine's set
                                        (default: all eight) and the results averaged on the device, rotated back into the
                                        orientation the slot was loaded in.  Needs 8 x batch_size <= 65536.  See
@@ -170,9 +177,10 @@ int p3hip_load_slot_keyed(p3hip_engine* e, int slot, const p3hip_features* f, ui
 int p3hip_get_slot_keyed(p3hip_engine* e, int slot, p3hip_result* out, int* symmetry, int* from_cache);
 int p3hip_cache_stats(const p3hip_engine* e, uint64_t out[4]);
 
-/* ---- calibrated INT8 (P3HIP_FLAG_INT8) ----------------------------------------------------------------
- * The quantized tensors are the inputs of every conv of the layer-wise blocks, numbered block by block, conv by conv
- * (the order of the block's .p3w convs).  Each has one symmetric activation scale s_a = max |v| / 127.
+/* ---- calibrated INT8 (P3HIP_FLAG_INT8, P3HIP_FLAG_INT8_FUSED) ---------------------------------------------
+ * The quantized tensors are the inputs of every conv of the layer-wise blocks (INT8_FUSED: of the btl blocks), numbered
+ * block by block, conv by conv (the order of the block's .p3w convs).  Each has one symmetric activation scale
+ * s_a = max |v| / 127.
  *   p3hip_int8_calibrate   one p3hip_run on the fp16 plan (results fetched with p3hip_get_slot as usual) that also
  *                          folds max |v| of every quantized tensor into the engine's running maxima and sets
  *                          s_a = max / 127 from everything observed so far: the MinMax calibrator, called once per

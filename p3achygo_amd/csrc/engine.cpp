@@ -26,6 +26,7 @@
 
 #include "../../include/p3hip.h"
 #include "kernels.h"
+#include "block_i8.h"
 #include "lconv_i8.h"
 #include "slot_state.h"
 #include "symmetry.h"
@@ -355,7 +356,9 @@ struct p3hip_engine {
   // P3HIP_FLAG_INT8: the layer-wise blocks' convs run on int8 inputs with per-tensor activation
   // scales.  amax: running per-tensor maxima of the calibration runs (float bits, atomicMax); scale: the s_a = max / 127
   // the int8 kernels read at launch time, so that a replayed graph sees new scales.
-  bool int8 = false, calibrating = false, have_scales = false;
+  // P3HIP_FLAG_INT8_FUSED (section 9, "Fused INT8 blocks"): int8 is set as well; the C = 256 / C_b = 128 btl blocks are
+  // planned layer by layer (the fp16 plan the calibration runs) and run as one k_block_i8 launch each (csrc/block_i8.hip)
+  bool int8 = false, i8f = false, calibrating = false, have_scales = false;
   int n_q = 0;
   unsigned* d_amax = nullptr;
   float* d_ascale = nullptr;
@@ -466,17 +469,24 @@ size_t add_stream(Arena& ar, const std::vector<_Float16>& s, int& nms, int cout_
 bool build_plan(p3hip_engine* e, Arena& ar) {
   const WeightFile& wf = e->wf;
   const int C = wf.C, Cb = wf.Cb;
-  const bool fused = (C == 256 && Cb == 128) || (C == 128 && Cb == 64);
+  const bool i8f = e->i8f;
+  const bool fused = !i8f && ((C == 256 && Cb == 128) || (C == 128 && Cb == 64));
   const bool classic = wf.btype == 2 && C == 192 && wf.inner == 2;   // b15c192_classic
   const bool bottleneck_ok = wf.btype == 1 || (wf.btype == 0 && wf.inner >= 1 && wf.inner <= 3);
-  const bool layerwise = (C == 384 && Cb == 192 && bottleneck_ok) || classic;
+  // P3HIP_FLAG_INT8_FUSED: the btl trunks of the fused block kernel's C = 256 width, alone
+  const bool i8f_ok = i8f && !(e->flags & P3HIP_FLAG_INT8) && C == 256 && Cb == 128 && wf.btype == 0 && wf.inner >= 1 &&
+                      wf.inner <= 3;
+  const bool layerwise = (C == 384 && Cb == 192 && bottleneck_ok) || classic || i8f_ok;
   const bool v_ok = wf.V == 32 || wf.V == 48 || wf.V == 64 || wf.V == 80;
   // transformer trunk: the file's C is the model width d and Cb the head count (include/p3hip.h: d a multiple of 32,
   // 64 <= d <= 384, head width d / heads 32 or 64); the stream is padded to C = p3::tfm_stream_width(d), and V is what
   // the heads of that width serve (the fused heads at C = 128 / 256: {32, 48, 64}; the C = 384 heads: v_ok)
   const bool tfm = wf.btype == 3 && p3::tfm_supported(wf.model_C, Cb) && C == p3::tfm_stream_width(wf.model_C) &&
                    (C == 384 || p3::heads_fusable(C, wf.V));
-  if ((!((fused && bottleneck_ok) || layerwise) && !tfm) || wf.H != 32 || !v_ok) {
+  // (a trunk the fp16 engine serves and INT8_FUSED does not is refused below, with INT8_FUSED's own message)
+  const bool arch_ok = (fused && bottleneck_ok) || layerwise || tfm ||
+                       (i8f && ((C == 256 && Cb == 128) || (C == 128 && Cb == 64)) && bottleneck_ok);
+  if (!arch_ok || wf.H != 32 || !v_ok) {
     e->err = "unsupported architecture for the HIP engine (need (C, Cb) in {(128,64), (256,128), (384,192)} with "
              "btl (1-3 inner layers) or nbt blocks, or C=192 classic blocks of two convs, or a transformer trunk "
              "(" P3HIP_TRANSFORMER_SET "); H=32, V in {32,48,64,80} (transformer: V in {32,48,64}, and 80 at d > 256))";
@@ -486,6 +496,12 @@ bool build_plan(p3hip_engine* e, Arena& ar) {
   if (tfm) {
     e->tfm_heads = Cb;
     e->tfm_D = wf.model_C / Cb;
+  }
+  if (i8f && !i8f_ok) {
+    e->err = "INT8_FUSED is available only for C = 256 / C_b = 128 trunks of btl blocks with 1, 2 or 3 inner layers "
+             "(b12c256btl3 and its kin, broadcast blocks at any interval), and not together with P3HIP_FLAG_INT8; nbt and "
+             "C = 128 trunks, the layer-wise trunks (P3HIP_FLAG_INT8 serves those) and the transformer are not served";
+    return false;
   }
   if (e->int8 && !layerwise) {
     e->err = "INT8 is available only for layer-wise trunks (C = 384 / C_b = 192 btl or nbt blocks, C = 192 classic "
@@ -508,7 +524,7 @@ bool build_plan(p3hip_engine* e, Arena& ar) {
   // k_blockw serves C = 256 / C_b = 128 btl trunks; the broadcast blocks then run as their own launches
   {
     static const bool want_blockw = getenv("P3HIP_BLOCKW") != nullptr && atoi(getenv("P3HIP_BLOCKW")) != 0;
-    e->blockw = want_blockw && C == 256 && Cb == 128 && wf.btype == 0 && wf.inner >= 1 && wf.inner <= 3;
+    e->blockw = want_blockw && !i8f && C == 256 && Cb == 128 && wf.btype == 0 && wf.inner >= 1 && wf.inner <= 3;
     if (e->blockw) e->bcast_fuse = false;
   }
   bool have_xa = false;   // layer-wise path: u holds mish(bn0(x)) of the next block
@@ -677,7 +693,8 @@ bool build_plan(p3hip_engine* e, Arena& ar) {
       // a broadcast block still activates its input while staging (pre) — every workgroup of
       // an output pass would otherwise redo that VALU work.  `xa` = activated copy of x, in u.
       FoldedBN next_bn0{};
-      const bool next_layerwise = i + 1 < wf.nblocks && !wf.is_broadcast(i + 1);
+      // (an INT8_FUSED block depends on the stored x alone: every block's first conv activates it, pre)
+      const bool next_layerwise = !i8f && i + 1 < wf.nblocks && !wf.is_broadcast(i + 1);
       if (next_layerwise) next_bn0 = fold_bn(ar, wf, "blocks." + std::to_string(i + 1) + ".bn0", C);
       const FoldedBN none{};
       auto add_layer = [&](int j, int kw, int cin, int cout, bool pre, const FoldedBN& pre_bn, bool act, bool res,
@@ -1152,6 +1169,22 @@ bool enqueue_forward(p3hip_engine* e, const Pass& p) {
         if (a.pre) { a.scale_in = e->dev<float>(lp.pre_bn.scale_off); a.shift_in = e->dev<float>(lp.pre_bn.shift_off); }
         if (a.act || a.dual) { a.scale_out = e->dev<float>(lp.out_bn.scale_off); a.shift_out = e->dev<float>(lp.out_bn.shift_off); }
       };
+      if (e->i8f && !e->calibrating) {
+        // one launch runs the block's convs with the activations in LDS; the layers carry its tensors
+        p3::BlockI8Args a{};
+        a.x = e->d_x; a.npos = npos; a.inner = wf.inner;
+        a.act_scale = e->d_ascale; a.q0 = bp.layers[0].qidx;
+        for (size_t j = 0; j < bp.layers.size(); ++j) {
+          const LayerPlan& lp = bp.layers[j];
+          a.w[j] = e->dev<int8_t>(lp.q_off); a.w_scale[j] = e->dev<float>(lp.qs_off);
+          // bn_j is the prologue of conv 0 and the epilogue of conv j - 1
+          const FoldedBN& bn = j == 0 ? lp.pre_bn : bp.layers[j - 1].out_bn;
+          a.scale[j] = e->dev<float>(bn.scale_off); a.shift[j] = e->dev<float>(bn.shift_off);
+        }
+        if (!timed_launch(e, p.timed, [&] { return e->check(p3::launch_block_i8(a, e->n_cu, s), "launch k_block_i8"); }))
+          return false;
+        continue;
+      }
       if (e->int8 && !e->calibrating) {
         // the int8 plan (its callers check int8_ready): the same regions, an int8 tensor where the fp16 plan stores an activated one
         for (const LayerPlan& lp : bp.layers) {
@@ -1373,7 +1406,8 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
   e->direct_results = getenv("P3HIP_NO_DIRECT_RESULTS") == nullptr;
   e->time_run = getenv("P3HIP_TIME_RUN") != nullptr;
   e->blockw_diag = getenv("P3HIP_BLOCKW_DIAG") != nullptr;
-  e->int8 = (flags & P3HIP_FLAG_INT8) != 0;
+  e->int8 = (flags & (P3HIP_FLAG_INT8 | P3HIP_FLAG_INT8_FUSED)) != 0;
+  e->i8f = (flags & P3HIP_FLAG_INT8_FUSED) != 0;
   e->sym = sym;
   e->rows = sym ? p3::kNumSyms * batch_size : batch_size;
   auto fail = [&](const std::string& m) {
@@ -1805,18 +1839,21 @@ double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
                                double* flops_per_launch, const char** kernel_name) {
   const WeightFile& wf = e->wf;
   const BlockPlan* bp = nullptr;
-  int nfused = 0, n3x3 = 0, c3 = 0;
+  int nfused = 0, n3x3 = 0, c3 = 0, nlw = 0;
   for (const BlockPlan& b : e->blocks) {
     if (b.kind == 0 || b.kind == 1) { if (!bp) bp = &b; ++nfused; }   // fused block kernel
-    if (b.kind == 4)
+    if (b.kind == 4) {
+      ++nlw;
       for (const LayerPlan& lp : b.layers)
         if (lp.kw == 3) { ++n3x3; c3 = lp.cin; }
+    }
   }
   if (n_positions < 1 || n_positions > e->batch || iters < 1 || !e->bind() || !int8_ready(e)) return -1.0;
   // The timed kernel (enqueue_forward records an event pair around each of its launches) and its launches per forward
   // pass: the attention kernel k_tfm_attn of transformer trunks, the fused block kernel, or else the 3x3 layer conv
   // k_lconv<3, ..> of layer-wise trunks (C = 384, classic)
-  const int per_pass = e->tfm ? wf.nblocks : (bp ? nfused : n3x3);
+  // (P3HIP_FLAG_INT8_FUSED: k_block_i8, one launch per btl block)
+  const int per_pass = e->tfm ? wf.nblocks : (bp ? nfused : (e->i8f ? nlw : n3x3));
   if (per_pass == 0) return -1.0;
   if (e->sym) {
     // symmetry averaging: the trunk runs over the k copies of the resident slots (p3hip_upload put them in d_sfeats)
@@ -1851,6 +1888,10 @@ double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
     // q.k^T and p.v over the 361 x 361 tokens of every head (algorithmic, not the padded 384 keys)
     flops = 2.0 * n_positions * 2.0 * kNLoc * kNLoc * wf.model_C;
     name = "k_tfm_attn";
+  } else if (e->i8f) {
+    // every conv of one btl block, as for the fp16 block launch below
+    flops = 2.0 * n_positions * kNLoc * (wf.inner * 9.0 * wf.Cb * wf.Cb + 2.0 * wf.C * wf.Cb);
+    name = p3::block_i8_kernel_name();
   } else if (!bp) {
     flops = 2.0 * n_positions * kNLoc * 9.0 * c3 * c3;
     name = e->int8 ? p3::lconv_i8_kernel_name(3, c3, c3) : (c3 == 192 ? "k_lconv<3,192,192>" : "k_lconv<3,64,64>");

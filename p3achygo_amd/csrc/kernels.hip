@@ -1698,6 +1698,10 @@ hipError_t launch_lconv(int kw, int cin, int cout, const LConvArgs& a, int grid,
   P3_LCONV(3, 192, 192, false, false, true, true)     // nbt conv2 / conv4 (t' raw + act(t')), classic conv1 (+x, + next act)
   P3_LCONV(1, 192, 384, false, false, true, false)    // expand + x
   P3_LCONV(1, 192, 384, false, false, true, true)     // expand + x, + the next block's activated input
+  // C = 256 / C_b = 128 btl blocks layer by layer: the fp16 plan P3HIP_FLAG_INT8_FUSED calibrates on
+  P3_LCONV(1, 256, 128, true, true, false, false)
+  P3_LCONV(3, 128, 128, false, true, false, false)
+  P3_LCONV(1, 128, 256, false, false, true, false)
 #undef P3_LCONV
   return hipErrorInvalidValue;
 }

@@ -38,7 +38,8 @@ FLAG_RUN_ALL_SLOTS = 2
 FLAG_SHARED_DEVICE = 4
 FLAG_LAUNCH_GRAPH = 8
 FLAG_INT8 = 16   # calibrated INT8 convs in the layer-wise blocks (include/p3hip.h)
-FLAG_SYMMETRY_AVG = 32   # every slot averaged over a set of the eight symmetries on the device
+FLAG_INT8_FUSED = 64   # calibrated INT8 of the C = 256 btl trunks, one fused int8 block kernel per block (section 9)
+FLAG_SYMMETRY_AVG = 32  # every slot averaged over a set of the eight symmetries on the device
 
 
 class EngineError(RuntimeError):
