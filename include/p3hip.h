@@ -126,6 +126,17 @@ typedef struct p3hip_engine p3hip_engine;
 #define P3HIP_TRANSFORMER_SET \
   "transformer: d a multiple of 32 with 64 <= d <= 384, head width d / heads 32 or 64, every block alike"
 
+/* Conv trunks the engine runs.  (C, C_b) = (128, 64) and (256, 128) run the fused block kernels, (384, 192) and classic
+ * C = 192 the templated layer-wise kernels; every other shape of the set runs layer-wise through kernels that take the
+ * widths as launch arguments (csrc/conv_any.hip), in fp16 only.  There a file's C and C_b are zero-padded to the next
+ * multiple of 64 when the weights are packed (padded channels are exactly 0 everywhere); p3hip_flops_per_position
+ * counts the file's own widths, p3hip_debug_x returns the padded stream.  P3HIP_CONV_ANY=1 in the environment at
+ * p3hip_create sends (384, 192) and classic C = 192 through those kernels too, with bit-identical results.
+ * p3hip_create refuses every other conv trunk with this wording: */
+#define P3HIP_CONV_SET \
+  "conv: C a multiple of 32 with 64 <= C <= 512; btl (1-3 inner layers) and nbt blocks with C_b a multiple of 16, " \
+  "32 <= C_b <= C; classic blocks of two 3x3 convs (C_b ignored); broadcast blocks at any interval >= 2"
+
 /* Creates an engine from a `.p3w` weight file (see p3achygo_amd/netspec.py) for a static
  * batch of `batch_size` slots on HIP device `device_ordinal`.  `version` is the model
  * feature version (engine_factory.cc:37-53; only 1 is supported: 15 planes + 8 scalars).

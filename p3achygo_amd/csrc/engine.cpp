@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <chrono>
 
+#include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <cstdio>
@@ -27,6 +28,7 @@
 #include "../../include/p3hip.h"
 #include "kernels.h"
 #include "block_i8.h"
+#include "conv_any.h"
 #include "lconv_i8.h"
 #include "slot_state.h"
 #include "symmetry.h"
@@ -59,6 +61,10 @@ struct WeightFile {
   // of the stem and the heads are zero-padded to it (pad_transformer_io), so that k_init and the heads of that width
   // serve the trunk unchanged.  model_C == C for every other architecture.
   int model_C = 0;
+  // Conv trunks of the set P3HIP_CONV_SET whose C or C_b is not a multiple of 64: C and Cb become the next multiples of
+  // 64 and every tensor is zero-padded to them (pad_conv); model_C / model_Cb keep the file's widths.  model_Cb == Cb
+  // for every other architecture.
+  int model_Cb = 0;
   std::vector<std::vector<float>> padded;
   std::vector<float> data;
   std::map<std::string, Tensor> tensors;
@@ -108,8 +114,80 @@ struct WeightFile {
       tensors[std::string(e.name, strnlen(e.name, sizeof e.name))] = t;
     }
     model_C = C;
+    model_Cb = Cb;
+    if (conv_set(C, Cb, btype, inner, bint) && H == 32) {
+      const int Cp = (C + 63) / 64 * 64, Cbp = btype == 2 ? Cb : (Cb + 63) / 64 * 64;
+      if (Cp != C || Cbp != Cb) pad_conv(Cp, Cbp);
+    }
     if (btype == 3 && p3::tfm_supported(C, Cb) && p3::tfm_stream_width(C) != C) pad_transformer_io(p3::tfm_stream_width(C));
     return true;
+  }
+  // The conv trunks of include/p3hip.h P3HIP_CONV_SET (the file's own widths)
+  static bool conv_set(int C, int Cb, int btype, int inner, int bint) {
+    if (C % 32 != 0 || C < 64 || C > 512 || bint < 2) return false;
+    if (btype == 2) return inner == 2;                                   // classic: two 3x3 convs, C_b is ignored
+    if (btype != 1 && !(btype == 0 && inner >= 1 && inner <= 3)) return false;
+    return Cb % 16 == 0 && Cb >= 32 && Cb <= C;
+  }
+  // Every tensor with a C or C_b axis zero-padded to Cp / Cbp channels: conv rows and columns, the stem's weights and
+  // bias, and BN gamma = beta = mean = var = 0, which folds to scale = shift = 0.  mish(0) = 0, so a padded channel of
+  // x, t and u is exactly 0 everywhere (the broadcast dense adds its bias to it; the zero bn1 that follows removes it).
+  void pad_conv(int Cp, int Cbp) {
+    auto pad = [&](const std::string& n, const std::vector<int>& od, const std::vector<int>& nd) {
+      auto it = tensors.find(n);
+      size_t on = 1, nn = 1;
+      for (int d : od) on *= d;
+      for (int d : nd) nn *= d;
+      if (it == tensors.end() || it->second.size() != on) return;   // build_plan reports it as missing
+      std::vector<float> w(nn, 0.0f);
+      std::vector<int> idx(od.size(), 0);
+      for (size_t i = 0; i < on; ++i) {
+        size_t o = 0;
+        for (size_t k = 0; k < od.size(); ++k) o = o * nd[k] + idx[k];
+        w[o] = it->second.data[i];
+        for (int k = (int)od.size() - 1; k >= 0; --k) {
+          if (++idx[k] < od[k]) break;
+          idx[k] = 0;
+        }
+      }
+      padded.push_back(std::move(w));
+      Tensor t;
+      t.dims = nd;
+      t.data = padded.back().data();
+      it->second = t;
+    };
+    auto bn = [&](const std::string& n, int c, int cp) {
+      for (const char* f : {".gamma", ".beta", ".mean", ".var"}) pad(n + f, {c}, {cp});
+    };
+    auto conv = [&](const std::string& n, int k, int ci, int co, int cip, int cop) {
+      pad(n + ".w", {k, k, ci, co}, {k, k, cip, cop});
+    };
+    pad("init_conv.w", {5, 5, 15, C}, {5, 5, 15, Cp});
+    pad("init_game.w", {8, C}, {8, Cp});
+    pad("init_game.b", {C}, {Cp});
+    for (int i = 0; i < nblocks; ++i) {
+      const std::string p = "blocks." + std::to_string(i);
+      if (is_broadcast(i) || btype == 2) {
+        const int k = btype == 2 && !is_broadcast(i) ? 3 : 1;
+        for (int j = 0; j < 2; ++j) {
+          bn(p + ".bn" + std::to_string(j), C, Cp);
+          conv(p + ".conv" + std::to_string(j), k, C, C, Cp, Cp);
+        }
+      } else {
+        const int last = btype == 0 ? inner + 1 : 5;
+        bn(p + ".bn0", C, Cp);
+        conv(p + ".conv0", 1, C, Cb, Cp, Cbp);
+        for (int j = 1; j < last; ++j) {
+          bn(p + ".bn" + std::to_string(j), Cb, Cbp);
+          conv(p + ".conv" + std::to_string(j), 3, Cb, Cb, Cbp, Cbp);
+        }
+        bn(p + ".bn" + std::to_string(last), Cb, Cbp);
+        conv(p + ".conv" + std::to_string(last), 1, Cb, C, Cbp, Cp);
+      }
+    }
+    for (const char* n : {"policy.conv_p", "policy.conv_g", "value.conv"}) conv(n, 1, C, 32, Cp, 32);
+    C = Cp;
+    Cb = Cbp;
   }
   // [..][C] -> [..][Cp] (init conv, game dense) and [C][32] -> [Cp][32] (the head convs), zeros in the new channels
   void pad_transformer_io(int Cp) {
@@ -374,6 +452,10 @@ struct p3hip_engine {
   int rows = 0;
   unsigned char* d_sfeats = nullptr;
   float* d_cout = nullptr;
+  // The layer-wise conv trunk through the kernels of conv_any.hip (widths as launch arguments): every trunk of
+  // P3HIP_CONV_SET that the templated kernels do not serve, and with P3HIP_CONV_ANY=1 in the environment at create the
+  // templated layer-wise shapes too (C = 384 / C_b = 192 btl and nbt, classic C = 192), bit for bit the same results
+  bool conv_any = false, conv_any_env = false;
   bool heads_fused = false;   // k_headsx: the head convs inside the heads kernel (C <= 256; P3HIP_NO_HFUSE clears it)
   std::map<std::string, size_t> head_off;
 
@@ -470,13 +552,22 @@ bool build_plan(p3hip_engine* e, Arena& ar) {
   const WeightFile& wf = e->wf;
   const int C = wf.C, Cb = wf.Cb;
   const bool i8f = e->i8f;
-  const bool fused = !i8f && ((C == 256 && Cb == 128) || (C == 128 && Cb == 64));
-  const bool classic = wf.btype == 2 && C == 192 && wf.inner == 2;   // b15c192_classic
+  // a conv file whose widths were padded (WeightFile::pad_conv) never takes the plan of the shape it was padded to
+  const bool exact = wf.btype == 3 || (wf.model_C == C && wf.model_Cb == Cb);
+  const bool fused = !i8f && exact && ((C == 256 && Cb == 128) || (C == 128 && Cb == 64));
+  const bool classic = wf.btype == 2 && wf.inner == 2;                 // two 3x3 convs C -> C
+  const bool classic192 = classic && exact && C == 192;                // b15c192_classic
   const bool bottleneck_ok = wf.btype == 1 || (wf.btype == 0 && wf.inner >= 1 && wf.inner <= 3);
   // P3HIP_FLAG_INT8_FUSED: the btl trunks of the fused block kernel's C = 256 width, alone
-  const bool i8f_ok = i8f && !(e->flags & P3HIP_FLAG_INT8) && C == 256 && Cb == 128 && wf.btype == 0 && wf.inner >= 1 &&
+  const bool i8f_ok = i8f && !(e->flags & P3HIP_FLAG_INT8) && exact && C == 256 && Cb == 128 && wf.btype == 0 && wf.inner >= 1 &&
                       wf.inner <= 3;
-  const bool layerwise = (C == 384 && Cb == 192 && bottleneck_ok) || classic || i8f_ok;
+  const bool fused_shape = exact && ((C == 256 && Cb == 128) || (C == 128 && Cb == 64)) && bottleneck_ok;
+  const bool lw_shape = (exact && C == 384 && Cb == 192 && bottleneck_ok) || classic192;   // the templated k_lconv's shapes
+  // every other conv trunk of P3HIP_CONV_SET: layer-wise through conv_any.hip, C and Cb padded to multiples of 64
+  const bool any = !fused_shape && !lw_shape &&
+                   WeightFile::conv_set(wf.model_C, wf.model_Cb, wf.btype, wf.inner, wf.bint) && C % 64 == 0 &&
+                   (wf.btype == 2 || Cb % 64 == 0);
+  const bool layerwise = lw_shape || i8f_ok || any;
   const bool v_ok = wf.V == 32 || wf.V == 48 || wf.V == 64 || wf.V == 80;
   // transformer trunk: the file's C is the model width d and Cb the head count (include/p3hip.h: d a multiple of 32,
   // 64 <= d <= 384, head width d / heads 32 or 64); the stream is padded to C = p3::tfm_stream_width(d), and V is what
@@ -485,13 +576,20 @@ bool build_plan(p3hip_engine* e, Arena& ar) {
                    (C == 384 || p3::heads_fusable(C, wf.V));
   // (a trunk the fp16 engine serves and INT8_FUSED does not is refused below, with INT8_FUSED's own message)
   const bool arch_ok = (fused && bottleneck_ok) || layerwise || tfm ||
-                       (i8f && ((C == 256 && Cb == 128) || (C == 128 && Cb == 64)) && bottleneck_ok);
+                       (i8f && fused_shape);
   if (!arch_ok || wf.H != 32 || !v_ok) {
-    e->err = "unsupported architecture for the HIP engine (need (C, Cb) in {(128,64), (256,128), (384,192)} with "
-             "btl (1-3 inner layers) or nbt blocks, or C=192 classic blocks of two convs, or a transformer trunk "
-             "(" P3HIP_TRANSFORMER_SET "); H=32, V in {32,48,64,80} (transformer: V in {32,48,64}, and 80 at d > 256))";
+    e->err = "unsupported architecture for the HIP engine (need a conv trunk (" P3HIP_CONV_SET "), or a transformer "
+             "trunk (" P3HIP_TRANSFORMER_SET "); H=32, V in {32,48,64,80} (transformer: V in {32,48,64}, and 80 at "
+             "d > 256))";
     return false;
   }
+  if (any && e->int8) {
+    e->err = std::string(e->i8f ? "INT8_FUSED" : "INT8") + " is not available for this conv trunk: P3HIP_FLAG_INT8 "
+             "serves C = 384 / C_b = 192 btl or nbt blocks and C = 192 classic blocks, P3HIP_FLAG_INT8_FUSED serves "
+             "C = 256 / C_b = 128 btl blocks with 1, 2 or 3 inner layers; the other widths run in fp16 only";
+    return false;
+  }
+  e->conv_any = any || (e->conv_any_env && lw_shape && !e->int8);
   e->tfm = tfm;
   if (tfm) {
     e->tfm_heads = Cb;
@@ -509,8 +607,9 @@ bool build_plan(p3hip_engine* e, Arena& ar) {
     return false;
   }
   // slice width of the per-position kernels that stage C channels (k_conv1x1 family)
-  const int CB = classic ? 64 : ((layerwise || tfm) ? 128 : Cb);
-  const int CPI = classic ? 64 : 128;   // output pass width of the init conv
+  // (layer-wise: p3::conv_any_slice(C) = 64 at classic C = 192, 128 at C = 384 and at INT8_FUSED's C = 256)
+  const int CB = layerwise ? p3::conv_any_slice(C) : (tfm ? 128 : Cb);
+  const int CPI = layerwise ? p3::conv_any_init_pass(C) : 128;   // output pass width of the init conv
   // init conv
   {
     std::vector<_Float16> s;
@@ -844,7 +943,7 @@ bool build_plan(p3hip_engine* e, Arena& ar) {
             for (int el = 0; el < 8; ++el)
               af.push_back((_Float16)w[(size_t)(st * 32 + 8 * (lane >> 4) + el) * 96 + ct * 16 + (lane & 15)]);
       e->heads_conv_a_off = ar.add(af.data(), af.size() * 2);
-      e->heads_fused = getenv("P3HIP_NO_HFUSE") == nullptr;
+      e->heads_fused = getenv("P3HIP_NO_HFUSE") == nullptr && !e->conv_any;
     }
     FoldedBN g = fold_bn(ar, wf, "policy.gpool_bn", 32);
     e->head_off["gbn_scale"] = g.scale_off;
@@ -1110,12 +1209,17 @@ bool enqueue_forward(p3hip_engine* e, const Pass& p) {
   const WeightFile& wf = e->wf;
   const int C = wf.C, npos = p.npos;
   hipStream_t s = e->stream;
+  const bool any = e->conv_any;
+  auto conv1x1 = [&](int which, const p3::Conv1x1Args& a) {
+    return any ? p3::launch_conv1x1_any(C, which, a, e->n_cu, s) : p3::launch_conv1x1(C, which, a, e->n_cu, s);
+  };
   {
     p3::InitArgs a{};
     a.feats = p.feats; a.x = e->d_x; a.npos = npos;
     a.wstream = e->d_arena + e->init_stream_off; a.nms_total = e->init_nms;
     a.game_w = e->dev<float>(e->game_w_off); a.game_b = e->dev<float>(e->game_b_off);
-    if (!e->check(p3::launch_init(C, a, grid_for(e, npos, 1), s), "launch k_init")) return false;
+    if (!e->check(e->conv_any ? p3::launch_init_any(C, a, grid_for(e, npos, 1), s)
+                              : p3::launch_init(C, a, grid_for(e, npos, 1), s), "launch k_init")) return false;
   }
 #ifdef P3_DIAG
   e->launch_index = 0;
@@ -1146,18 +1250,19 @@ bool enqueue_forward(p3hip_engine* e, const Pass& p) {
       c0.in = e->d_x; c0.out16 = e->d_t; c0.npos = npos;
       c0.wstream = e->d_arena + bp.stream_off; c0.nms_total = bp.nms;
       c0.scale = e->dev<float>(bp.bn[0].scale_off); c0.shift = e->dev<float>(bp.bn[0].shift_off);
-      if (!bp.first_fused && !e->check(p3::launch_conv1x1(C, 0, c0, e->n_cu, s), "launch conv_first")) return false;
+      if (!bp.first_fused && !e->check(conv1x1(0, c0), "launch conv_first")) return false;
       p3::BDenseArgs d{};
       d.t = e->d_t; d.u = e->d_u; d.npos = npos;
       d.wstream = e->d_arena + bp.stream2_off; d.nms_total = bp.nms2;
       d.bias = e->dev<float>(bp.dense_bias_off);
       d.scale = e->dev<float>(bp.bn[1].scale_off); d.shift = e->dev<float>(bp.bn[1].shift_off);
       if (!(bp.first_fused && bp.dense_fused) &&
-          !e->check(p3::launch_bdense(C, d, grid_for(e, npos, 1), s), "launch bdense")) return false;
+          !e->check(any ? p3::launch_bdense_any(C, d, grid_for(e, npos, 1), s)
+                        : p3::launch_bdense(C, d, grid_for(e, npos, 1), s), "launch bdense")) return false;
       p3::Conv1x1Args c1{};
       c1.in = e->d_u; c1.out16 = e->d_x; c1.npos = npos;
       c1.wstream = e->d_arena + bp.stream3_off; c1.nms_total = bp.nms3;
-      if (!bp.last_fused && !e->check(p3::launch_conv1x1(C, 1, c1, e->n_cu, s), "launch conv_last")) return false;
+      if (!bp.last_fused && !e->check(conv1x1(1, c1), "launch conv_last")) return false;
     } else if (bp.kind == 4) {
       const size_t half = (size_t)e->rows * wf.Cb * kNLoc;   // elements of one C_b-channel tensor
       _Float16* bufs[5] = {e->d_x, e->d_t, e->d_t + half, e->d_u, e->d_u + half};
@@ -1209,7 +1314,10 @@ bool enqueue_forward(p3hip_engine* e, const Pass& p) {
         p3::LConvArgs a{};
         fill(a, lp);
         a.wstream = e->d_arena + lp.stream_off; a.nms_total = lp.nms;
-        auto launch = [&] { return e->check(p3::launch_lconv(lp.kw, lp.cin, lp.cout, a, e->n_cu, s), "launch k_lconv"); };
+        auto launch = [&] {
+          return e->check(any ? p3::launch_lconv_any(lp.kw, lp.cin, lp.cout, a, e->n_cu, s)
+                              : p3::launch_lconv(lp.kw, lp.cin, lp.cout, a, e->n_cu, s), any ? "launch k_lconv_any" : "launch k_lconv");
+        };
         if (!timed_launch(e, lp.kw == 3 ? p.timed : nullptr, launch)) return false;
       }
     } else if (e->blockw && bp.kind == 0) {
@@ -1249,7 +1357,7 @@ bool enqueue_forward(p3hip_engine* e, const Pass& p) {
     p3::Conv1x1Args c{};
     c.in = e->d_x; c.out32 = e->d_hp; c.npos = npos;
     c.wstream = e->d_arena + e->heads_stream_off; c.nms_total = e->heads_nms;
-    if (!e->heads_fused && !e->check(p3::launch_conv1x1(C, 2, c, e->n_cu, s), "launch head convs")) return false;
+    if (!e->heads_fused && !e->check(conv1x1(2, c), "launch head convs")) return false;
     p3::HeadsArgs h{};
     h.x = e->d_x;
     h.conv_a = e->d_arena + e->heads_conv_a_off;
@@ -1406,6 +1514,7 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
   e->direct_results = getenv("P3HIP_NO_DIRECT_RESULTS") == nullptr;
   e->time_run = getenv("P3HIP_TIME_RUN") != nullptr;
   e->blockw_diag = getenv("P3HIP_BLOCKW_DIAG") != nullptr;
+  e->conv_any_env = getenv("P3HIP_CONV_ANY") != nullptr && atoi(getenv("P3HIP_CONV_ANY")) != 0;
   e->int8 = (flags & (P3HIP_FLAG_INT8 | P3HIP_FLAG_INT8_FUSED)) != 0;
   e->i8f = (flags & P3HIP_FLAG_INT8_FUSED) != 0;
   e->sym = sym;
@@ -1431,6 +1540,10 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
   const int C = e->wf.C;
   const size_t B = batch_size;
   const size_t R = e->rows;   // the per-row device buffers: 8 x batch copies with P3HIP_FLAG_SYMMETRY_AVG
+  // t holds a C-channel tensor (broadcast blocks, classic blocks, the transformer's o) or, in a layer-wise btl / nbt block,
+  // two C_b-channel ones side by side (enqueue_forward, regions 1 and 2): 2 C_b > C where C_b > C / 2 (P3HIP_CONV_SET
+  // allows C_b up to C, and padding C_b to a multiple of 64 can pass C / 2 as well)
+  const size_t Ct = (e->wf.btype == 0 || e->wf.btype == 1) ? std::max<size_t>(C, 2 * (size_t)e->wf.Cb) : (size_t)C;
   const size_t qkv_bytes = 3 * R * p3::kTfmLPad * (size_t)e->wf.model_C * 2;   // heads x head width = model width
   bool ok = e->check(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking), "hipStreamCreate") &&
             e->check(hipMalloc((void**)&e->d_arena, ar.host.size()), "hipMalloc arena") &&
@@ -1443,7 +1556,7 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
             e->check(hipMalloc((void**)&e->d_res, B * p3::kResultFloats * 4), "hipMalloc results") &&
             e->check(hipMalloc((void**)&e->d_feats, R * kFeatBytes), "hipMalloc feats") &&
             e->check(hipMalloc((void**)&e->d_x, R * C * kNLoc * 2), "hipMalloc x") &&
-            e->check(hipMalloc((void**)&e->d_t, R * C * kNLoc * 2), "hipMalloc t") &&
+            e->check(hipMalloc((void**)&e->d_t, R * Ct * kNLoc * 2), "hipMalloc t") &&
             e->check(hipMalloc((void**)&e->d_u, R * C * kNLoc * 2), "hipMalloc u") &&
             (e->wf.btype != 1 || e->check(hipMalloc((void**)&e->d_s, R * e->wf.Cb * kNLoc * 2), "hipMalloc s")) &&
             (!e->tfm || e->check(hipMalloc((void**)&e->d_qkv, qkv_bytes), "hipMalloc qkv")) &&
@@ -1820,7 +1933,7 @@ int p3hip_get_raw(p3hip_engine* e, int slot, float* out) {
 
 void p3hip_flops_per_position(const p3hip_engine* e, double* total, double* conv3x3) {
   const WeightFile& w = e->wf;
-  const double C = w.model_C, Cb = w.Cb, H = w.H, V = w.V, L = kNLoc;
+  const double C = w.model_C, Cb = w.model_Cb, H = w.H, V = w.V, L = kNLoc;
   double mac = L * 25 * 15 * C + 8 * C, mac3 = 0;
   for (int i = 0; i < w.nblocks; ++i) {
     if (e->tfm) mac += L * 4 * C * C + 2 * L * L * C + L * 3 * C * 2 * C;   // q k v o, q.k^T and p.v, SwiGLU
@@ -1893,8 +2006,11 @@ double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
     flops = 2.0 * n_positions * kNLoc * (wf.inner * 9.0 * wf.Cb * wf.Cb + 2.0 * wf.C * wf.Cb);
     name = p3::block_i8_kernel_name();
   } else if (!bp) {
-    flops = 2.0 * n_positions * kNLoc * 9.0 * c3 * c3;
-    name = e->int8 ? p3::lconv_i8_kernel_name(3, c3, c3) : (c3 == 192 ? "k_lconv<3,192,192>" : "k_lconv<3,64,64>");
+    // (conv_any: the file's own width, not the padded one the kernel runs)
+    const double w3 = e->conv_any ? (wf.btype == 2 ? wf.model_C : wf.model_Cb) : c3;
+    flops = 2.0 * n_positions * kNLoc * 9.0 * w3 * w3;
+    name = e->int8 ? p3::lconv_i8_kernel_name(3, c3, c3)
+                   : (e->conv_any ? p3::lconv_any_kernel_name(3) : (c3 == 192 ? "k_lconv<3,192,192>" : "k_lconv<3,64,64>"));
   } else {
     const double n3 = (wf.btype == 0) ? wf.inner : 4;
     // every conv the block kernel executes: the inner 3x3s plus the 1x1 reduce and expand

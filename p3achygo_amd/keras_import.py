@@ -102,9 +102,10 @@ def config_from_arguments(args: dict) -> netspec.NetConfig:
                 bottleneck_channels=int(args["num_bottleneck_channels"]), head_channels=int(args["num_head_channels"]),
                 c_val=int(args["c_val"]), broadcast_interval=int(args["broadcast_interval"]), inner_layers=inner,
                 block_type=block_type)
-    for cfg in netspec.CONFIGS.values():
-        if all(getattr(cfg, k) == v for k, v in want.items()):
-            return cfg
+    for table in (netspec.CONFIGS, netspec.WIDE_CONV_CONFIGS):
+        for cfg in table.values():
+            if all(getattr(cfg, k) == v for k, v in want.items()):
+                return cfg
     return netspec.NetConfig(name=str(args.get("name", "imported")), **want)
 
 
@@ -154,6 +155,11 @@ def import_checkpoint(src: str, dst: str, config_name: Optional[str] = None) -> 
         cfg = config_from_arguments(args)
     tensors, unused = convert(datasets, cfg)
     netspec.save_p3w(dst, cfg, tensors)
+    if cfg.block_type != "transformer" and not netspec.conv_supported(cfg):
+        # converted all the same (the CPU oracle runs any shape); one line says that the HIP engine will not
+        print(f"{dst}: note: the HIP engine will not run this conv trunk (C = {cfg.channels}, C_b = "
+              f"{cfg.bottleneck_channels}, H = {cfg.head_channels}, V = {cfg.c_val}, {cfg.block_type}); it runs "
+              f"{netspec.CONV_SET}, with H = 32 and V in {{32, 48, 64, 80}}", file=sys.stderr)
     return cfg, unused
 
 

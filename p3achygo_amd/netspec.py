@@ -143,9 +143,50 @@ WIDE_TRANSFORMER_CONFIGS: Dict[str, NetConfig] = {
 }
 
 
+# The conv trunks the engine runs (include/p3hip.h P3HIP_CONV_SET, same wording), with H = 32 and V in {32, 48, 64, 80}.
+CONV_SET = ("conv: C a multiple of 32 with 64 <= C <= 512; btl (1-3 inner layers) and nbt blocks with C_b a multiple of 16, "
+            "32 <= C_b <= C; classic blocks of two 3x3 convs (C_b ignored); broadcast blocks at any interval >= 2")
+
+
+def conv_supported(cfg: NetConfig) -> bool:
+    """True where the HIP engine runs the conv trunk `cfg` (CONV_SET, H = 32, V in {32, 48, 64, 80})."""
+    C, Cb = cfg.channels, cfg.bottleneck_channels
+    if cfg.block_type not in ("btl", "nbt", "classic") or cfg.head_channels != 32 or cfg.c_val not in (32, 48, 64, 80):
+        return False
+    if C % 32 != 0 or not 64 <= C <= 512 or cfg.broadcast_interval < 2:
+        return False
+    if cfg.block_type == "classic":
+        return cfg.inner_layers == 2
+    if cfg.block_type == "btl" and not 1 <= cfg.inner_layers <= 3:
+        return False
+    return Cb % 16 == 0 and 32 <= Cb <= C
+
+
+# Not in the reference's table (its ModelConfig constructor takes any channels / bottleneck_channels): conv nets of
+# widths the fused and the templated layer-wise kernels do not serve, for tests and measurements.  They run layer-wise
+# through csrc/conv_any.hip, C and C_b padded to multiples of 64.  Kept apart from CONFIGS, whose entries the
+# conftest's weight_files fixture generates.
+WIDE_CONV_CONFIGS: Dict[str, NetConfig] = {
+    c.name: c
+    for c in [
+        NetConfig("test_b3c64btl2", 3, 64, 32, 32, 32, 3, 2, "btl"),           # the narrow end; C_b padded 32 -> 64
+        NetConfig("test_b3c96nbt", 3, 96, 48, 32, 48, 3, 2, "nbt"),            # both padded (128, 64)
+        NetConfig("test_b3c192btl3", 3, 192, 96, 32, 48, 3, 3, "btl"),         # C_b padded 96 -> 128
+        NetConfig("test_b3c256btl2_cb64", 3, 256, 64, 32, 64, 3, 2, "btl"),    # C_b < C / 2, nothing padded
+        NetConfig("test_b3c128classic", 3, 128, 64, 32, 64, 3, 2, "classic"),
+        NetConfig("test_b3c320nbt", 3, 320, 160, 32, 80, 3, 2, "nbt"),         # C_b padded 160 -> 192
+        NetConfig("test_b3c512nbt", 3, 512, 256, 32, 80, 3, 2, "nbt"),         # the wide end
+        NetConfig("test_b4c512btl3_i2", 4, 512, 128, 32, 64, 2, 3, "btl"),     # broadcast blocks 1 and 3
+        NetConfig("b12c192btl3", 12, 192, 96, 32, 64, 5, 3, "btl"),
+        NetConfig("b10c512nbt", 10, 512, 256, 32, 80, 4, 2, "nbt"),
+        NetConfig("b14c320btl3", 14, 320, 160, 32, 80, 6, 3, "btl"),           # tools/gpu_conv_widths_bench.py
+    ]
+}
+
+
 def get_config(name: str) -> NetConfig:
-    """A config of CONFIGS, TRANSFORMER_CONFIGS or WIDE_TRANSFORMER_CONFIGS by name."""
-    for table in (CONFIGS, TRANSFORMER_CONFIGS, WIDE_TRANSFORMER_CONFIGS):
+    """A config of CONFIGS, TRANSFORMER_CONFIGS, WIDE_TRANSFORMER_CONFIGS or WIDE_CONV_CONFIGS by name."""
+    for table in (CONFIGS, TRANSFORMER_CONFIGS, WIDE_TRANSFORMER_CONFIGS, WIDE_CONV_CONFIGS):
         if name in table:
             return table[name]
     raise KeyError(name)
