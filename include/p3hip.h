@@ -112,6 +112,12 @@ typedef struct p3hip_engine p3hip_engine;
                                        activations stay in LDS ("Fused INT8 blocks"); p3hip_int8_* as
                                        for P3HIP_FLAG_INT8, (inner layers + 2) quantized tensors per btl block.
                                        p3hip_create returns NULL for any other trunk and for both INT8 flags together */
+#define P3HIP_FLAG_INT8_C128 128u   /* the same plan for the C = 128 / C_b = 64 trunks of btl blocks with 1, 2 or 3 inner
+                                       layers (b12c128btl3, b10c128btl3, small), broadcast blocks at any interval: every
+                                       btl block is one launch of k_block_i8<128,64>, two workgroups per CU (DESIGN.md
+                                       section 9, "Fused INT8 blocks at C = 128"); p3hip_int8_* as for
+                                       P3HIP_FLAG_INT8_FUSED.  p3hip_create returns NULL for any other trunk (nbt, other
+                                       widths, classic, transformers) and for any two of the three INT8 flags together */
 #define P3HIP_FLAG_SYMMETRY_AVG 32u /* every slot a run evaluates is evaluated under each symmetry of the engine's set
                                        (default: all eight) and the results averaged on the device, rotated back into the
                                        orientation the slot was loaded in.  Needs 8 x batch_size <= 65536.  See
@@ -188,8 +194,8 @@ int p3hip_load_slot_keyed(p3hip_engine* e, int slot, const p3hip_features* f, ui
 int p3hip_get_slot_keyed(p3hip_engine* e, int slot, p3hip_result* out, int* symmetry, int* from_cache);
 int p3hip_cache_stats(const p3hip_engine* e, uint64_t out[4]);
 
-/* ---- calibrated INT8 (P3HIP_FLAG_INT8, P3HIP_FLAG_INT8_FUSED) ---------------------------------------------
- * The quantized tensors are the inputs of every conv of the layer-wise blocks (INT8_FUSED: of the btl blocks), numbered
+/* ---- calibrated INT8 (P3HIP_FLAG_INT8, P3HIP_FLAG_INT8_FUSED, P3HIP_FLAG_INT8_C128) ------------------------
+ * The quantized tensors are the inputs of every conv of the layer-wise blocks (INT8_FUSED, INT8_C128: of the btl blocks), numbered
  * block by block, conv by conv (the order of the block's .p3w convs).  Each has one symmetric activation scale
  * s_a = max |v| / 127.
  *   p3hip_int8_calibrate   one p3hip_run on the fp16 plan (results fetched with p3hip_get_slot as usual) that also

@@ -1,5 +1,6 @@
-// block_i8.h — arguments and launcher of the fused INT8 block kernel of the C = 256 / C_b = 128 btl trunks
-// (block_i8.hip, P3HIP_FLAG_INT8_FUSED).  Numerics: DESIGN.md section 9 "Fused INT8 blocks".
+// block_i8.h — arguments and launchers of the fused INT8 block kernels: C = 256 / C_b = 128 btl trunks (block_i8.hip,
+// P3HIP_FLAG_INT8_FUSED) and C = 128 / C_b = 64 btl trunks (block_i8_c128.hip, P3HIP_FLAG_INT8_C128).
+// Numerics: DESIGN.md section 9 "Fused INT8 blocks".
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -8,12 +9,13 @@ namespace p3 {
 
 constexpr int kBlockI8MaxConvs = 5;   // reduce + up to three inner 3x3 + expand
 
-// One btl block with `inner` 3x3 layers on the stored fp16 x [npos][256 / 8][361][8], in place:
+// One btl block with `inner` 3x3 layers on the stored fp16 x [npos][C / 8][361][8], in place (C = 256, C_b = 128 or
+// C = 128, C_b = 64):
 //   a0 = q(mish(bn0(x)))                                  quantized with act_scale[q0]
 //   conv j = 0 .. inner:  a_{j+1} = q(mish(bn_{j+1}(acc * (act_scale[q0 + j] * w_scale[j][c]))))   with act_scale[q0 + j + 1]
 //   x <- fp16((float) x + acc * (act_scale[q0 + inner + 1] * w_scale[inner + 1][c]))
-// w[j]: the conv's weights in pack_lconv_i8 order (lconv_i8.h); scale[0] / shift[0]: folded bn0 [256];
-// scale[j] / shift[j], j >= 1: folded bn_j [128].
+// w[j]: the conv's weights in pack_lconv_i8 order (lconv_i8.h); scale[0] / shift[0]: folded bn0 [C];
+// scale[j] / shift[j], j >= 1: folded bn_j [C_b].
 struct BlockI8Args {
   _Float16* x;
   int npos, inner;
@@ -27,5 +29,9 @@ struct BlockI8Args {
 
 hipError_t launch_block_i8(const BlockI8Args& a, int n_cu, hipStream_t s);
 const char* block_i8_kernel_name();
+
+// the same block at C = 128 / C_b = 64: 256-thread workgroups, two per CU
+hipError_t launch_block_i8_c128(const BlockI8Args& a, int n_cu, hipStream_t s);
+const char* block_i8_c128_kernel_name();
 
 }  // namespace p3

@@ -436,7 +436,9 @@ struct p3hip_engine {
   // the int8 kernels read at launch time, so that a replayed graph sees new scales.
   // P3HIP_FLAG_INT8_FUSED (section 9, "Fused INT8 blocks"): int8 is set as well; the C = 256 / C_b = 128 btl blocks are
   // planned layer by layer (the fp16 plan the calibration runs) and run as one k_block_i8 launch each (csrc/block_i8.hip)
-  bool int8 = false, i8f = false, calibrating = false, have_scales = false;
+  // P3HIP_FLAG_INT8_C128 (section 9, "Fused INT8 blocks at C = 128"): int8, i8f and i8c128 are set; the same plan on the
+  // C = 128 / C_b = 64 btl blocks (csrc/block_i8_c128.hip), calibrated through k_lconv_any
+  bool int8 = false, i8f = false, i8c128 = false, calibrating = false, have_scales = false;
   int n_q = 0;
   unsigned* d_amax = nullptr;
   float* d_ascale = nullptr;
@@ -558,9 +560,13 @@ bool build_plan(p3hip_engine* e, Arena& ar) {
   const bool classic = wf.btype == 2 && wf.inner == 2;                 // two 3x3 convs C -> C
   const bool classic192 = classic && exact && C == 192;                // b15c192_classic
   const bool bottleneck_ok = wf.btype == 1 || (wf.btype == 0 && wf.inner >= 1 && wf.inner <= 3);
-  // P3HIP_FLAG_INT8_FUSED: the btl trunks of the fused block kernel's C = 256 width, alone
-  const bool i8f_ok = i8f && !(e->flags & P3HIP_FLAG_INT8) && exact && C == 256 && Cb == 128 && wf.btype == 0 && wf.inner >= 1 &&
-                      wf.inner <= 3;
+  // P3HIP_FLAG_INT8_FUSED: the btl trunks of the fused block kernel's C = 256 width; P3HIP_FLAG_INT8_C128: those of its
+  // C = 128 width; each alone among the three INT8 flags
+  const bool i8c = e->i8c128;
+  const uint32_t i8_flags = e->flags & (P3HIP_FLAG_INT8 | P3HIP_FLAG_INT8_FUSED | P3HIP_FLAG_INT8_C128);
+  const bool i8_alone = (i8_flags & (i8_flags - 1)) == 0;
+  const bool i8f_ok = i8f && i8_alone && exact && (i8c ? (C == 128 && Cb == 64) : (C == 256 && Cb == 128)) && wf.btype == 0 &&
+                      wf.inner >= 1 && wf.inner <= 3;
   const bool fused_shape = exact && ((C == 256 && Cb == 128) || (C == 128 && Cb == 64)) && bottleneck_ok;
   const bool lw_shape = (exact && C == 384 && Cb == 192 && bottleneck_ok) || classic192;   // the templated k_lconv's shapes
   // every other conv trunk of P3HIP_CONV_SET: layer-wise through conv_any.hip, C and Cb padded to multiples of 64
@@ -583,10 +589,19 @@ bool build_plan(p3hip_engine* e, Arena& ar) {
              "d > 256))";
     return false;
   }
+  // (INT8_C128 answers every trunk it does not serve with its own message, the runtime-width conv trunks included)
+  if (i8c && !i8f_ok) {
+    e->err = "INT8_C128 is available only for C = 128 / C_b = 64 trunks of btl blocks with 1, 2 or 3 inner layers "
+             "(b12c128btl3, b10c128btl3, small and their kin, broadcast blocks at any interval), and not together with "
+             "another INT8 flag; nbt trunks, the other widths (P3HIP_FLAG_INT8_FUSED serves C = 256 / C_b = 128 btl trunks, "
+             "P3HIP_FLAG_INT8 the layer-wise trunks) and the transformer are not served";
+    return false;
+  }
   if (any && e->int8) {
-    e->err = std::string(e->i8f ? "INT8_FUSED" : "INT8") + " is not available for this conv trunk: P3HIP_FLAG_INT8 "
-             "serves C = 384 / C_b = 192 btl or nbt blocks and C = 192 classic blocks, P3HIP_FLAG_INT8_FUSED serves "
-             "C = 256 / C_b = 128 btl blocks with 1, 2 or 3 inner layers; the other widths run in fp16 only";
+    e->err = std::string(e->i8f ? "INT8_FUSED" : "INT8") + " is not available for this conv trunk: "
+             "P3HIP_FLAG_INT8 serves C = 384 / C_b = 192 btl or nbt blocks and C = 192 classic blocks, P3HIP_FLAG_INT8_FUSED "
+             "serves C = 256 / C_b = 128 btl blocks with 1, 2 or 3 inner layers, P3HIP_FLAG_INT8_C128 serves C = 128 / "
+             "C_b = 64 btl blocks with 1, 2 or 3 inner layers; the other widths run in fp16 only";
     return false;
   }
   e->conv_any = any || (e->conv_any_env && lw_shape && !e->int8);
@@ -607,7 +622,8 @@ bool build_plan(p3hip_engine* e, Arena& ar) {
     return false;
   }
   // slice width of the per-position kernels that stage C channels (k_conv1x1 family)
-  // (layer-wise: p3::conv_any_slice(C) = 64 at classic C = 192, 128 at C = 384 and at INT8_FUSED's C = 256)
+  // (layer-wise: p3::conv_any_slice(C) = 64 at classic C = 192 and at INT8_C128's C = 128, 128 at C = 384 and at
+  // INT8_FUSED's C = 256)
   const int CB = layerwise ? p3::conv_any_slice(C) : (tfm ? 128 : Cb);
   const int CPI = layerwise ? p3::conv_any_init_pass(C) : 128;   // output pass width of the init conv
   // init conv
@@ -1286,8 +1302,10 @@ bool enqueue_forward(p3hip_engine* e, const Pass& p) {
           const FoldedBN& bn = j == 0 ? lp.pre_bn : bp.layers[j - 1].out_bn;
           a.scale[j] = e->dev<float>(bn.scale_off); a.shift[j] = e->dev<float>(bn.shift_off);
         }
-        if (!timed_launch(e, p.timed, [&] { return e->check(p3::launch_block_i8(a, e->n_cu, s), "launch k_block_i8"); }))
-          return false;
+        auto launch = [&] {
+          return e->check(e->i8c128 ? p3::launch_block_i8_c128(a, e->n_cu, s) : p3::launch_block_i8(a, e->n_cu, s), "launch k_block_i8");
+        };
+        if (!timed_launch(e, p.timed, launch)) return false;
         continue;
       }
       if (e->int8 && !e->calibrating) {
@@ -1314,9 +1332,11 @@ bool enqueue_forward(p3hip_engine* e, const Pass& p) {
         p3::LConvArgs a{};
         fill(a, lp);
         a.wstream = e->d_arena + lp.stream_off; a.nms_total = lp.nms;
+        // (INT8_C128 calibrates through the runtime-width kernel: k_lconv has no C = 128 / C_b = 64 instantiations)
+        const bool lany = any || e->i8c128;
         auto launch = [&] {
-          return e->check(any ? p3::launch_lconv_any(lp.kw, lp.cin, lp.cout, a, e->n_cu, s)
-                              : p3::launch_lconv(lp.kw, lp.cin, lp.cout, a, e->n_cu, s), any ? "launch k_lconv_any" : "launch k_lconv");
+          return e->check(lany ? p3::launch_lconv_any(lp.kw, lp.cin, lp.cout, a, e->n_cu, s)
+                               : p3::launch_lconv(lp.kw, lp.cin, lp.cout, a, e->n_cu, s), lany ? "launch k_lconv_any" : "launch k_lconv");
         };
         if (!timed_launch(e, lp.kw == 3 ? p.timed : nullptr, launch)) return false;
       }
@@ -1515,8 +1535,9 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
   e->time_run = getenv("P3HIP_TIME_RUN") != nullptr;
   e->blockw_diag = getenv("P3HIP_BLOCKW_DIAG") != nullptr;
   e->conv_any_env = getenv("P3HIP_CONV_ANY") != nullptr && atoi(getenv("P3HIP_CONV_ANY")) != 0;
-  e->int8 = (flags & (P3HIP_FLAG_INT8 | P3HIP_FLAG_INT8_FUSED)) != 0;
-  e->i8f = (flags & P3HIP_FLAG_INT8_FUSED) != 0;
+  e->int8 = (flags & (P3HIP_FLAG_INT8 | P3HIP_FLAG_INT8_FUSED | P3HIP_FLAG_INT8_C128)) != 0;
+  e->i8f = (flags & (P3HIP_FLAG_INT8_FUSED | P3HIP_FLAG_INT8_C128)) != 0;
+  e->i8c128 = (flags & P3HIP_FLAG_INT8_C128) != 0;
   e->sym = sym;
   e->rows = sym ? p3::kNumSyms * batch_size : batch_size;
   auto fail = [&](const std::string& m) {
@@ -1965,7 +1986,7 @@ double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
   // The timed kernel (enqueue_forward records an event pair around each of its launches) and its launches per forward
   // pass: the attention kernel k_tfm_attn of transformer trunks, the fused block kernel, or else the 3x3 layer conv
   // k_lconv<3, ..> of layer-wise trunks (C = 384, classic)
-  // (P3HIP_FLAG_INT8_FUSED: k_block_i8, one launch per btl block)
+  // (P3HIP_FLAG_INT8_FUSED, P3HIP_FLAG_INT8_C128: k_block_i8, one launch per btl block)
   const int per_pass = e->tfm ? wf.nblocks : (bp ? nfused : (e->i8f ? nlw : n3x3));
   if (per_pass == 0) return -1.0;
   if (e->sym) {
@@ -2004,7 +2025,7 @@ double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
   } else if (e->i8f) {
     // every conv of one btl block, as for the fp16 block launch below
     flops = 2.0 * n_positions * kNLoc * (wf.inner * 9.0 * wf.Cb * wf.Cb + 2.0 * wf.C * wf.Cb);
-    name = p3::block_i8_kernel_name();
+    name = e->i8c128 ? p3::block_i8_c128_kernel_name() : p3::block_i8_kernel_name();
   } else if (!bp) {
     // (conv_any: the file's own width, not the padded one the kernel runs)
     const double w3 = e->conv_any ? (wf.btype == 2 ? wf.model_C : wf.model_Cb) : c3;

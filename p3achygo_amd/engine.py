@@ -39,6 +39,7 @@ FLAG_SHARED_DEVICE = 4
 FLAG_LAUNCH_GRAPH = 8
 FLAG_INT8 = 16   # calibrated INT8 convs in the layer-wise blocks (include/p3hip.h)
 FLAG_INT8_FUSED = 64   # calibrated INT8 of the C = 256 btl trunks, one fused int8 block kernel per block (section 9)
+FLAG_INT8_C128 = 128   # the same for the C = 128 / C_b = 64 btl trunks (b12c128btl3): k_block_i8<128,64>, two workgroups per CU
 FLAG_SYMMETRY_AVG = 32  # every slot averaged over a set of the eight symmetries on the device
 
 
@@ -188,23 +189,25 @@ class HipEngine:
         self._L.p3hip_cache_stats(self._h, out)
         return {"lookups": out[0], "hits": out[1], "stored": out[2], "entries": out[3]}
 
-    # -- calibrated INT8 (FLAG_INT8) -----------------------------------------------------
+    # -- calibrated INT8 (FLAG_INT8, FLAG_INT8_FUSED, FLAG_INT8_C128) --------------------
     def int8_calibrate(self) -> None:
         """RunInference on the fp16 plan that also folds every quantized tensor's max |v| into the engine's running
-        maxima (MinMax calibration): load a calibration batch, call this, fetch results as usual if wanted."""
+        maxima (MinMax calibration): load a calibration batch, call this, fetch results as usual if wanted.  Any of
+        FLAG_INT8, FLAG_INT8_FUSED and FLAG_INT8_C128."""
         self._ck(self._L.p3hip_int8_calibrate(self._h), "int8_calibrate")
 
     def int8_scales(self) -> np.ndarray:
-        """The activation scales s_a = max / 127, block by block, conv by conv (the calibration cache)."""
+        """The activation scales s_a = max / 127, block by block, conv by conv (the calibration cache); with
+        FLAG_INT8_FUSED or FLAG_INT8_C128 (inner layers + 2) per btl block."""
         n = self._L.p3hip_int8_scales(self._h, None, 0)
         if n < 0:
-            raise EngineError("int8_scales: the engine was not created with FLAG_INT8")
+            raise EngineError("int8_scales: the engine was not created with FLAG_INT8, FLAG_INT8_FUSED or FLAG_INT8_C128")
         out = np.zeros(n, np.float32)
         self._L.p3hip_int8_scales(self._h, out.ctypes.data, n)
         return out
 
     def set_int8_scales(self, scales) -> None:
-        """Loads a saved calibration (what int8_scales returned)."""
+        """Loads a saved calibration (what int8_scales returned by an engine of the same INT8 flag and net)."""
         s = np.ascontiguousarray(scales, np.float32)
         self._ck(self._L.p3hip_int8_set_scales(self._h, s.ctypes.data, len(s)), "set_int8_scales")
 

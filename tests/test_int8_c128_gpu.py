@@ -1,0 +1,357 @@
+"""Fused INT8 blocks of the C = 128 / C_b = 64 btl trunks on the MI355X (P3HIP_FLAG_INT8_C128, DESIGN.md section 9
+"Fused INT8 blocks at C = 128", csrc/block_i8_c128.hip).
+
+Every engine here is calibrated on tests/int8_restatement.calibration_batches() (or loads the scales of one that was).
+Accuracy is judged against the float64 goldens within int8_block_c128.BOUNDS, and block by block, teacher-forced,
+against the CPU emulation of the same scheme (tests/int8_block_c128.py) run from the engine's own x.
+
+Measured on one MI355X (mean |d x| to the INT8 emulation over mean |d x| to the unquantized fp16 block, per btl block,
+bound 0.5): b12c128btl3 at batch 300, btl blocks 0, 1, 2, 3, 5, 6, 7, 8, 10, 11: 0.000, 0.000, 0.001, 0.000, 0.000, 0.000,
+0.010, 0.000, 0.000, 0.010 (mean |d| to the emulation 1.0e-9 ... 1.7e-5 against 1.3e-3 ... 2.4e-3 to the fp16 block);
+test_b5c128btl1_i2 at batch 37 (blocks 0, 2, 4) and test_b3c128btl2 at batch 1 (blocks 0, 1): 0.000 on every block.
+Goldens on b12c128btl3 at batches 513 and 1024: 0.044 / 2.3e-4 / 1.7e-3 (logits / move probabilities / value
+probabilities).  See DESIGN.md section 9 "Fused INT8 blocks at C = 128"."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from conftest import ROOT, load_golden  # noqa: E402
+import int8_block_c128 as bc  # noqa: E402
+import trunk_emulation as te  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+# 1: a single workgroup; 7: fewer workgroups than CUs; 513: one more position than two workgroups on each of 256 CUs,
+# so the persistent loop wraps with a tail; 1024: two full turns
+BATCHES = (1, 7, 513, 1024)
+BLOCK_JOBS = [("test_b3c128btl2", 1), ("test_b5c128btl1_i2", 37), ("b12c128btl3", 300)]
+RATIO_BOUND = 0.5
+
+
+def _flag():
+    from p3achygo_amd import engine
+    return engine.FLAG_INT8_C128
+
+
+def _calibrated(path, batch, flags=0):
+    from p3achygo_amd import engine
+    eng = engine.HipEngine(path, batch, flags=_flag() | flags)
+    for cal in bc.calibration_batches():
+        assert len(cal) <= batch
+        eng.load_all(cal)
+        eng.int8_calibrate()
+        for i in range(len(cal)):
+            eng.GetBatch(i)
+    return eng
+
+
+_SCALES = {}
+
+
+def _scales(path):
+    """The calibrated scales of the net at `path` (one calibration per file and session)."""
+    if path not in _SCALES:
+        eng = _calibrated(path, 16)
+        _SCALES[path] = eng.int8_scales()
+        eng.close()
+    return _SCALES[path]
+
+
+def _with_scales(path, batch, flags=0):
+    from p3achygo_amd import engine
+    eng = engine.HipEngine(path, batch, flags=_flag() | flags)
+    eng.set_int8_scales(_scales(path))
+    return eng
+
+
+def _fetch(eng, slots):
+    raw = np.stack([eng.get_raw(s) for s in slots])
+    res = [eng.GetBatch(s) for s in slots]
+    return {"raw": raw.astype(np.float64),
+            "move_probs": np.stack([np.ctypeslib.as_array(r.move_probs) for r in res]).astype(np.float64),
+            "value_probs": np.stack([np.ctypeslib.as_array(r.value_probs) for r in res]).astype(np.float64)}
+
+
+def _run(eng, pos, slots=None):
+    """outputs of `pos` loaded at `slots` (default 0..n-1) as arrays like the goldens"""
+    slots = list(range(len(pos))) if slots is None else slots
+    for k, s in enumerate(slots):
+        eng.LoadBatch(s, pos[k:k + 1])
+    eng.RunInference()
+    return _fetch(eng, slots)
+
+
+def _weights(name):
+    from p3achygo_amd import netspec
+    cfg = netspec.CONFIGS[name]
+    return cfg, netspec.generate_weights(cfg, randomize=True)
+
+
+@pytest.mark.parametrize("name", bc.SERVED)
+def test_engine_matches_the_goldens_within_the_emulation_bounds_at_every_batch(built, weight_files, name):
+    """Batches of 1, 7, 513 and 1024: the fixture's positions repeated to fill the batch; every copy within BOUNDS of the
+    golden (so inside three times the emulation's own error) and bit-identical to the first copy."""
+    g, pos = load_golden(name)
+    path = weight_files(name)
+    for batch in BATCHES:
+        eng = _with_scales(path, batch)
+        idx = np.arange(batch) % len(pos)
+        eng.load_all(pos[idx])
+        eng.RunInference()
+        got = _fetch(eng, range(batch))
+        eng.close()
+        n = min(batch, len(pos))
+        err = bc.errors({k: v[:n] for k, v in got.items()}, {k: np.asarray(g[k])[:n] for k in got})
+        print(f"{name} batch {batch}: {err}")
+        for k, bound in bc.BOUNDS[name].items():
+            assert err[k] <= bound, (name, batch, err)
+        for k in got:
+            assert np.array_equal(got[k], got[k][idx]), (name, batch, k)   # copies of a position: bit-identical
+
+
+_CHILD = r"""
+import os, sys
+sys.path.insert(0, %r)
+import numpy as np
+from p3achygo_amd import engine, features
+d = np.load(sys.argv[1], allow_pickle=True)
+out = {}
+for key in d["keys"]:
+    path, C, nblk, slots = d[key + ":path"].item(), int(d[key + ":C"]), int(d[key + ":blocks"]), d[key + ":slots"]
+    pos = np.frombuffer(d[key + ":pos"].tobytes(), dtype=features.features_dtype()).copy()
+    cal = np.frombuffer(d["cal"].tobytes(), dtype=features.features_dtype()).copy().reshape(int(d["ncal"]), -1)
+    os.environ.pop("P3HIP_DEBUG_STOP_BLOCK", None)
+    eng = engine.HipEngine(path, 16, flags=engine.FLAG_INT8_C128)
+    for c in cal:
+        eng.load_all(c)
+        eng.int8_calibrate()
+    scales = eng.int8_scales()
+    eng.close()
+    out[key + ":scales"] = scales
+    for stop in range(nblk + 1):
+        if stop < nblk:
+            os.environ["P3HIP_DEBUG_STOP_BLOCK"] = str(stop)
+        else:
+            os.environ.pop("P3HIP_DEBUG_STOP_BLOCK", None)
+        eng = engine.HipEngine(path, len(pos), flags=engine.FLAG_INT8_C128)
+        eng.set_int8_scales(scales)
+        eng.load_all(pos)
+        eng.RunInference()
+        out[f"{key}:x{stop}"] = eng.debug_x(len(pos), C)[slots]
+        if stop == nblk:
+            out[f"{key}:raw"] = np.stack([eng.get_raw(int(s)) for s in slots])
+        eng.close()
+np.savez(sys.argv[2], **out)
+"""
+
+
+def _job_batch(name, batch):
+    """Positions of a job: the fixture's first positions scattered among seeded fill; the compared slots."""
+    from p3achygo_amd import features
+    _, gpos = load_golden(name)
+    special = gpos[:min(4, batch)]
+    pos = features.random_positions(batch, seed=43, n_games=16, max_moves=300, komis=(7.5, -7.5, 0.5))
+    at = [int(s) for s in np.linspace(0, batch - 1, len(special)).round()] if batch > 1 else [0]
+    pos[at] = special[:len(at)]
+    slots = sorted(set(at) | set(range(5, batch, 97)) | {batch - 1})
+    return pos, np.asarray(slots)
+
+
+@pytest.mark.parametrize("name,batch", BLOCK_JOBS)
+def test_blocks_teacher_forced(built, tmp_path, name, batch):
+    """One child process per configuration under its own time limit, nothing retried.  The engine's x after block k
+    against the emulation of block k from the engine's x after block k - 1 with the engine's scales: for a btl block
+    mean |d| to the INT8 emulation at most 0.5 of mean |d| to the unquantized fp16 block; the stem, the broadcast blocks
+    and the heads (the fp16 engine's kernels) by trunk_emulation's bounds."""
+    import torch
+    from p3achygo_amd import netspec
+    cfg, W = _weights(name)
+    path = str(tmp_path / (name + ".p3w"))
+    netspec.save_p3w(path, cfg, W)
+    pos, slots = _job_batch(name, batch)
+    cal = np.stack(bc.calibration_batches())
+    spec = {"keys": np.array([name]), name + ":path": np.array(path), name + ":C": np.array(cfg.channels),
+            name + ":blocks": np.array(cfg.blocks), name + ":slots": slots,
+            name + ":pos": np.frombuffer(pos.tobytes(), np.uint8), "cal": np.frombuffer(cal.tobytes(), np.uint8),
+            "ncal": np.array(len(cal))}
+    inp, outp = tmp_path / "in.npz", tmp_path / "out.npz"
+    np.savez(inp, **spec)
+    env = dict(os.environ)
+    for k in ("P3HIP_NO_FUSE", "P3HIP_NO_BFUSE", "P3HIP_DEBUG_STOP_BLOCK"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, "-c", _CHILD % ROOT, str(inp), str(outp)], env=env, capture_output=True,
+                       text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = np.load(outp)
+    scales = out[name + ":scales"]
+    assert len(scales) == len(bc.quantized_tensors(cfg))
+    xs = [out[f"{name}:x{s}"].astype(np.float64).reshape(len(slots), cfg.channels, 19, 19) for s in range(cfg.blocks + 1)]
+    emu = te.Trunk(cfg, W)
+    x0 = emu.stem(pos[slots])
+    te.check_block(xs[0], x0, te.rms(x0), f"{name} stem", slots, *te.bounds(cfg, "stem"))
+    worst = 0.0
+    for k in range(cfg.blocks):
+        if cfg.block_kind(k) == "broadcast":
+            m = emu.block(k, torch.from_numpy(xs[k]))
+            te.check_block(xs[k + 1], m, te.block_scale(xs[k], m), f"{name} block {k} (broadcast)", slots,
+                           *te.bounds(cfg, k))
+            continue
+        q = bc.block(cfg, W, k, xs[k], bc.block_scales(cfg, scales, k))
+        f = bc.block(cfg, W, k, xs[k], None)
+        d_q, d_f = float(np.abs(xs[k + 1] - q).mean()), float(np.abs(xs[k + 1] - f).mean())
+        print(f"{name} batch {batch} block {k}: mean |d| to the INT8 emulation {d_q:.3e}, to the fp16 block {d_f:.3e}, "
+              f"ratio {d_q / d_f:.3f}")
+        worst = max(worst, d_q / d_f)
+        assert np.isfinite(xs[k + 1]).all()
+        assert d_q <= RATIO_BOUND * d_f, (name, k, d_q, d_f)
+    want = emu.heads(torch.from_numpy(xs[-1]))
+    d = np.abs(out[f"{name}:raw"] - want)
+    assert d.max() <= te.HEADS_TOL, (name, float(d.max()))
+    print(f"{name}: worst btl ratio {worst:.3f}, heads max |d| {d.max():.2e}")
+
+
+def test_calibration_repeats_and_saved_scales_reproduce_the_results(built, weight_files):
+    """Repeated calibration: bit-identical scales, one per quantized tensor.  set_int8_scales(int8_scales()) on a fresh
+    engine: the same output bits.  A run before any scales fails with a message."""
+    from p3achygo_amd import engine, features, netspec
+    name = "test_b5c128btl1_i2"
+    path = weight_files(name)
+    pos = features.random_positions(24, seed=31)
+    a = _calibrated(path, 32)
+    sa = a.int8_scales()
+    want = _run(a, pos)["raw"]
+    a.close()
+    b = _calibrated(path, 32)
+    sb = b.int8_scales()
+    b.close()
+    assert np.array_equal(sa, sb) and (sa > 0).all()
+    assert len(sa) == len(bc.quantized_tensors(netspec.CONFIGS[name]))
+    c = engine.HipEngine(path, 32, flags=_flag())
+    assert len(c.int8_scales()) == len(sa)
+    c.LoadBatch(0, pos[:1])
+    with pytest.raises(engine.EngineError, match="no activation scales"):
+        c.RunInference()
+    c.set_int8_scales(sa)
+    assert np.array_equal(c.int8_scales(), sa)
+    assert np.array_equal(_run(c, pos)["raw"], want)
+    with pytest.raises(engine.EngineError, match="quantized tensors"):
+        c.set_int8_scales(sa[:-1])
+    c.close()
+
+
+def test_calibrated_scales_match_the_emulation(built, weight_files):
+    from oracle import oracle
+    name = "test_b3c128btl2"
+    path = weight_files(name)
+    cfg, W = _weights(name)
+    net = oracle.OracleNet(path)
+    want = bc.minmax_scales(cfg, W, [net.fill_inputs(c) for c in bc.calibration_batches()])
+    got = _scales(path)
+    assert len(got) == len(want)
+    # the engine calibrates on its fp16 plan: equal within a few fp16 roundings of the maxima
+    np.testing.assert_allclose(got, want, rtol=4e-3, atol=0)
+
+
+def test_a_position_alone_or_in_a_full_batch_of_1024(built, weight_files):
+    """The same bits whether the position runs alone (one workgroup) or anywhere in 1024 (two turns of the persistent
+    loop)."""
+    from p3achygo_amd import features
+    path = weight_files("b12c128btl3")
+    pos = features.random_positions(1024, seed=5, n_games=64)
+    full = _with_scales(path, 1024)
+    full.load_all(pos)
+    full.RunInference()
+    at = [0, 1, 511, 512, 513, 1023]
+    want = np.stack([full.get_raw(s) for s in at])
+    full.close()
+    one = _with_scales(path, 1)
+    for k, s in enumerate(at):
+        assert np.array_equal(_run(one, pos[s:s + 1])["raw"][0], want[k].astype(np.float64)), s
+    one.close()
+
+
+def test_launch_graph_replays_bit_for_bit_and_sees_new_scales(built, weight_files):
+    from p3achygo_amd import engine, features
+    path = weight_files("test_b5c128btl1_i2")
+    B = 32
+    pos = features.random_positions(B, seed=8)
+    ref = _with_scales(path, B)
+    gr = _with_scales(path, B, engine.FLAG_LAUNCH_GRAPH)
+    s = ref.int8_scales()
+    want = _run(ref, pos)["raw"]
+    for rnd in range(4):                       # eager, capture, replay, replay
+        assert np.array_equal(_run(gr, pos)["raw"], want), rnd
+    assert gr.graph_state() == 1
+    s2 = (s * np.float32(1.25)).astype(np.float32)
+    ref.set_int8_scales(s2)
+    gr.set_int8_scales(s2)
+    want2 = _run(ref, pos)["raw"]
+    assert not np.array_equal(want2, want)
+    assert np.array_equal(_run(gr, pos)["raw"], want2) and gr.graph_state() == 1
+    ref.close()
+    gr.close()
+
+
+def test_compaction_and_run_all_slots_equal_the_plain_engine(built, weight_files):
+    from p3achygo_amd import engine, features
+    path = weight_files("test_b5c128btl1_i2")
+    pos = features.random_positions(20, seed=17)
+    plain = _with_scales(path, 20)
+    want = _run(plain, pos)["raw"]
+    plain.close()
+    slots = list(range(2, 62, 3))              # 20 of 64 slots: compacted to a dense batch of 20
+    comp = _with_scales(path, 64)
+    assert np.array_equal(_run(comp, pos, slots)["raw"], want)
+    comp.close()
+    allslots = _with_scales(path, 64, engine.FLAG_RUN_ALL_SLOTS)
+    assert np.array_equal(_run(allslots, pos, slots)["raw"], want)
+    allslots.close()
+
+
+def test_with_the_nn_cache(built, weight_files):
+    """Cache hits are bit-identical to the INT8_C128 evaluation."""
+    from p3achygo_amd import features
+    path = weight_files("test_b3c128btl2")
+    pos = features.random_positions(16, seed=12)
+    ref = _with_scales(path, 16)
+    want = _run(ref, pos)["raw"]
+    ref.close()
+    eng = _with_scales(path, 16)
+    eng.EnableCache(8)
+    key = lambda i: (1000 + i, 77)
+    for rnd in range(2):
+        for i in range(16):
+            eng.LoadBatchKeyed(i, pos[i:i + 1], *key(i))
+        eng.RunInference()
+        for i in range(16):
+            if rnd == 0:
+                assert np.array_equal(eng.get_raw(i), want[i])
+            r, _, hit = eng.GetBatchKeyed(i)
+            assert hit == (rnd == 1)
+            assert np.array_equal(np.ctypeslib.as_array(r.move_logits), want[i][:362].astype(np.float32))
+    eng.close()
+
+
+def test_symmetry_averaging_follows_the_rule_bit_for_bit(built, weight_files):
+    """All eight symmetries (and one, and two): tests/symavg_restatement.py applied to the engine's eight
+    single-symmetry results."""
+    from p3achygo_amd import engine, features
+    from test_symmetry_avg_gpu import _check_rule
+    path = weight_files("test_b3c128btl2")
+    _check_rule(path, features.random_positions(19, seed=44), engine.symmetry_maps()[0], masks=(0x01, 0x81, 0xFF),
+                flags=_flag(), scales=_scales(path))
+
+
+def test_trunk_kernel_timing_names_the_block_kernel(built, weight_files):
+    from p3achygo_amd import features
+    eng = _with_scales(weight_files("b12c128btl3"), 16)
+    eng.load_all(features.random_positions(16, seed=3))
+    eng.upload()
+    ms, flops, kname = eng.time_trunk_kernel(16, 2)
+    eng.close()
+    assert kname == "k_block_i8<128,64>" and ms > 0
+    assert flops == 2.0 * 16 * 361 * (3 * 9 * 64 * 64 + 2 * 128 * 64)

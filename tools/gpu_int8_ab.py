@@ -1,15 +1,18 @@
 """fp16 against calibrated INT8, interleaved A/B on one MI355X: the layer-wise trunks (P3HIP_FLAG_INT8, the default)
-or, with --flag int8_fused, the C = 256 btl trunks (P3HIP_FLAG_INT8_FUSED; default net b12c256btl3).
+or, with --flag int8_fused, the C = 256 btl trunks (P3HIP_FLAG_INT8_FUSED; default net b12c256btl3), or, with
+--flag int8_c128, the C = 128 btl trunks (P3HIP_FLAG_INT8_C128; default net b12c128btl3).
 
 For each trunk and batch size, the two engines are built from the same seeded .p3w; the INT8 engine is calibrated on
 tests/int8_restatement.calibration_batches().  Legs alternate fp16, int8, fp16, int8, ...; each leg times
 `--steps` device-resident forward passes (engine only: no H2D / D2H) with the chip's clock, power and limiter residency
 sampled beside it (p3achygo_amd/power_sampler.py, as bench.py does), then the trunk kernel alone
-(p3hip_time_trunk_kernel: the 3x3 layer conv, keys k3x3_*; with --flag int8_fused the block launch, keys block_*).
+(p3hip_time_trunk_kernel: the 3x3 layer conv, keys k3x3_*; with --flag int8_fused or int8_c128 the block launch, keys
+block_*).
 Prints one JSON line per leg and a summary per (trunk, batch); --out writes them all.
 
   python tools/gpu_int8_ab.py --nets b14c384btl3 b10c384nbt b15c192_classic --batches 1024 256 --rounds 3
   python tools/gpu_int8_ab.py --flag int8_fused --batches 1024 256 --rounds 3 --out profiles/int8_fused_ab.jsonl
+  python tools/gpu_int8_ab.py --flag int8_c128 --batches 1024 256 --rounds 3 --out profiles/int8_c128_ab.jsonl
 """
 import argparse
 import json
@@ -50,7 +53,7 @@ def leg(eng, batch, steps, kernel_iters, k="k3x3"):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--flag", choices=["int8", "int8_fused"], default="int8")
+    ap.add_argument("--flag", choices=["int8", "int8_fused", "int8_c128"], default="int8")
     ap.add_argument("--nets", nargs="+", default=None)
     ap.add_argument("--batches", nargs="+", type=int, default=[1024, 256])
     ap.add_argument("--rounds", type=int, default=3)
@@ -60,9 +63,12 @@ def main():
     args = ap.parse_args()
     import int8_restatement as ir
     from p3achygo_amd import engine, features, netspec
-    fused = args.flag == "int8_fused"
-    nets = args.nets or (["b12c256btl3"] if fused else ["b14c384btl3", "b10c384nbt", "b15c192_classic"])
-    flag, k = (engine.FLAG_INT8_FUSED, "block") if fused else (engine.FLAG_INT8, "k3x3")
+    fused = args.flag in ("int8_fused", "int8_c128")   # one int8 block launch per btl block
+    default_nets = {"int8": ["b14c384btl3", "b10c384nbt", "b15c192_classic"], "int8_fused": ["b12c256btl3"],
+                    "int8_c128": ["b12c128btl3"]}
+    nets = args.nets or default_nets[args.flag]
+    flag = {"int8": engine.FLAG_INT8, "int8_fused": engine.FLAG_INT8_FUSED, "int8_c128": engine.FLAG_INT8_C128}[args.flag]
+    k = "block" if fused else "k3x3"
     lines = []
     with tempfile.TemporaryDirectory() as d:
         for name in nets:
