@@ -123,6 +123,15 @@ typedef struct p3hip_engine p3hip_engine;
                                        orientation the slot was loaded in.  Needs 8 x batch_size <= 65536.  See
                                        p3hip_set_symmetries below */
 
+#define P3HIP_FLAG_FP32 256u        /* full-precision inference of the conv trunks: every trunk of P3HIP_CONV_SET runs layer by
+                                       layer in fp32 from the stem to the heads (csrc/conv_f32.hip).
+                                       Weights are packed as fp32, the three head convs included, activations are stored as
+                                       fp32, BN fold, mish and residual adds run in fp32, and every product accumulates on
+                                       the f32-input MFMA (v_mfma_f32_32x32x2_f32, bit-equal to an fmaf chain): no fp16 value
+                                       exists in the pass.  The activation buffers are twice the fp16 plan's.  The other
+                                       flags, the NN cache and compaction work as on any engine.  p3hip_create returns NULL
+                                       for a transformer trunk and together with any of the three INT8 flags */
+
 /* Transformer trunks (python/model_transformer.py TransformerBlock, a generic_arch of "transformer" blocks) the engine
  * runs: every block has the same embed_dim d and num_heads h, d equals the stem's channels, d is a multiple of 32 with
  * 64 <= d <= 384, the head width d / h is 32 or 64; any block count the .p3w header allows; H = 32 and V what the heads
@@ -134,7 +143,7 @@ typedef struct p3hip_engine p3hip_engine;
 
 /* Conv trunks the engine runs.  (C, C_b) = (128, 64) and (256, 128) run the fused block kernels, (384, 192) and classic
  * C = 192 the templated layer-wise kernels; every other shape of the set runs layer-wise through kernels that take the
- * widths as launch arguments (csrc/conv_any.hip), in fp16 only.  There a file's C and C_b are zero-padded to the next
+ * widths as launch arguments (csrc/conv_any.hip), in fp16 or fp32 (P3HIP_FLAG_FP32, csrc/conv_f32.hip).  There a file's C and C_b are zero-padded to the next
  * multiple of 64 when the weights are packed (padded channels are exactly 0 everywhere); p3hip_flops_per_position
  * counts the file's own widths, p3hip_debug_x returns the padded stream.  P3HIP_CONV_ANY=1 in the environment at
  * p3hip_create sends (384, 192) and classic C = 192 through those kernels too, with bit-identical results.
@@ -246,7 +255,8 @@ int p3hip_get_raw(p3hip_engine* e, int slot, float* out);
  * algorithmic FLOPs of the convs one launch executes (inner 3x3s + 1x1 reduce/expand,
  * unpadded 361 points).  Transformer trunks: times the attention kernel k_tfm_attn and writes the FLOPs of its
  * q.k^T and p.v products over 361 x 361 tokens.  Layer-wise trunks: times the 3x3 layer conv, k_lconv<3,..>, or on an
- * INT8 engine k_lconv_i8<3,..>, and writes the FLOPs of one 3x3 conv. */
+ * INT8 engine k_lconv_i8<3,..>, and writes the FLOPs of one 3x3 conv.  A P3HIP_FLAG_FP32 engine is layer-wise whatever its
+ * trunk: it times k_lconv_f32<3> and writes the FLOPs of one 3x3 conv at the file's own widths. */
 double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
                                double* flops_per_launch, const char** kernel_name);
 /* P3HIP_FLAG_LAUNCH_GRAPH: 1 once the full-batch forward pass has been captured and is being replayed,
@@ -258,6 +268,7 @@ int p3hip_graph_state(const p3hip_engine* e);
 int p3hip_blockw_stamps(p3hip_engine* e, unsigned long long* out, int n);
 /* Debugging aid: the residual stream x after the last forward pass (stopped early by P3HIP_DEBUG_STOP_BLOCK in the
  * environment, if set), n_positions x C x 361 values in the device layout [pos][C / 8][361][8], as floats.
+ * A P3HIP_FLAG_FP32 engine returns its stored fp32 values, exactly, in the same order.
  * Transformer trunks: C is the stream's padded width (the model's d channels, then the channels up to 128, 256 or 384
  * that stay zero). */
 int p3hip_debug_x(p3hip_engine* e, float* out, int n_positions);

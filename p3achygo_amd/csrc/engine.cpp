@@ -29,6 +29,7 @@
 #include "kernels.h"
 #include "block_i8.h"
 #include "conv_any.h"
+#include "conv_f32.h"
 #include "lconv_i8.h"
 #include "slot_state.h"
 #include "symmetry.h"
@@ -350,6 +351,7 @@ struct LayerPlan {
   // this layer's input among the engine's quantized tensors (its output, when quantized, is the next one: its consumer)
   size_t q_off = 0, qs_off = 0;
   int qidx = -1;
+  size_t w32_off = 0;   // P3HIP_FLAG_FP32: the fp32 weight image (conv_f32.h pack_conv_f32)
 };
 
 // One transformer block (kind 5): arena offsets of its tensors, the GEMM weights as MFMA A fragments (transformer.h)
@@ -367,6 +369,7 @@ struct BlockPlan {
   size_t stream2_off = 0, stream3_off = 0;
   int nms2 = 0, nms3 = 0;
   size_t dense_bias_off = 0;
+  size_t w32_first = 0, w32_dense = 0, w32_last = 0;   // P3HIP_FLAG_FP32: conv_first, the dense, conv_last in fp32
   // Broadcast 1x1 convs taken into the neighbouring block launches (k_block's BC form).
   //   on a broadcast block: its conv_first runs at the tail of the launch before it / its conv_last
   //   at the head of the launch after it;
@@ -458,6 +461,11 @@ struct p3hip_engine {
   // P3HIP_CONV_SET that the templated kernels do not serve, and with P3HIP_CONV_ANY=1 in the environment at create the
   // templated layer-wise shapes too (C = 384 / C_b = 192 btl and nbt, classic C = 192), bit for bit the same results
   bool conv_any = false, conv_any_env = false;
+  // P3HIP_FLAG_FP32: every conv trunk layer by layer through the kernels of conv_f32.hip; weights and the activation
+  // buffers d_x, d_t, d_u are fp32 (the buffers keep their fp16 pointer types and are 4 bytes per element), the heads
+  // run k_heads on the hp the fp32 head convs write.  No fp16 value exists in the pass.
+  bool f32 = false;
+  size_t init_w32_off = 0, heads_w32_off = 0;
   bool heads_fused = false;   // k_headsx: the head convs inside the heads kernel (C <= 256; P3HIP_NO_HFUSE clears it)
   std::map<std::string, size_t> head_off;
 
@@ -554,9 +562,19 @@ bool build_plan(p3hip_engine* e, Arena& ar) {
   const WeightFile& wf = e->wf;
   const int C = wf.C, Cb = wf.Cb;
   const bool i8f = e->i8f;
+  const bool f32 = e->f32;
+  if (f32 && wf.btype == 3) {
+    e->err = "P3HIP_FLAG_FP32 serves the conv trunks only (" P3HIP_CONV_SET "); the transformer trunks run in fp16";
+    return false;
+  }
+  if (f32 && e->int8) {
+    e->err = "P3HIP_FLAG_FP32 cannot be combined with P3HIP_FLAG_INT8, P3HIP_FLAG_INT8_FUSED or P3HIP_FLAG_INT8_C128: an "
+             "engine runs one precision plan";
+    return false;
+  }
   // a conv file whose widths were padded (WeightFile::pad_conv) never takes the plan of the shape it was padded to
   const bool exact = wf.btype == 3 || (wf.model_C == C && wf.model_Cb == Cb);
-  const bool fused = !i8f && exact && ((C == 256 && Cb == 128) || (C == 128 && Cb == 64));
+  const bool fused = !i8f && !f32 && exact && ((C == 256 && Cb == 128) || (C == 128 && Cb == 64));
   const bool classic = wf.btype == 2 && wf.inner == 2;                 // two 3x3 convs C -> C
   const bool classic192 = classic && exact && C == 192;                // b15c192_classic
   const bool bottleneck_ok = wf.btype == 1 || (wf.btype == 0 && wf.inner >= 1 && wf.inner <= 3);
@@ -573,7 +591,8 @@ bool build_plan(p3hip_engine* e, Arena& ar) {
   const bool any = !fused_shape && !lw_shape &&
                    WeightFile::conv_set(wf.model_C, wf.model_Cb, wf.btype, wf.inner, wf.bint) && C % 64 == 0 &&
                    (wf.btype == 2 || Cb % 64 == 0);
-  const bool layerwise = lw_shape || i8f_ok || any;
+  // (P3HIP_FLAG_FP32 runs the fused shapes layer by layer too)
+  const bool layerwise = lw_shape || i8f_ok || any || (f32 && fused_shape);
   const bool v_ok = wf.V == 32 || wf.V == 48 || wf.V == 64 || wf.V == 80;
   // transformer trunk: the file's C is the model width d and Cb the head count (include/p3hip.h: d a multiple of 32,
   // 64 <= d <= 384, head width d / heads 32 or 64); the stream is padded to C = p3::tfm_stream_width(d), and V is what
@@ -604,7 +623,7 @@ bool build_plan(p3hip_engine* e, Arena& ar) {
              "C_b = 64 btl blocks with 1, 2 or 3 inner layers; the other widths run in fp16 only";
     return false;
   }
-  e->conv_any = any || (e->conv_any_env && lw_shape && !e->int8);
+  e->conv_any = !f32 && (any || (e->conv_any_env && lw_shape && !e->int8));
   e->tfm = tfm;
   if (tfm) {
     e->tfm_heads = Cb;
@@ -630,9 +649,15 @@ bool build_plan(p3hip_engine* e, Arena& ar) {
   {
     std::vector<_Float16> s;
     const Tensor& w = wf.get("init_conv.w", (size_t)25 * 15 * C);  // [5][5][15][C]
-    for (int cp = 0; cp < C / CPI; ++cp)
-      pack_segment(s, w.data, 25, 28, 15, C, 0, 16, cp * CPI, CPI);
-    e->init_stream_off = add_stream(ar, s, e->init_nms, CPI);
+    if (f32) {
+      std::vector<float> s32;
+      p3::pack_conv_f32(s32, w.data, 25, 15, C, 16, C);
+      e->init_w32_off = ar.add(s32.data(), s32.size() * 4);
+    } else {
+      for (int cp = 0; cp < C / CPI; ++cp)
+        pack_segment(s, w.data, 25, 28, 15, C, 0, 16, cp * CPI, CPI);
+      e->init_stream_off = add_stream(ar, s, e->init_nms, CPI);
+    }
     e->game_w_off = ar.add(wf.get("init_game.w", (size_t)8 * C).data, 8 * C * 4);
     e->game_b_off = ar.add(wf.get("init_game.b", (size_t)C).data, C * 4);
   }
@@ -732,6 +757,20 @@ bool build_plan(p3hip_engine* e, Arena& ar) {
       bp.bn[1] = fold_bn(ar, wf, p + ".bn1", C);
       const int CPb = (CB == 128) ? 128 : 64;
       std::vector<_Float16> s0, s1, s2;
+      if (f32) {
+        std::vector<float> w32;
+        p3::pack_conv_f32(w32, W(0, 1, C, C), 1, C, C, C, C);
+        bp.w32_first = ar.add(w32.data(), w32.size() * 4);
+        w32.clear();
+        p3::pack_dense_f32(w32, wf.get(p + ".dense.w", (size_t)kNLoc * kNLoc).data);
+        bp.w32_dense = ar.add(w32.data(), w32.size() * 4);
+        w32.clear();
+        p3::pack_conv_f32(w32, W(1, 1, C, C), 1, C, C, C, C);
+        bp.w32_last = ar.add(w32.data(), w32.size() * 4);
+        bp.dense_bias_off = ar.add(wf.get(p + ".dense.b", (size_t)kNLoc).data, kNLoc * 4);
+        e->blocks.push_back(bp);
+        continue;
+      }
       for (int cp = 0; cp < C / CPb; ++cp)
         for (int ip = 0; ip < C / CB; ++ip) {
           pack_segment(s0, W(0, 1, C, C), 1, 1, C, C, ip * CB, CB, cp * CPb, CPb);
@@ -816,9 +855,15 @@ bool build_plan(p3hip_engine* e, Arena& ar) {
                            bool dual, const FoldedBN& out_bn, int in_buf, int out_buf, int out2_buf) {
         LayerPlan lp{kw, cin, cout, pre, act, res, dual, pre_bn, out_bn, in_buf, out_buf, out2_buf};
         std::vector<_Float16> s;
-        for (int cp = 0; cp < cout / 64; ++cp)
-          for (int ip = 0; ip < cin / 64; ++ip) pack_segment(s, W(j, kw, cin, cout), kw * kw, kw * kw, cin, cout, ip * 64, 64, cp * 64, 64);
-        lp.stream_off = add_stream(ar, s, lp.nms, 64);
+        if (f32) {
+          std::vector<float> w32;
+          p3::pack_conv_f32(w32, W(j, kw, cin, cout), kw * kw, cin, cout, cin, cout);
+          lp.w32_off = ar.add(w32.data(), w32.size() * 4);
+        } else {
+          for (int cp = 0; cp < cout / 64; ++cp)
+            for (int ip = 0; ip < cin / 64; ++ip) pack_segment(s, W(j, kw, cin, cout), kw * kw, kw * kw, cin, cout, ip * 64, 64, cp * 64, 64);
+          lp.stream_off = add_stream(ar, s, lp.nms, 64);
+        }
         if (e->int8) {
           std::vector<int8_t> q;
           std::vector<float> sw;
@@ -946,12 +991,18 @@ bool build_plan(p3hip_engine* e, Arena& ar) {
         w[(size_t)c * 96 + 64 + o] = wv[c * 32 + o];
       }
     std::vector<_Float16> s;
-    for (int cp = 0; cp < 2; ++cp)
-      for (int ip = 0; ip < C / CB; ++ip) pack_segment(s, w.data(), 1, 1, C, 96, ip * CB, CB, cp * 64, 64);
-    e->heads_stream_off = add_stream(ar, s, e->heads_nms, 64);
+    if (f32) {
+      std::vector<float> w32;
+      p3::pack_conv_f32(w32, w.data(), 1, C, 96, C, 128);
+      e->heads_w32_off = ar.add(w32.data(), w32.size() * 4);
+    } else {
+      for (int cp = 0; cp < 2; ++cp)
+        for (int ip = 0; ip < C / CB; ++ip) pack_segment(s, w.data(), 1, 1, C, 96, ip * CB, CB, cp * 64, 64);
+      e->heads_stream_off = add_stream(ar, s, e->heads_nms, 64);
+    }
     // the same weights as MFMA 16x16x32 A fragments for k_headsx (the convs inside the heads kernel):
     // [cout tile ct][k32 step][lane (n = lane & 15, q = lane >> 4)][8] = w[cin = 32 step + 8 q + e][cout = 16 ct + n]
-    if (p3::heads_fusable(C, wf.V)) {
+    if (!f32 && p3::heads_fusable(C, wf.V)) {
       std::vector<_Float16> af;
       for (int ct = 0; ct < 6; ++ct)
         for (int st = 0; st < C / 32; ++st)
@@ -978,7 +1029,7 @@ bool build_plan(p3hip_engine* e, Arena& ar) {
       e->head_off[h.name] = ar.add(t.data, t.size() * 4);
     }
     // k_headsx takes the same tensors as one image in its LDS order (kernels.h heads_image_floats)
-    if (p3::heads_fusable(C, wf.V) && wf.missing.empty()) {
+    if (!f32 && p3::heads_fusable(C, wf.V) && wf.missing.empty()) {
       std::vector<float> img;
       auto put = [&](const char* name, size_t n, size_t pad = 0) {
         const Tensor& t = wf.get(name, n);
@@ -1229,7 +1280,11 @@ bool enqueue_forward(p3hip_engine* e, const Pass& p) {
   auto conv1x1 = [&](int which, const p3::Conv1x1Args& a) {
     return any ? p3::launch_conv1x1_any(C, which, a, e->n_cu, s) : p3::launch_conv1x1(C, which, a, e->n_cu, s);
   };
-  {
+  if (e->f32) {
+    const p3::InitF32Args a{p.feats, (float*)e->d_x, npos, C, e->dev<float>(e->init_w32_off), e->dev<float>(e->game_w_off),
+                            e->dev<float>(e->game_b_off)};
+    if (!e->check(p3::launch_init_f32(a, e->n_cu, s), "launch k_init_f32")) return false;
+  } else {
     p3::InitArgs a{};
     a.feats = p.feats; a.x = e->d_x; a.npos = npos;
     a.wstream = e->d_arena + e->init_stream_off; a.nms_total = e->init_nms;
@@ -1261,6 +1316,33 @@ bool enqueue_forward(p3hip_engine* e, const Pass& p) {
       const p3::TfmFfnArgs f{o, e->d_x, npos, e->d_arena + bp.tfm.wo, e->dev<float>(bp.tfm.rms_out),
                              e->d_arena + bp.tfm.wgu, e->d_arena + bp.tfm.wdown};
       if (!e->check(p3::launch_tfm_ffn(d, f, s), "launch k_tfm_ffn")) return false;
+    } else if (bp.kind == 3 && e->f32) {
+      float *x = (float*)e->d_x, *t = (float*)e->d_t, *u = (float*)e->d_u;
+      p3::LConvF32Args c0{};   // t = mish(conv_first(mish(bn0(x))))
+      c0.in = x; c0.out = t; c0.npos = npos; c0.cin = c0.cout = C; c0.w = e->dev<float>(bp.w32_first);
+      c0.pre = 1; c0.act = 2;
+      c0.scale_in = e->dev<float>(bp.bn[0].scale_off); c0.shift_in = e->dev<float>(bp.bn[0].shift_off);
+      if (!e->check(p3::launch_lconv_f32(1, c0, e->n_cu, s), "launch conv_first (fp32)")) return false;
+      const p3::BDenseF32Args d{t, u, npos, C, e->dev<float>(bp.w32_dense), e->dev<float>(bp.dense_bias_off),
+                                e->dev<float>(bp.bn[1].scale_off), e->dev<float>(bp.bn[1].shift_off)};
+      if (!e->check(p3::launch_bdense_f32(d, e->n_cu, s), "launch k_bdense_f32")) return false;
+      p3::LConvF32Args c1{};   // x += conv_last(u)
+      c1.in = u; c1.out = x; c1.npos = npos; c1.cin = c1.cout = C; c1.w = e->dev<float>(bp.w32_last);
+      c1.res = 1;
+      if (!e->check(p3::launch_lconv_f32(1, c1, e->n_cu, s), "launch conv_last (fp32)")) return false;
+    } else if (bp.kind == 4 && e->f32) {
+      const size_t half = (size_t)e->rows * wf.Cb * kNLoc;   // elements of one C_b-channel tensor
+      float* bufs[5] = {(float*)e->d_x, (float*)e->d_t, (float*)e->d_t + half, (float*)e->d_u, (float*)e->d_u + half};
+      for (const LayerPlan& lp : bp.layers) {
+        p3::LConvF32Args a{};
+        a.in = bufs[lp.in_buf]; a.out = bufs[lp.out_buf]; a.out2 = lp.out2_buf >= 0 ? bufs[lp.out2_buf] : nullptr;
+        a.npos = npos; a.cin = lp.cin; a.cout = lp.cout; a.w = e->dev<float>(lp.w32_off);
+        a.pre = lp.pre; a.act = lp.act; a.res = lp.res; a.dual = lp.dual;
+        if (a.pre) { a.scale_in = e->dev<float>(lp.pre_bn.scale_off); a.shift_in = e->dev<float>(lp.pre_bn.shift_off); }
+        if (a.act || a.dual) { a.scale_out = e->dev<float>(lp.out_bn.scale_off); a.shift_out = e->dev<float>(lp.out_bn.shift_off); }
+        auto launch = [&] { return e->check(p3::launch_lconv_f32(lp.kw, a, e->n_cu, s), "launch k_lconv_f32"); };
+        if (!timed_launch(e, lp.kw == 3 ? p.timed : nullptr, launch)) return false;
+      }
     } else if (bp.kind == 3) {
       p3::Conv1x1Args c0{};
       c0.in = e->d_x; c0.out16 = e->d_t; c0.npos = npos;
@@ -1377,7 +1459,12 @@ bool enqueue_forward(p3hip_engine* e, const Pass& p) {
     p3::Conv1x1Args c{};
     c.in = e->d_x; c.out32 = e->d_hp; c.npos = npos;
     c.wstream = e->d_arena + e->heads_stream_off; c.nms_total = e->heads_nms;
-    if (!e->heads_fused && !e->check(conv1x1(2, c), "launch head convs")) return false;
+    if (e->f32) {
+      p3::LConvF32Args hc{};   // the three head convs C -> 96 in fp32, hp in k_heads' layout
+      hc.in = (const float*)e->d_x; hc.out = e->d_hp; hc.npos = npos; hc.cin = C; hc.cout = 128; hc.hp = 1;
+      hc.w = e->dev<float>(e->heads_w32_off);
+      if (!e->check(p3::launch_lconv_f32(1, hc, e->n_cu, s), "launch head convs (fp32)")) return false;
+    } else if (!e->heads_fused && !e->check(conv1x1(2, c), "launch head convs")) return false;
     p3::HeadsArgs h{};
     h.x = e->d_x;
     h.conv_a = e->d_arena + e->heads_conv_a_off;
@@ -1538,6 +1625,7 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
   e->int8 = (flags & (P3HIP_FLAG_INT8 | P3HIP_FLAG_INT8_FUSED | P3HIP_FLAG_INT8_C128)) != 0;
   e->i8f = (flags & (P3HIP_FLAG_INT8_FUSED | P3HIP_FLAG_INT8_C128)) != 0;
   e->i8c128 = (flags & P3HIP_FLAG_INT8_C128) != 0;
+  e->f32 = (flags & P3HIP_FLAG_FP32) != 0;
   e->sym = sym;
   e->rows = sym ? p3::kNumSyms * batch_size : batch_size;
   auto fail = [&](const std::string& m) {
@@ -1565,6 +1653,7 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
   // two C_b-channel ones side by side (enqueue_forward, regions 1 and 2): 2 C_b > C where C_b > C / 2 (P3HIP_CONV_SET
   // allows C_b up to C, and padding C_b to a multiple of 64 can pass C / 2 as well)
   const size_t Ct = (e->wf.btype == 0 || e->wf.btype == 1) ? std::max<size_t>(C, 2 * (size_t)e->wf.Cb) : (size_t)C;
+  const size_t eb = e->f32 ? 4 : 2;   // bytes per activation element
   const size_t qkv_bytes = 3 * R * p3::kTfmLPad * (size_t)e->wf.model_C * 2;   // heads x head width = model width
   bool ok = e->check(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking), "hipStreamCreate") &&
             e->check(hipMalloc((void**)&e->d_arena, ar.host.size()), "hipMalloc arena") &&
@@ -1576,10 +1665,11 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
             e->check(hipHostMalloc((void**)&e->h_out, B * p3::kResultFloats * 4, hipHostMallocDefault), "hipHostMalloc") &&
             e->check(hipMalloc((void**)&e->d_res, B * p3::kResultFloats * 4), "hipMalloc results") &&
             e->check(hipMalloc((void**)&e->d_feats, R * kFeatBytes), "hipMalloc feats") &&
-            e->check(hipMalloc((void**)&e->d_x, R * C * kNLoc * 2), "hipMalloc x") &&
-            e->check(hipMalloc((void**)&e->d_t, R * Ct * kNLoc * 2), "hipMalloc t") &&
-            e->check(hipMalloc((void**)&e->d_u, R * C * kNLoc * 2), "hipMalloc u") &&
-            (e->wf.btype != 1 || e->check(hipMalloc((void**)&e->d_s, R * e->wf.Cb * kNLoc * 2), "hipMalloc s")) &&
+            e->check(hipMalloc((void**)&e->d_x, R * C * kNLoc * eb), "hipMalloc x") &&
+            e->check(hipMalloc((void**)&e->d_t, R * Ct * kNLoc * eb), "hipMalloc t") &&
+            e->check(hipMalloc((void**)&e->d_u, R * C * kNLoc * eb), "hipMalloc u") &&
+            // (d_s is the fused nbt kernel's scratch; the fp32 plan runs layer by layer and has none)
+            (e->wf.btype != 1 || e->f32 || e->check(hipMalloc((void**)&e->d_s, R * e->wf.Cb * kNLoc * 2), "hipMalloc s")) &&
             (!e->tfm || e->check(hipMalloc((void**)&e->d_qkv, qkv_bytes), "hipMalloc qkv")) &&
             e->check(hipMalloc((void**)&e->d_hp, R * 96 * kNLoc * 4), "hipMalloc hp") &&
             e->check(hipMalloc((void**)&e->d_out, B * p3::kOutStride * 4), "hipMalloc out") &&
@@ -2028,9 +2118,9 @@ double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
     name = e->i8c128 ? p3::block_i8_c128_kernel_name() : p3::block_i8_kernel_name();
   } else if (!bp) {
     // (conv_any: the file's own width, not the padded one the kernel runs)
-    const double w3 = e->conv_any ? (wf.btype == 2 ? wf.model_C : wf.model_Cb) : c3;
+    const double w3 = (e->conv_any || e->f32) ? (wf.btype == 2 ? wf.model_C : wf.model_Cb) : c3;
     flops = 2.0 * n_positions * kNLoc * 9.0 * w3 * w3;
-    name = e->int8 ? p3::lconv_i8_kernel_name(3, c3, c3)
+    name = e->f32 ? p3::lconv_f32_kernel_name(3) : e->int8 ? p3::lconv_i8_kernel_name(3, c3, c3)
                    : (e->conv_any ? p3::lconv_any_kernel_name(3) : (c3 == 192 ? "k_lconv<3,192,192>" : "k_lconv<3,64,64>"));
   } else {
     const double n3 = (wf.btype == 0) ? wf.inner : 4;
@@ -2062,6 +2152,10 @@ int p3hip_debug_x(p3hip_engine* e, float* out, int n_positions) {
   if (e->sym) { e->err = "p3hip_debug_x: not available on a P3HIP_FLAG_SYMMETRY_AVG engine"; return 1; }
   if (!e->bind() || n_positions < 1 || n_positions > e->batch) return 1;
   const size_t n = (size_t)n_positions * e->wf.C * kNLoc;
+  if (e->f32) {   // the fp32 stream has the same order: the stored values themselves
+    hipStreamSynchronize(e->stream);
+    return hipMemcpy(out, e->d_x, n * 4, hipMemcpyDeviceToHost) == hipSuccess ? 0 : 2;
+  }
   std::vector<_Float16> h(n);
   hipStreamSynchronize(e->stream);
   if (hipMemcpy(h.data(), e->d_x, n * 2, hipMemcpyDeviceToHost) != hipSuccess) return 2;

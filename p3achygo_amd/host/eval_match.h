@@ -94,6 +94,9 @@ struct EvalPlayerConfig {   // PlayerSearchConfig (player_config.h:20-108), same
   // extension: the player's engine averages every evaluation over these symmetries on the device
   // (P3HIP_FLAG_SYMMETRY_AVG + p3hip_set_symmetries; bit s = symmetry s).  0 = off: one random symmetry per leaf.
   uint32_t nn_symmetry_mask = 0;
+  // extension: the player's engine runs the fp32 plan (P3HIP_FLAG_FP32, conv trunks only).  0 = the fp16 plan.  A net
+  // against itself with one player in fp32 measures what fp16 costs in play.
+  int nn_fp32 = 0;
 };
 
 // nn_symmetry_mask: decimal or 0x hex, 0 .. 255
@@ -222,6 +225,13 @@ inline bool ParsePlayerConfigStream(std::istream& in, EvalPlayerConfig* cfg, std
           if (err) *err = "nn_symmetry_mask must be 0 .. 255, decimal or 0x hex: " + line;
           return false;
         }
+      }
+      else if (key == "nn_fp32") {
+        if (val != "0" && val != "1") {
+          if (err) *err = "nn_fp32 must be 0 or 1: " + line;
+          return false;
+        }
+        cfg->nn_fp32 = val == "1";
       }
       // unknown keys are ignored (player_config.h:243)
     }
