@@ -130,7 +130,21 @@ typedef struct p3hip_engine p3hip_engine;
                                        the f32-input MFMA (v_mfma_f32_32x32x2_f32, bit-equal to an fmaf chain): no fp16 value
                                        exists in the pass.  The activation buffers are twice the fp16 plan's.  The other
                                        flags, the NN cache and compaction work as on any engine.  p3hip_create returns NULL
-                                       for a transformer trunk and together with any of the three INT8 flags */
+                                       for a transformer trunk (those have P3HIP_FLAG_FP32_TFM) and together with any of the
+                                       three INT8 flags */
+#define P3HIP_FLAG_FP32_TFM 512u    /* full-precision inference of the transformer trunks: every trunk of
+                                       P3HIP_TRANSFORMER_SET runs in fp32 from the stem to the heads
+                                       (csrc/transformer_f32.hip; DESIGN.md section 11, "Transformer trunks").  The stem and
+                                       the head convs are those of P3HIP_FLAG_FP32 at the stream's width; the six GEMM
+                                       matrices of a block are packed as fp32, the residual stream, q, k, v, o, the softmax
+                                       numerators and silu(gate) * up are fp32, and every product accumulates on the
+                                       f32-input MFMA (v_mfma_f32_16x16x4_f32): no fp16 value exists in the pass.  The
+                                       activation buffers are twice the fp16 plan's.  The other flags, the NN cache and
+                                       compaction work as on any engine.  p3hip_create returns NULL for a conv trunk when
+                                       P3HIP_FLAG_FP32 is not set as well, and together with any of the three INT8 flags */
+#define P3HIP_FLAG_FP32_ANY (256u | 512u) /* P3HIP_FLAG_FP32 | P3HIP_FLAG_FP32_TFM: full precision whatever the trunk.  A
+                                       conv trunk takes the plan of P3HIP_FLAG_FP32 (bit-identical to that flag alone), a
+                                       transformer trunk the plan of P3HIP_FLAG_FP32_TFM */
 
 /* Transformer trunks (python/model_transformer.py TransformerBlock, a generic_arch of "transformer" blocks) the engine
  * runs: every block has the same embed_dim d and num_heads h, d equals the stem's channels, d is a multiple of 32 with
@@ -268,7 +282,7 @@ int p3hip_graph_state(const p3hip_engine* e);
 int p3hip_blockw_stamps(p3hip_engine* e, unsigned long long* out, int n);
 /* Debugging aid: the residual stream x after the last forward pass (stopped early by P3HIP_DEBUG_STOP_BLOCK in the
  * environment, if set), n_positions x C x 361 values in the device layout [pos][C / 8][361][8], as floats.
- * A P3HIP_FLAG_FP32 engine returns its stored fp32 values, exactly, in the same order.
+ * A P3HIP_FLAG_FP32 or P3HIP_FLAG_FP32_TFM engine returns its stored fp32 values, exactly, in the same order.
  * Transformer trunks: C is the stream's padded width (the model's d channels, then the channels up to 128, 256 or 384
  * that stay zero). */
 int p3hip_debug_x(p3hip_engine* e, float* out, int n_positions);
@@ -277,7 +291,8 @@ int p3hip_debug_x(p3hip_engine* e, float* out, int n_positions);
  * attention output o as [pos][361][d].  It only reads buffers the forward pass owns.  The heads take o's buffer as
  * scratch: o is the last block's only on an engine stopped in front of them (P3HIP_DEBUG_STOP_BLOCK = n ends the pass
  * in front of block n; n = the block count ends it after the last block, in front of the heads).  Returns non-zero for
- * an engine without a transformer trunk, for n_positions < 1 or beyond the last run's, and for any other `which`. */
+ * an engine without a transformer trunk, for n_positions < 1 or beyond the last run's, and for any other `which`.
+ * A P3HIP_FLAG_FP32_TFM engine returns its stored fp32 values, exactly, in the same orders. */
 int p3hip_debug_tfm(p3hip_engine* e, int which, float* out, int n_positions);
 /* Algorithmic FLOPs (2*MAC) of one position: total, and 3x3 trunk convs only. */
 void p3hip_flops_per_position(const p3hip_engine* e, double* total, double* conv3x3);

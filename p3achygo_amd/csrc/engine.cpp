@@ -34,6 +34,7 @@
 #include "slot_state.h"
 #include "symmetry.h"
 #include "transformer.h"
+#include "transformer_f32.h"
 
 namespace {
 
@@ -464,6 +465,8 @@ struct p3hip_engine {
   // P3HIP_FLAG_FP32: every conv trunk layer by layer through the kernels of conv_f32.hip; weights and the activation
   // buffers d_x, d_t, d_u are fp32 (the buffers keep their fp16 pointer types and are 4 bytes per element), the heads
   // run k_heads on the hp the fp32 head convs write.  No fp16 value exists in the pass.
+  // P3HIP_FLAG_FP32_TFM: the same for a transformer trunk, its blocks through the kernels of transformer_f32.hip; d_qkv
+  // is fp32 too.
   bool f32 = false;
   size_t init_w32_off = 0, heads_w32_off = 0;
   bool heads_fused = false;   // k_headsx: the head convs inside the heads kernel (C <= 256; P3HIP_NO_HFUSE clears it)
@@ -563,12 +566,21 @@ bool build_plan(p3hip_engine* e, Arena& ar) {
   const int C = wf.C, Cb = wf.Cb;
   const bool i8f = e->i8f;
   const bool f32 = e->f32;
-  if (f32 && wf.btype == 3) {
-    e->err = "P3HIP_FLAG_FP32 serves the conv trunks only (" P3HIP_CONV_SET "); the transformer trunks run in fp16";
+  // P3HIP_FLAG_FP32 serves the conv trunks, P3HIP_FLAG_FP32_TFM the transformers; both together: whatever the trunk
+  const bool f32_conv = (e->flags & P3HIP_FLAG_FP32) != 0, f32_tfm = (e->flags & P3HIP_FLAG_FP32_TFM) != 0;
+  if (f32 && wf.btype == 3 && !f32_tfm) {
+    e->err = "P3HIP_FLAG_FP32 serves the conv trunks only (" P3HIP_CONV_SET "); the transformer trunks run in fp16, or in "
+             "fp32 with P3HIP_FLAG_FP32_TFM";
+    return false;
+  }
+  if (f32 && wf.btype != 3 && !f32_conv) {
+    e->err = "P3HIP_FLAG_FP32_TFM serves the transformer trunks only (" P3HIP_TRANSFORMER_SET "); the conv trunks have "
+             "P3HIP_FLAG_FP32";
     return false;
   }
   if (f32 && e->int8) {
-    e->err = "P3HIP_FLAG_FP32 cannot be combined with P3HIP_FLAG_INT8, P3HIP_FLAG_INT8_FUSED or P3HIP_FLAG_INT8_C128: an "
+    e->err = std::string(f32_conv ? (f32_tfm ? "P3HIP_FLAG_FP32 | P3HIP_FLAG_FP32_TFM" : "P3HIP_FLAG_FP32") : "P3HIP_FLAG_FP32_TFM") +
+             " cannot be combined with P3HIP_FLAG_INT8, P3HIP_FLAG_INT8_FUSED or P3HIP_FLAG_INT8_C128: an "
              "engine runs one precision plan";
     return false;
   }
@@ -727,6 +739,23 @@ bool build_plan(p3hip_engine* e, Arena& ar) {
     bp.kind = 5;
     bp.tfm.rms_in = ar.add(T("rms_in.scale", c), c * 4);
     bp.tfm.rms_out = ar.add(T("rms_out.scale", c), c * 4);
+    if (f32) {   // P3HIP_FLAG_FP32_TFM: the same fragments in fp32 (transformer_f32.h pack_tfm_f32), no fp16 image
+      std::vector<float> w32;
+      for (const char* n : {"q.w", "k.w", "v.w"}) p3::pack_tfm_f32(w32, T(n, (size_t)c * c), c, c, c, 0);
+      bp.tfm.wqkv = ar.add(w32.data(), w32.size() * 4);
+      w32.clear();
+      p3::pack_tfm_f32(w32, T("o.w", (size_t)c * c), c, c, c, 0);
+      bp.tfm.wo = ar.add(w32.data(), w32.size() * 4);
+      w32.clear();
+      p3::pack_tfm_f32(w32, T("ffn_gate.w", (size_t)c * f), c, f, f, 0);
+      p3::pack_tfm_f32(w32, T("ffn_up.w", (size_t)c * f), c, f, f, 0);
+      bp.tfm.wgu = ar.add(w32.data(), w32.size() * 4);
+      w32.clear();
+      p3::pack_tfm_f32(w32, T("ffn_down.w", (size_t)f * c), f, c, c, 0);
+      bp.tfm.wdown = ar.add(w32.data(), w32.size() * 4);
+      e->blocks.push_back(bp);
+      continue;
+    }
     std::vector<_Float16> w;
     for (const char* n : {"q.w", "k.w", "v.w"}) pack_afrag(w, T(n, (size_t)c * c), c, c, c, 0);
     bp.tfm.wqkv = ar.add(w.data(), w.size() * 2);
@@ -1303,7 +1332,20 @@ bool enqueue_forward(p3hip_engine* e, const Pass& p) {
   for (size_t bi = 0; bi < e->blocks.size(); ++bi) {
     if (stop_block >= 0 && (int)bi >= stop_block) return true;
     const BlockPlan& bp = e->blocks[bi];
-    if (bp.kind == 5) {
+    if (bp.kind == 5 && e->f32) {
+      const int d = wf.model_C;
+      const size_t per = (size_t)e->rows * p3::kTfmLPad * d;   // one of q, k, v: [rows][head][384][D] floats
+      float *x = (float*)e->d_x, *q = (float*)e->d_qkv, *k = q + per, *v = k + per, *o = (float*)e->d_t;
+      const p3::TfmQkvF32Args a{x, q, k, v, npos, d, e->tfm_D, e->dev<float>(bp.tfm.rms_in), e->dev<float>(bp.tfm.wqkv),
+                                e->dev<float>(e->rope_cos_off), e->dev<float>(e->rope_sin_off)};
+      if (!e->check(p3::launch_tfm_qkv_f32(a, s), "launch k_tfm_qkv_f32")) return false;
+      const p3::TfmAttnF32Args b{q, k, v, o, npos, e->tfm_heads};
+      if (!timed_launch(e, p.timed, [&] { return e->check(p3::launch_tfm_attn_f32(e->tfm_D, b, s), "launch k_tfm_attn_f32"); }))
+        return false;
+      const p3::TfmFfnF32Args f{o, x, npos, d, e->dev<float>(bp.tfm.wo), e->dev<float>(bp.tfm.rms_out),
+                                e->dev<float>(bp.tfm.wgu), e->dev<float>(bp.tfm.wdown)};
+      if (!e->check(p3::launch_tfm_ffn_f32(f, s), "launch k_tfm_ffn_f32")) return false;
+    } else if (bp.kind == 5) {
       const int d = wf.model_C;
       const size_t per = (size_t)e->rows * p3::kTfmLPad * d;   // one of q, k, v: [rows][head][384][D]
       _Float16 *q = e->d_qkv, *k = q + per, *v = k + per, *o = e->d_t;
@@ -1625,7 +1667,7 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
   e->int8 = (flags & (P3HIP_FLAG_INT8 | P3HIP_FLAG_INT8_FUSED | P3HIP_FLAG_INT8_C128)) != 0;
   e->i8f = (flags & (P3HIP_FLAG_INT8_FUSED | P3HIP_FLAG_INT8_C128)) != 0;
   e->i8c128 = (flags & P3HIP_FLAG_INT8_C128) != 0;
-  e->f32 = (flags & P3HIP_FLAG_FP32) != 0;
+  e->f32 = (flags & (P3HIP_FLAG_FP32 | P3HIP_FLAG_FP32_TFM)) != 0;
   e->sym = sym;
   e->rows = sym ? p3::kNumSyms * batch_size : batch_size;
   auto fail = [&](const std::string& m) {
@@ -1654,7 +1696,7 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
   // allows C_b up to C, and padding C_b to a multiple of 64 can pass C / 2 as well)
   const size_t Ct = (e->wf.btype == 0 || e->wf.btype == 1) ? std::max<size_t>(C, 2 * (size_t)e->wf.Cb) : (size_t)C;
   const size_t eb = e->f32 ? 4 : 2;   // bytes per activation element
-  const size_t qkv_bytes = 3 * R * p3::kTfmLPad * (size_t)e->wf.model_C * 2;   // heads x head width = model width
+  const size_t qkv_bytes = 3 * R * p3::kTfmLPad * (size_t)e->wf.model_C * eb;   // heads x head width = model width
   bool ok = e->check(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking), "hipStreamCreate") &&
             e->check(hipMalloc((void**)&e->d_arena, ar.host.size()), "hipMalloc arena") &&
             // on the engine's own stream: it is non-blocking (no implicit ordering with the null stream a plain
@@ -2111,7 +2153,7 @@ double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
   if (e->tfm) {
     // q.k^T and p.v over the 361 x 361 tokens of every head (algorithmic, not the padded 384 keys)
     flops = 2.0 * n_positions * 2.0 * kNLoc * kNLoc * wf.model_C;
-    name = "k_tfm_attn";
+    name = e->f32 ? p3::tfm_attn_f32_kernel_name() : "k_tfm_attn";
   } else if (e->i8f) {
     // every conv of one btl block, as for the fp16 block launch below
     flops = 2.0 * n_positions * kNLoc * (wf.inner * 9.0 * wf.Cb * wf.Cb + 2.0 * wf.C * wf.Cb);
@@ -2175,9 +2217,13 @@ int p3hip_debug_tfm(p3hip_engine* e, int which, float* out, int n_positions) {
   const size_t d = (size_t)e->wf.model_C;
   const size_t per = (size_t)e->rows * p3::kTfmLPad * d;
   const size_t n = (size_t)n_positions * (which < 3 ? p3::kTfmLPad : kNLoc) * d;
+  hipStreamSynchronize(e->stream);
+  if (e->f32) {   // the fp32 buffers have the same orders: the stored values themselves
+    const float* src32 = which < 3 ? (const float*)e->d_qkv + which * per : (const float*)e->d_t;
+    return hipMemcpy(out, src32, n * 4, hipMemcpyDeviceToHost) == hipSuccess ? 0 : 2;
+  }
   const _Float16* src = which < 3 ? e->d_qkv + which * per : e->d_t;
   std::vector<_Float16> h(n);
-  hipStreamSynchronize(e->stream);
   if (hipMemcpy(h.data(), src, n * 2, hipMemcpyDeviceToHost) != hipSuccess) return 2;
   for (size_t i = 0; i < n; ++i) out[i] = (float)h[i];
   return 0;

@@ -41,6 +41,8 @@ FLAG_INT8 = 16   # calibrated INT8 convs in the layer-wise blocks (include/p3hip
 FLAG_INT8_FUSED = 64   # calibrated INT8 of the C = 256 btl trunks, one fused int8 block kernel per block (section 9)
 FLAG_INT8_C128 = 128   # the same for the C = 128 / C_b = 64 btl trunks (b12c128btl3): k_block_i8<128,64>, two workgroups per CU
 FLAG_FP32 = 256   # the conv trunks layer by layer in fp32, weights and activations included
+FLAG_FP32_TFM = 512   # the transformer trunks in fp32, weights and activations included
+FLAG_FP32_ANY = FLAG_FP32 | FLAG_FP32_TFM   # full precision whatever the trunk
 FLAG_SYMMETRY_AVG = 32  # every slot averaged over a set of the eight symmetries on the device
 
 

@@ -94,7 +94,7 @@ struct EvalPlayerConfig {   // PlayerSearchConfig (player_config.h:20-108), same
   // extension: the player's engine averages every evaluation over these symmetries on the device
   // (P3HIP_FLAG_SYMMETRY_AVG + p3hip_set_symmetries; bit s = symmetry s).  0 = off: one random symmetry per leaf.
   uint32_t nn_symmetry_mask = 0;
-  // extension: the player's engine runs the fp32 plan (P3HIP_FLAG_FP32, conv trunks only).  0 = the fp16 plan.  A net
+  // extension: the player's engine runs its trunk's fp32 plan (P3HIP_FLAG_FP32_ANY: conv and transformer trunks).  0 = the fp16 plan.  A net
   // against itself with one player in fp32 measures what fp16 costs in play.
   int nn_fp32 = 0;
 };

@@ -1,14 +1,19 @@
-"""fp16 against fp32 (P3HIP_FLAG_FP32), interleaved A/B on one MI355X.
+"""fp16 against fp32 (P3HIP_FLAG_FP32_ANY: P3HIP_FLAG_FP32 on conv trunks, P3HIP_FLAG_FP32_TFM on transformers),
+interleaved A/B on one MI355X.
 
 For each trunk and batch size, the two engines are built from the same seeded .p3w.  Legs alternate fp16, fp32, fp16,
 fp32, ...; each leg times `--steps` device-resident forward passes (engine only: no H2D / D2H) with the chip's clock,
 power and limiter residency sampled beside it (p3achygo_amd/power_sampler.py, as bench.py does), then the trunk kernel
 alone (p3hip_time_trunk_kernel).  The fp32 leg's kernel is the 3x3 layer conv k_lconv_f32<3>, reported with its time per
 launch and its fraction of the 157.3 TFLOP/s of the f32-input MFMA; the fp16 leg's is whatever the fp16 plan of the
-trunk runs (the fused block kernel at C = 128 / 256, the 3x3 layer conv at C = 384).
+trunk runs (the fused block kernel at C = 128 / 256, the 3x3 layer conv at C = 384).  On a transformer trunk both legs
+time their attention kernel (k_tfm_attn, k_tfm_attn_f32), and the summary's fp32 kernel keys are fp32_attn_* where a conv
+trunk has fp32_k3x3_*.
 Prints one JSON line per leg and a summary per (trunk, batch); --out writes them all.
 
   python tools/gpu_fp32_ab.py --out profiles/fp32_ab.jsonl
+  python tools/gpu_fp32_ab.py --nets test_b2d96h3_tfm test_b2d192h6_tfm test_b2d384h12_tfm --batches 1024 \
+      --out profiles/fp32_tfm_ab.jsonl
 """
 import argparse
 import json
@@ -20,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-PEAK_F32_MFMA = 157.3e12   # v_mfma_f32_32x32x2_f32: the fp32 vector rate (MI355X_MICROARCH.md)
+PEAK_F32_MFMA = 157.3e12   # v_mfma_f32_32x32x2_f32 / v_mfma_f32_16x16x4_f32: the fp32 vector rate
 
 
 def main():
@@ -42,7 +47,7 @@ def main():
             netspec.save_p3w(path, cfg, netspec.generate_weights(cfg, randomize=True))
             for batch in args.batches:
                 pos = features.random_positions(batch, seed=7, n_games=max(1, batch // 16))
-                engs = {"fp16": engine.HipEngine(path, batch), "fp32": engine.HipEngine(path, batch, flags=engine.FLAG_FP32)}
+                engs = {"fp16": engine.HipEngine(path, batch), "fp32": engine.HipEngine(path, batch, flags=engine.FLAG_FP32_ANY)}
                 for eng in engs.values():
                     eng.load_all(pos)
                     eng.upload()
@@ -57,13 +62,14 @@ def main():
                 for eng in engs.values():
                     eng.close()
                 med = lambda k, f: sorted(v[f] for v in res[k])[len(res[k]) // 2]
+                k32 = "fp32_attn" if cfg.block_type == "transformer" else "fp32_k3x3"
                 s = {"summary": True, "net": name, "batch": batch,
                      "fp16_pos_per_s": med("fp16", "pos_per_s"), "fp32_pos_per_s": med("fp32", "pos_per_s"),
                      "fp16_kernel": res["fp16"][0]["kernel_name"], "fp16_kernel_ms": med("fp16", "kernel_ms"),
-                     "fp32_kernel": res["fp32"][0]["kernel_name"], "fp32_k3x3_ms": med("fp32", "kernel_ms")}
+                     "fp32_kernel": res["fp32"][0]["kernel_name"], k32 + "_ms": med("fp32", "kernel_ms")}
                 s["fp32_over_fp16_time"] = s["fp16_pos_per_s"] / s["fp32_pos_per_s"]
-                s["fp32_k3x3_tflops"] = res["fp32"][0]["kernel_flops"] / (s["fp32_k3x3_ms"] * 1e-3) / 1e12
-                s["fp32_k3x3_of_f32_mfma_peak"] = s["fp32_k3x3_tflops"] * 1e12 / PEAK_F32_MFMA
+                s[k32 + "_tflops"] = res["fp32"][0]["kernel_flops"] / (s[k32 + "_ms"] * 1e-3) / 1e12
+                s[k32 + "_of_f32_mfma_peak"] = s[k32 + "_tflops"] * 1e12 / PEAK_F32_MFMA
                 for kind in ("fp16", "fp32"):
                     chips = [v["chip"] for v in res[kind] if v.get("chip")]
                     if chips:

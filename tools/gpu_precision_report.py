@@ -1,13 +1,15 @@
 """What each precision plan costs in accuracy, measured against the fp32 engine on one MI355X: the counterpart of the
 reference's cc/nn/engine/scripts/compare_engines.cc.
 
-For one net and N positions of features.random_positions, runs the fp32 engine (P3HIP_FLAG_FP32), the fp16 engine and
+For one net and N positions of features.random_positions, runs the fp32 engine (P3HIP_FLAG_FP32_ANY: the fp32 plan of
+the net's trunk, conv or transformer; a transformer's only other plan is fp16), the fp16 engine and
 every INT8 plan that serves the net (P3HIP_FLAG_INT8, _INT8_FUSED, _INT8_C128: the ones p3hip_create accepts, calibrated
 on the same positions), and prints one JSON line per plan: its largest and mean deviation from the fp32 engine in the raw
 outputs and in the move, value and score probabilities, and the largest and mean KL(fp32 || plan) of the move, value and
-score distributions.  --out writes the lines (default profiles/precision_report.jsonl).
+score distributions.  --out writes the lines (default profiles/precision_report.jsonl); --append adds them to the file.
 
   python tools/gpu_precision_report.py --net b12c256btl3 --positions 1024
+  python tools/gpu_precision_report.py --net b14d96h3_transformer --positions 512 --append
 """
 import argparse
 import json
@@ -50,6 +52,7 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "precision_report.jsonl"))
+    ap.add_argument("--append", action="store_true", help="add the lines to --out instead of replacing it")
     args = ap.parse_args()
     from p3achygo_amd import engine, features, netspec
     cfg = netspec.get_config(args.net)
@@ -58,7 +61,7 @@ def main():
     with tempfile.TemporaryDirectory() as d:
         path = os.path.join(d, args.net + ".p3w")
         netspec.save_p3w(path, cfg, netspec.generate_weights(cfg, randomize=True))
-        eng = engine.HipEngine(path, args.batch, flags=engine.FLAG_FP32)
+        eng = engine.HipEngine(path, args.batch, flags=engine.FLAG_FP32_ANY)
         ref = evaluate(eng, pos, args.batch)
         eng.close()
         plans = [("fp16", 0), ("int8", engine.FLAG_INT8), ("int8_fused", engine.FLAG_INT8_FUSED), ("int8_c128", engine.FLAG_INT8_C128)]
@@ -87,7 +90,7 @@ def main():
             lines.append(x)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
+        with open(args.out, "a" if args.append else "w") as f:
             for x in lines:
                 f.write(json.dumps(x) + "\n")
 
