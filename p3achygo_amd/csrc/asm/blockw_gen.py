@@ -131,7 +131,7 @@ class BlockGen:
         self.e = Emitter()
         self.ngran = 32 + 72 * L          # granules of one block: reduce 16, layers 72 each, expand 16
         self.nstamp = 0
-        # parameter table of one block (floats, engine.cpp): bn0 scale[256] shift[256], both times log2(e);
+        # parameter table of one block (floats, plan.cpp pack_blockw_runs): bn0 scale[256] shift[256], both times log2(e);
         # then per conv j = 0..L (reduce, inner layers): the NEXT BN's shift[128] times log2(e) (its scale is in the weights)
         self.prm_floats = 512 + 128 * (L + 1)
 

@@ -1,4 +1,4 @@
-"""numpy restatement of what k_blockw computes, and of engine.cpp's packing of its weight stream / parameter table
+"""numpy restatement of what k_blockw computes, and of plan.cpp's packing of its weight stream / parameter table
 (test infrastructure: tests/test_blockw_asm_cpu.py runs the generated assembly in sim.py against this)."""
 import numpy as np
 
@@ -66,7 +66,7 @@ def granule(Wf, tap, k0, cout0, scale=None):
 
 
 def pack_block(W, bn, L):
-    """-> (weight stream fp16, parameter floats) of one block, engine.cpp build_plan's order"""
+    """-> (weight stream fp16, parameter floats) of one block, plan.cpp pack_blockw_runs' order"""
     ws = []
     sc = lambda j: (bn[j][0] * LOG2E).astype(np.float32)      # noqa: E731
     w0 = W[0].reshape(1, 256, 128)

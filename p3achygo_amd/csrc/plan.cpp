@@ -1,0 +1,753 @@
+// plan.cpp — choose_plan (which trunk path an engine runs, and every refusal) and build_plan (the weights of that path
+// repacked into the arena image, one packer per block family).  No HIP runtime call.
+#include "plan.h"
+
+#include <cmath>
+#include <cstdlib>
+#include <utility>
+
+#include "../../include/p3hip.h"
+#include "conv_any.h"
+#include "conv_f32.h"
+#include "lconv_i8.h"
+#include "transformer.h"
+#include "transformer_f32.h"
+
+namespace eng {
+
+Options Options::from_env() {
+  auto set = [](const char* n) { return getenv(n) != nullptr; };
+  auto num = [](const char* n, int dflt) { return getenv(n) ? atoi(getenv(n)) : dflt; };
+  Options o;
+  o.c128_wg8 = set("P3HIP_C128_WG8");
+  o.bcast_fuse = !set("P3HIP_NO_BFUSE");
+  o.dense_fuse = !set("P3HIP_NO_DFUSE");
+  o.heads_fuse = !set("P3HIP_NO_HFUSE");
+  o.stop_block = num("P3HIP_DEBUG_STOP_BLOCK", -1);
+  o.fuse = !set("P3HIP_NO_FUSE");
+  o.join = o.fuse && !set("P3HIP_NO_JOIN");
+  o.stagger = num("P3HIP_STAGGER", -1);
+  o.pair_turns = !set("P3HIP_NO_PAIR_TURNS");
+  o.direct_results = !set("P3HIP_NO_DIRECT_RESULTS");
+  o.time_run = set("P3HIP_TIME_RUN");
+  o.blockw = num("P3HIP_BLOCKW", 0) != 0;
+  o.blockw_diag = set("P3HIP_BLOCKW_DIAG");
+  o.conv_any = num("P3HIP_CONV_ANY", 0) != 0;
+  return o;
+}
+
+PlanChoice choose_plan(const WeightFile& wf, uint32_t flags, const Options& opt, std::string& err) {
+  const int C = wf.C, Cb = wf.Cb;
+  const bool int8 = (flags & (P3HIP_FLAG_INT8 | P3HIP_FLAG_INT8_FUSED | P3HIP_FLAG_INT8_C128)) != 0;
+  const bool i8f = (flags & (P3HIP_FLAG_INT8_FUSED | P3HIP_FLAG_INT8_C128)) != 0;
+  const bool i8c = (flags & P3HIP_FLAG_INT8_C128) != 0;
+  // P3HIP_FLAG_FP32 serves the conv trunks, P3HIP_FLAG_FP32_TFM the transformers; both together: whatever the trunk
+  const bool f32_conv = (flags & P3HIP_FLAG_FP32) != 0, f32_tfm = (flags & P3HIP_FLAG_FP32_TFM) != 0;
+  const bool f32 = f32_conv || f32_tfm;
+  PlanChoice c;
+  if (f32 && wf.btype == 3 && !f32_tfm) {
+    err = "P3HIP_FLAG_FP32 serves the conv trunks only (" P3HIP_CONV_SET "); the transformer trunks run in fp16, or in "
+          "fp32 with P3HIP_FLAG_FP32_TFM";
+    return c;
+  }
+  if (f32 && wf.btype != 3 && !f32_conv) {
+    err = "P3HIP_FLAG_FP32_TFM serves the transformer trunks only (" P3HIP_TRANSFORMER_SET "); the conv trunks have "
+          "P3HIP_FLAG_FP32";
+    return c;
+  }
+  if (f32 && int8) {
+    err = std::string(f32_conv ? (f32_tfm ? "P3HIP_FLAG_FP32 | P3HIP_FLAG_FP32_TFM" : "P3HIP_FLAG_FP32") : "P3HIP_FLAG_FP32_TFM") +
+          " cannot be combined with P3HIP_FLAG_INT8, P3HIP_FLAG_INT8_FUSED or P3HIP_FLAG_INT8_C128: an "
+          "engine runs one precision plan";
+    return c;
+  }
+  // a conv file whose widths were padded (WeightFile::pad_conv) never takes the plan of the shape it was padded to
+  const bool exact = wf.btype == 3 || (wf.model_C == C && wf.model_Cb == Cb);
+  const bool fused = !i8f && !f32 && exact && ((C == 256 && Cb == 128) || (C == 128 && Cb == 64));
+  const bool classic = wf.btype == 2 && wf.inner == 2;                 // two 3x3 convs C -> C
+  const bool classic192 = classic && exact && C == 192;                // b15c192_classic
+  const bool bottleneck_ok = wf.btype == 1 || (wf.btype == 0 && wf.inner >= 1 && wf.inner <= 3);
+  // P3HIP_FLAG_INT8_FUSED: the btl trunks of the fused block kernel's C = 256 width; P3HIP_FLAG_INT8_C128: those of its
+  // C = 128 width; each alone among the three INT8 flags
+  const uint32_t i8_flags = flags & (P3HIP_FLAG_INT8 | P3HIP_FLAG_INT8_FUSED | P3HIP_FLAG_INT8_C128);
+  const bool i8_alone = (i8_flags & (i8_flags - 1)) == 0;
+  const bool i8f_ok = i8f && i8_alone && exact && (i8c ? (C == 128 && Cb == 64) : (C == 256 && Cb == 128)) && wf.btype == 0 &&
+                      wf.inner >= 1 && wf.inner <= 3;
+  const bool fused_shape = exact && ((C == 256 && Cb == 128) || (C == 128 && Cb == 64)) && bottleneck_ok;
+  const bool lw_shape = (exact && C == 384 && Cb == 192 && bottleneck_ok) || classic192;   // the templated k_lconv's shapes
+  // every other conv trunk of P3HIP_CONV_SET: layer-wise through conv_any.hip, C and Cb padded to multiples of 64
+  const bool any = !fused_shape && !lw_shape &&
+                   WeightFile::conv_set(wf.model_C, wf.model_Cb, wf.btype, wf.inner, wf.bint) && C % 64 == 0 &&
+                   (wf.btype == 2 || Cb % 64 == 0);
+  // (P3HIP_FLAG_FP32 runs the fused shapes layer by layer too)
+  const bool layerwise = lw_shape || i8f_ok || any || (f32 && fused_shape);
+  const bool v_ok = wf.V == 32 || wf.V == 48 || wf.V == 64 || wf.V == 80;
+  // transformer trunk: the file's C is the model width d and Cb the head count (include/p3hip.h: d a multiple of 32,
+  // 64 <= d <= 384, head width d / heads 32 or 64); the stream is padded to C = p3::tfm_stream_width(d), and V is what
+  // the heads of that width serve (the fused heads at C = 128 / 256: {32, 48, 64}; the C = 384 heads: v_ok)
+  const bool tfm = wf.btype == 3 && p3::tfm_supported(wf.model_C, Cb) && C == p3::tfm_stream_width(wf.model_C) &&
+                   (C == 384 || p3::heads_fusable(C, wf.V));
+  // (a trunk the fp16 engine serves and INT8_FUSED does not is refused below, with INT8_FUSED's own message)
+  const bool arch_ok = (fused && bottleneck_ok) || layerwise || tfm ||
+                       (i8f && fused_shape);
+  if (!arch_ok || wf.H != 32 || !v_ok) {
+    err = "unsupported architecture for the HIP engine (need a conv trunk (" P3HIP_CONV_SET "), or a transformer "
+          "trunk (" P3HIP_TRANSFORMER_SET "); H=32, V in {32,48,64,80} (transformer: V in {32,48,64}, and 80 at "
+          "d > 256))";
+    return c;
+  }
+  // (INT8_C128 answers every trunk it does not serve with its own message, the runtime-width conv trunks included)
+  if (i8c && !i8f_ok) {
+    err = "INT8_C128 is available only for C = 128 / C_b = 64 trunks of btl blocks with 1, 2 or 3 inner layers "
+          "(b12c128btl3, b10c128btl3, small and their kin, broadcast blocks at any interval), and not together with "
+          "another INT8 flag; nbt trunks, the other widths (P3HIP_FLAG_INT8_FUSED serves C = 256 / C_b = 128 btl trunks, "
+          "P3HIP_FLAG_INT8 the layer-wise trunks) and the transformer are not served";
+    return c;
+  }
+  if (any && int8) {
+    err = std::string(i8f ? "INT8_FUSED" : "INT8") + " is not available for this conv trunk: "
+          "P3HIP_FLAG_INT8 serves C = 384 / C_b = 192 btl or nbt blocks and C = 192 classic blocks, P3HIP_FLAG_INT8_FUSED "
+          "serves C = 256 / C_b = 128 btl blocks with 1, 2 or 3 inner layers, P3HIP_FLAG_INT8_C128 serves C = 128 / "
+          "C_b = 64 btl blocks with 1, 2 or 3 inner layers; the other widths run in fp16 only";
+    return c;
+  }
+  if (i8f && !i8f_ok) {
+    err = "INT8_FUSED is available only for C = 256 / C_b = 128 trunks of btl blocks with 1, 2 or 3 inner layers "
+          "(b12c256btl3 and its kin, broadcast blocks at any interval), and not together with P3HIP_FLAG_INT8; nbt and "
+          "C = 128 trunks, the layer-wise trunks (P3HIP_FLAG_INT8 serves those) and the transformer are not served";
+    return c;
+  }
+  if (int8 && !layerwise) {
+    err = "INT8 is available only for layer-wise trunks (C = 384 / C_b = 192 btl or nbt blocks, C = 192 classic "
+          "blocks); this trunk runs fused block kernels or the transformer";
+    return c;
+  }
+  // What is left is served.  (An INT8 flag left here has a layer-wise trunk that is not `any`; fp32 conv trunks are all
+  // layer-wise; k_blockw serves C = 256 / C_b = 128 btl trunks, whose inner count bottleneck_ok has checked.)
+  if (tfm) c.path = f32 ? Path::TfmF32 : Path::Tfm;
+  else if (f32) c.path = Path::F32Conv;
+  else if (i8f) c.path = i8c ? Path::Int8Fused128 : Path::Int8Fused256;
+  else if (int8) c.path = Path::Int8;
+  else if (any || (opt.conv_any && lw_shape)) c.path = Path::ConvAny;
+  else if (lw_shape) c.path = Path::Layerwise;
+  else c.path = (opt.blockw && C == 256 && Cb == 128 && wf.btype == 0) ? Path::Blockw : Path::Fused;
+  // (layer-wise: p3::conv_any_slice(C) = 64 at classic C = 192 and at INT8_C128's C = 128, 128 at C = 384 and at
+  // INT8_FUSED's C = 256)
+  c.CB = layerwise ? p3::conv_any_slice(C) : (tfm ? 128 : Cb);
+  c.CPI = layerwise ? p3::conv_any_init_pass(C) : 128;
+  c.heads_image = !f32 && p3::heads_fusable(C, wf.V);
+  c.heads_fused = c.heads_image && opt.heads_fuse && c.path != Path::ConvAny;
+  if (tfm) {
+    c.tfm_heads = Cb;
+    c.tfm_D = wf.model_C / Cb;
+  }
+  return c;
+}
+
+const HeadTensor kHeadTensors[kNumHeadTensors] = {
+    {"policy.gpool_dense.w", &p3::HeadsArgs::gd_w, 2 * 32 * 32, 0, 0},
+    {"policy.gpool_dense.b", &p3::HeadsArgs::gd_b, 32, 0, 12},
+    {"policy.out_moves.w", &p3::HeadsArgs::moves_w, 2 * 32, 0, 9},
+    {"policy.out_pass.w", &p3::HeadsArgs::pass_w, 4 * 32, 0, 7},
+    {"policy.out_pass.b", &p3::HeadsArgs::pass_b, 2, 0, -1},
+    {"policy.opt_moves.w", &p3::HeadsArgs::opt_moves_w, 32, 0, 10},
+    {"policy.opt_pass.w", &p3::HeadsArgs::opt_pass_w, 2 * 32, 0, 8},
+    {"policy.opt_pass.b", &p3::HeadsArgs::opt_pass_b, 1, 0, -1},
+    {"value.oq_embed.w", &p3::HeadsArgs::oq_embed_w, 0, 2 * 32, 1},
+    {"value.oq_embed.b", &p3::HeadsArgs::oq_embed_b, 0, 1, 13},
+    {"value.oq_out.w", &p3::HeadsArgs::oq_out_w, 0, 14, 4},
+    {"value.oq_out.b", &p3::HeadsArgs::oq_out_b, 14, 0, 16},
+    {"value.own.w", &p3::HeadsArgs::own_w, 32, 0, 11},
+    {"value.gamma_pre.w", &p3::HeadsArgs::gamma_pre_w, 0, 2 * 32, 2},
+    {"value.gamma_pre.b", &p3::HeadsArgs::gamma_pre_b, 0, 1, 14},
+    {"value.gamma_out.w", &p3::HeadsArgs::gamma_out_w, 0, 1, 5},
+    {"value.gamma_out.b", &p3::HeadsArgs::gamma_out_b, 1, 0, -1},
+    {"value.score_pre.w", &p3::HeadsArgs::score_pre_w, 0, 2 * 32 + 1, 3},
+    {"value.score_pre.b", &p3::HeadsArgs::score_pre_b, 0, 1, 15},
+    {"value.score_out.w", &p3::HeadsArgs::score_out_w, 0, 1, 6},
+    {"value.score_out.b", &p3::HeadsArgs::score_out_b, 1, 0, -1}};
+
+namespace {
+
+constexpr float kBnEps = 1e-3f;  // model.py:231
+
+// k16 blocks [h(2)][CP couts][8] fp16 in (tap major, channel-pair minor) order; see
+// conv_segment in conv_core.h.  W is HWIO flattened as [taps][cin_total][cout_total].
+void pack_segment(std::vector<_Float16>& dst, const float* W, int taps, int ntaps_pad,
+                  int cin_total, int cout_total, int cin0, int CB, int cout0, int CP) {
+  for (int tap = 0; tap < ntaps_pad; ++tap)
+    for (int q = 0; q < CB / 16; ++q)
+      for (int h = 0; h < 2; ++h)
+        for (int co = 0; co < CP; ++co)
+          for (int e = 0; e < 8; ++e) {
+            int ci = cin0 + q * 16 + h * 8 + e, c = cout0 + co;
+            float v = 0.0f;
+            if (tap < taps && ci < cin_total && c < cout_total)
+              v = W[((size_t)tap * cin_total + ci) * cout_total + c];
+            dst.push_back((_Float16)v);
+          }
+}
+
+// 3x3 weights of the fused block kernel: k16 blocks in (kernel row, k32 index, kernel column)
+// order — the three taps of a kernel row share their activation fragments (conv16.h
+// conv_segment16_3x3), so a step advances the column before the channel slice.
+void pack_segment_3x3(std::vector<_Float16>& dst, const float* W, int cin_total, int cout_total, int CB, int CP) {
+  for (int ky = 0; ky < 3; ++ky)
+    for (int q32 = 0; q32 < CB / 32; ++q32)
+      for (int kx = 0; kx < 3; ++kx)
+        for (int q = 2 * q32; q < 2 * q32 + 2; ++q)
+          for (int h = 0; h < 2; ++h)
+            for (int co = 0; co < CP; ++co)
+              for (int e = 0; e < 8; ++e) {
+                const int ci = q * 16 + h * 8 + e, tap = ky * 3 + kx;
+                float v = 0.0f;
+                if (ci < cin_total && co < cout_total) v = W[((size_t)tap * cin_total + ci) * cout_total + co];
+                dst.push_back((_Float16)v);
+              }
+}
+
+// k_blockw's weight granule (csrc/asm/blockw_gen.py): 64 output channels x 32 input channels of one tap as four
+// MFMA 32x32x16 A fragments, [k16 half j][cout tile c][h][n][8] = W[tap][k0 + 16 j + 8 h + e][cout0 + 32 c + n]: lane
+// (n, h) of fragment (j, c) reads its 16 bytes at (2 j + c) * 1024 + lane * 16.  scale (may be null): the folded BN scale
+// of the layer that FOLLOWS the conv, times log2(e), per output channel — multiplied in before the one fp16 rounding.
+void pack_granule(std::vector<_Float16>& dst, const float* W, int cin_total, int cout_total, int tap, int k0, int cout0,
+                  const float* scale) {
+  for (int j = 0; j < 2; ++j)
+    for (int c = 0; c < 2; ++c)
+      for (int h = 0; h < 2; ++h)
+        for (int n = 0; n < 32; ++n)
+          for (int el = 0; el < 8; ++el) {
+            const int co = cout0 + 32 * c + n;
+            float v = W[((size_t)tap * cin_total + k0 + 16 * j + 8 * h + el) * cout_total + co];
+            if (scale) v *= scale[co];
+            dst.push_back((_Float16)v);
+          }
+}
+// A Keras (in, out) matrix W[K][N] as MFMA 16x16x32 A fragments [N / 16][K / 32][64 lanes][8] (transformer.h).
+// `col0` / `ld`: the matrix is columns col0 .. col0 + N of a row-major [K][ld] tensor.
+void pack_afrag(std::vector<_Float16>& dst, const float* W, int K, int N, int ld, int col0) {
+  for (int ct = 0; ct < N / 16; ++ct)
+    for (int st = 0; st < K / 32; ++st)
+      for (int lane = 0; lane < 64; ++lane)
+        for (int el = 0; el < 8; ++el)
+          dst.push_back((_Float16)W[(size_t)(32 * st + 8 * (lane >> 4) + el) * ld + col0 + 16 * ct + (lane & 15)]);
+}
+FoldedBN fold_bn(Arena& ar, const WeightFile& wf, const std::string& prefix, size_t n) {
+  const Tensor& g = wf.get(prefix + ".gamma", n);
+  const Tensor& b = wf.get(prefix + ".beta", n);
+  const Tensor& m = wf.get(prefix + ".mean", n);
+  const Tensor& v = wf.get(prefix + ".var", n);
+  std::vector<float> sc(n), sh(n);
+  for (size_t i = 0; i < n; ++i) {
+    sc[i] = g.data[i] / std::sqrt(v.data[i] + kBnEps);
+    sh[i] = b.data[i] - m.data[i] * sc[i];
+  }
+  FoldedBN f;
+  f.scale_off = ar.add(sc.data(), n * 4);
+  f.shift_off = ar.add(sh.data(), n * 4);
+  return f;
+}
+
+// A stream is a whole number of macro-steps of 4 k16 blocks = cout_pass * 128 bytes
+// (conv_core.h ring_slot_bytes).
+// A stream that is not a whole number of macro-steps is a packing bug: it is reported through
+// Arena::bad_stream and fails p3hip_create (never abort() inside the library).
+size_t add_stream(Arena& ar, const std::vector<_Float16>& s, int& nms, int cout_pass) {
+  const size_t ms = (size_t)cout_pass * 128;
+  if (s.size() * 2 % ms != 0) ar.bad_stream = true;
+  nms = (int)(s.size() * 2 / ms);
+  return ar.add(s.data(), s.size() * 2);
+}
+
+// The broadcast dense matrix dw [361 i][361 j] as k16 blocks [j pass (3)][q (24)][h][128 j][8], K index r = 16 q + 8 h + e
+// a board row of `row_stride` points: 19, r = the point i itself; 20, r = the act buffer's padded board row 20 y + x
+// (zero rows for x = 19 and r >= 379), k_block's tail_dense.
+void pack_dense(std::vector<_Float16>& dst, const float* dw, int row_stride) {
+  for (int jp = 0; jp < 3; ++jp)
+    for (int q = 0; q < 24; ++q)
+      for (int h = 0; h < 2; ++h)
+        for (int jj = 0; jj < 128; ++jj)
+          for (int el = 0; el < 8; ++el) {
+            const int r = q * 16 + h * 8 + el, y = r / row_stride, x = r % row_stride, j = jp * 128 + jj;
+            const bool on_board = x < 19 && y < 19;
+            float v = (on_board && j < kNLoc) ? dw[(size_t)(y * 19 + x) * kNLoc + j] : 0.0f;
+            dst.push_back((_Float16)v);
+          }
+}
+
+// conv j of block i, checked against the [k][k][cin][cout] size the packer will read
+const float* conv_w(const WeightFile& wf, int i, int j, int kw, int cin, int cout) {
+  return wf.get("blocks." + std::to_string(i) + ".conv" + std::to_string(j) + ".w", (size_t)kw * kw * cin * cout).data;
+}
+
+// A run of consecutive fused blocks with the broadcast convs that ride at its ends.  The weight streams of a run go
+// into the arena back to back, after the run's other tensors: one k_block launch walks the streams of all its blocks
+// as ONE circular stream (position-major order, kernels.hip), so a run must be contiguous.  With the broadcast 1x1
+// convs fused in, a run's stream is [conv_last of the broadcast block before it] [its blocks] [conv_first of the
+// broadcast block after it].
+struct Run {
+  std::vector<_Float16> head, tail;
+  std::vector<std::pair<size_t, std::vector<_Float16>>> blocks;   // (plan index, stream)
+  int head_of = -1, tail_of = -1;
+};
+
+// What the packers share while build_plan walks the blocks
+struct Builder {
+  const WeightFile& wf;
+  const Options& opt;
+  Plan& plan;
+  Arena& ar;
+  bool have_xa = false;   // layer-wise path: u holds mish(bn0(x)) of the next block
+  Run cur;                // the run being collected
+  std::vector<Run> runs;  // laid out after the blocks, all runs back to back (lay_out_runs)
+  void flush_run() {
+    if (!cur.blocks.empty()) runs.push_back(std::move(cur));
+    cur = Run{};
+  }
+};
+
+void pack_stem(Builder& b) {
+  const WeightFile& wf = b.wf;
+  const int C = wf.C, CPI = b.plan.choice.CPI;
+  const Tensor& w = wf.get("init_conv.w", (size_t)25 * 15 * C);  // [5][5][15][C]
+  if (is_f32(b.plan.choice.path)) {
+    std::vector<float> s32;
+    p3::pack_conv_f32(s32, w.data, 25, 15, C, 16, C);
+    b.plan.init_w32_off = b.ar.add(s32.data(), s32.size() * 4);
+  } else {
+    std::vector<_Float16> s;
+    for (int cp = 0; cp < C / CPI; ++cp)
+      pack_segment(s, w.data, 25, 28, 15, C, 0, 16, cp * CPI, CPI);
+    b.plan.init_stream_off = add_stream(b.ar, s, b.plan.init_nms, CPI);
+  }
+  b.plan.game_w_off = b.ar.add(wf.get("init_game.w", (size_t)8 * C).data, 8 * C * 4);
+  b.plan.game_b_off = b.ar.add(wf.get("init_game.b", (size_t)C).data, C * 4);
+}
+
+void pack_rope(Builder& b) {
+  const int D = b.plan.choice.tfm_D;
+  std::vector<double> cd(kNLoc * D), sd(kNLoc * D);
+  spiral_rope_table(D, cd.data(), sd.data());
+  const std::vector<float> cf(cd.begin(), cd.end()), sf(sd.begin(), sd.end());
+  b.plan.rope_cos_off = b.ar.add(cf.data(), cf.size() * 4);
+  b.plan.rope_sin_off = b.ar.add(sf.data(), sf.size() * 4);
+}
+
+// Transformer block i, its GEMM weights as fragments of element type T: pack_afrag (fp16) or, for TfmF32, the same
+// fragments in fp32 (transformer_f32.h pack_tfm_f32; no fp16 image then)
+template <class T, class Pack>
+void pack_tfm_block(Builder& b, int i, Pack pack) {
+  const std::string p = "blocks." + std::to_string(i);
+  const int c = b.wf.model_C, f = 2 * c;
+  auto W = [&](const char* n, size_t sz) { return b.wf.get(p + "." + n, sz).data; };
+  BlockPlan bp;
+  bp.kind = 5;
+  bp.tfm.rms_in = b.ar.add(W("rms_in.scale", c), c * 4);
+  bp.tfm.rms_out = b.ar.add(W("rms_out.scale", c), c * 4);
+  std::vector<T> w;
+  auto flush = [&] {
+    const size_t off = b.ar.add(w.data(), w.size() * sizeof(T));
+    w.clear();
+    return off;
+  };
+  for (const char* n : {"q.w", "k.w", "v.w"}) pack(w, W(n, (size_t)c * c), c, c, c, 0);
+  bp.tfm.wqkv = flush();
+  pack(w, W("o.w", (size_t)c * c), c, c, c, 0);
+  bp.tfm.wo = flush();
+  pack(w, W("ffn_gate.w", (size_t)c * f), c, f, f, 0);
+  pack(w, W("ffn_up.w", (size_t)c * f), c, f, f, 0);
+  bp.tfm.wgu = flush();
+  pack(w, W("ffn_down.w", (size_t)f * c), f, c, c, 0);
+  bp.tfm.wdown = flush();
+  b.plan.blocks.push_back(bp);
+}
+
+// Broadcast block i (kind 3).  On the Fused path the run before it takes conv_first (and at C = 256 btl the dense) as
+// its tail, the run after it conv_last as its head; the stand-alone streams serve every other path, P3HIP_NO_BFUSE and
+// broadcast blocks without a fused neighbour.
+void pack_broadcast_block(Builder& b, int i) {
+  const WeightFile& wf = b.wf;
+  Arena& ar = b.ar;
+  const int C = wf.C, Cb = wf.Cb, CB = b.plan.choice.CB;
+  const std::string p = "blocks." + std::to_string(i);
+  BlockPlan bp;
+  bp.kind = 3;
+  b.have_xa = false;
+  bp.bn[0] = fold_bn(ar, wf, p + ".bn0", C);
+  bp.bn[1] = fold_bn(ar, wf, p + ".bn1", C);
+  if (is_f32(b.plan.choice.path)) {
+    std::vector<float> w32;
+    p3::pack_conv_f32(w32, conv_w(wf, i, 0, 1, C, C), 1, C, C, C, C);
+    bp.w32_first = ar.add(w32.data(), w32.size() * 4);
+    w32.clear();
+    p3::pack_dense_f32(w32, wf.get(p + ".dense.w", (size_t)kNLoc * kNLoc).data);
+    bp.w32_dense = ar.add(w32.data(), w32.size() * 4);
+    w32.clear();
+    p3::pack_conv_f32(w32, conv_w(wf, i, 1, 1, C, C), 1, C, C, C, C);
+    bp.w32_last = ar.add(w32.data(), w32.size() * 4);
+    bp.dense_bias_off = ar.add(wf.get(p + ".dense.b", (size_t)kNLoc).data, kNLoc * 4);
+    b.plan.blocks.push_back(bp);
+    return;
+  }
+  const int CPb = (CB == 128) ? 128 : 64;
+  std::vector<_Float16> s0, s1, s2;
+  for (int cp = 0; cp < C / CPb; ++cp)
+    for (int ip = 0; ip < C / CB; ++ip) {
+      pack_segment(s0, conv_w(wf, i, 0, 1, C, C), 1, 1, C, C, ip * CB, CB, cp * CPb, CPb);
+      pack_segment(s2, conv_w(wf, i, 1, 1, C, C), 1, 1, C, C, ip * CB, CB, cp * CPb, CPb);
+    }
+  const Tensor& dw = wf.get(p + ".dense.w", (size_t)kNLoc * kNLoc);  // [361 i][361 j]
+  pack_dense(s1, dw.data, 19);
+  // (k_blockw's trunks run their broadcast blocks as their own launches)
+  const bool fused_neighbours = b.plan.choice.path == Path::Fused && b.opt.bcast_fuse;
+  // fused copies: output pass 1 takes its K slices in the order (1, 0) — slice 1 is the one
+  // still in the act buffer when pass 0 ends (kernels.hip k_block, BC form)
+  std::vector<_Float16> f0, f2;
+  if (fused_neighbours)
+    for (int cp = 0; cp < 2; ++cp)
+      for (int k = 0; k < 2; ++k) {
+        const int ip = cp == 0 ? k : 1 - k;
+        pack_segment(f0, conv_w(wf, i, 0, 1, C, C), 1, 1, C, C, ip * Cb, Cb, cp * Cb, Cb);
+        pack_segment(f2, conv_w(wf, i, 1, 1, C, C), 1, 1, C, C, ip * Cb, Cb, cp * Cb, Cb);
+      }
+  if (fused_neighbours && !b.cur.blocks.empty()) {
+    b.cur.tail = f0;
+    b.cur.tail_of = i;
+    bp.first_fused = true;
+    // C = 256: the dense rides in that tail too (k_block, tail_dense).  Its stream there:
+    // [conv_first pass 0 (K slices 0, 1)] [dense] [conv_first pass 1 (K slices 0, 1)] [dense], the dense matrix
+    // with its K index = the act buffer's padded board row
+    if (C == 256 && Cb == 128 && wf.btype == 0 && b.opt.dense_fuse) {   // btl blocks only (k_block's tail_dense)
+      bp.dense_fused = true;
+      std::vector<_Float16> dpad;
+      pack_dense(dpad, dw.data, 20);
+      b.cur.tail.clear();
+      for (int cp = 0; cp < 2; ++cp) {
+        for (int ip = 0; ip < 2; ++ip) pack_segment(b.cur.tail, conv_w(wf, i, 0, 1, C, C), 1, 1, C, C, ip * Cb, Cb, cp * Cb, Cb);
+        b.cur.tail.insert(b.cur.tail.end(), dpad.begin(), dpad.end());
+      }
+    }
+  }
+  b.flush_run();
+  if (fused_neighbours && i + 1 < wf.nblocks && !wf.is_broadcast(i + 1)) {
+    b.cur.head = f2;
+    b.cur.head_of = i;   // last_fused is set when the run is laid out
+  }
+  bp.stream_off = add_stream(ar, s0, bp.nms, CPb);
+  bp.stream2_off = add_stream(ar, s1, bp.nms2, 128);
+  bp.stream3_off = add_stream(ar, s2, bp.nms3, CPb);
+  bp.dense_bias_off = ar.add(wf.get(p + ".dense.b", (size_t)kNLoc).data, kNLoc * 4);
+  b.plan.blocks.push_back(bp);
+}
+
+// Layer-wise block i (kind 4): one LayerPlan per conv, with its fp16 stream, or its fp32 image (F32Conv), and on the
+// INT8 paths the quantized weights as well (the fp16 streams are what the calibration runs)
+void pack_layerwise_block(Builder& b, int i) {
+  const WeightFile& wf = b.wf;
+  Arena& ar = b.ar;
+  const Path path = b.plan.choice.path;
+  const int C = wf.C, Cb = wf.Cb;
+  const bool classic = wf.btype == 2;
+  const std::string p = "blocks." + std::to_string(i);
+  BlockPlan bp;
+  bp.kind = 4;
+  const int nconv = classic ? 2 : ((wf.btype == 0) ? wf.inner + 2 : 6);
+  for (int j = 0; j < nconv; ++j) bp.bn[j] = fold_bn(ar, wf, p + ".bn" + std::to_string(j), (classic || j == 0) ? C : Cb);
+  // The consumer's prologue (BN + mish of its input) is applied ONCE by the producer: a
+  // layer either stores its output already activated for the next conv (act), or stores it
+  // raw and a second, activated copy (dual).  Only the first layer after the init conv or
+  // a broadcast block still activates its input while staging (pre) — every workgroup of
+  // an output pass would otherwise redo that VALU work.  `xa` = activated copy of x, in u.
+  FoldedBN next_bn0{};
+  // (an INT8_FUSED block depends on the stored x alone: every block's first conv activates it, pre)
+  const bool next_layerwise = !is_int8_fused(path) && i + 1 < wf.nblocks && !wf.is_broadcast(i + 1);
+  if (next_layerwise) next_bn0 = fold_bn(ar, wf, "blocks." + std::to_string(i + 1) + ".bn0", C);
+  const FoldedBN none{};
+  auto add_layer = [&](int j, int kw, int cin, int cout, bool pre, const FoldedBN& pre_bn, bool act, bool res,
+                       bool dual, const FoldedBN& out_bn, int in_buf, int out_buf, int out2_buf) {
+    LayerPlan lp{kw, cin, cout, pre, act, res, dual, pre_bn, out_bn, in_buf, out_buf, out2_buf};
+    if (is_f32(path)) {
+      std::vector<float> w32;
+      p3::pack_conv_f32(w32, conv_w(wf, i, j, kw, cin, cout), kw * kw, cin, cout, cin, cout);
+      lp.w32_off = ar.add(w32.data(), w32.size() * 4);
+    } else {
+      std::vector<_Float16> s;
+      for (int cp = 0; cp < cout / 64; ++cp)
+        for (int ip = 0; ip < cin / 64; ++ip)
+          pack_segment(s, conv_w(wf, i, j, kw, cin, cout), kw * kw, kw * kw, cin, cout, ip * 64, 64, cp * 64, 64);
+      lp.stream_off = add_stream(ar, s, lp.nms, 64);
+    }
+    if (is_int8(path)) {
+      std::vector<int8_t> q;
+      std::vector<float> sw;
+      p3::pack_lconv_i8(q, sw, conv_w(wf, i, j, kw, cin, cout), kw * kw, cin, cout);
+      lp.q_off = ar.add(q.data(), q.size());
+      lp.qs_off = ar.add(sw.data(), sw.size() * 4);
+      lp.qidx = b.plan.n_q++;
+    }
+    bp.layers.push_back(lp);
+  };
+  const bool from_xa = b.have_xa;          // first layer input: activated copy in u, or raw x with pre
+  const int in0 = from_xa ? 3 : 0;
+  if (classic) {         // x + conv3(act1(conv3(act0(x)))), model.py:330-368
+    add_layer(0, 3, C, C, !from_xa, bp.bn[0], true, false, false, bp.bn[1], in0, 1, -1);
+    add_layer(1, 3, C, C, false, none, false, true, next_layerwise, next_bn0, 1, 0, 3);
+  } else if (wf.btype == 0) {   // btl
+    add_layer(0, 1, C, Cb, !from_xa, bp.bn[0], true, false, false, bp.bn[1], in0, 1, -1);
+    int cur = 1;
+    for (int j = 1; j <= wf.inner; ++j) {
+      add_layer(j, 3, Cb, Cb, false, none, true, false, false, bp.bn[j + 1], cur, 3 - cur, -1);
+      cur = 3 - cur;
+    }
+    add_layer(wf.inner + 1, 1, Cb, C, false, none, false, true, next_layerwise, next_bn0, cur, 0, 3);
+  } else {               // nbt: the inner residual stream t stays raw in region 1
+    add_layer(0, 1, C, Cb, !from_xa, bp.bn[0], false, false, true, bp.bn[1], in0, 1, 2);   // t, act1(t)
+    add_layer(1, 3, Cb, Cb, false, none, true, false, false, bp.bn[2], 2, 3, -1);
+    add_layer(2, 3, Cb, Cb, false, none, false, true, true, bp.bn[3], 3, 1, 2);             // t' = t + ., act3(t')
+    add_layer(3, 3, Cb, Cb, false, none, true, false, false, bp.bn[4], 2, 3, -1);
+    add_layer(4, 3, Cb, Cb, false, none, false, true, true, bp.bn[5], 3, 1, 2);             // t'', act5(t'')
+    add_layer(5, 1, Cb, C, false, none, false, true, next_layerwise, next_bn0, 2, 0, 3);
+  }
+  b.have_xa = next_layerwise;
+  b.plan.blocks.push_back(bp);
+}
+
+// Fused block i (kind 0 btl, 1 nbt): its stream joins the run being collected
+void pack_fused_block(Builder& b, int i) {
+  const WeightFile& wf = b.wf;
+  const int C = wf.C, Cb = wf.Cb, CB = b.plan.choice.CB;
+  const std::string p = "blocks." + std::to_string(i);
+  BlockPlan bp;
+  bp.kind = wf.btype;
+  const int nconv = (wf.btype == 0) ? wf.inner + 2 : 6;
+  for (int j = 0; j < nconv; ++j) bp.bn[j] = fold_bn(b.ar, wf, p + ".bn" + std::to_string(j), j == 0 ? C : Cb);
+  std::vector<_Float16> s;
+  for (int ip = 0; ip < C / CB; ++ip) pack_segment(s, conv_w(wf, i, 0, 1, C, Cb), 1, 1, C, Cb, ip * CB, CB, 0, CB);
+  for (int j = 1; j < nconv - 1; ++j) pack_segment_3x3(s, conv_w(wf, i, j, 3, Cb, Cb), Cb, Cb, CB, CB);
+  for (int cp = 0; cp < C / CB; ++cp) pack_segment(s, conv_w(wf, i, nconv - 1, 1, Cb, C), 1, 1, Cb, C, 0, CB, cp * CB, CB);
+  b.cur.blocks.emplace_back(b.plan.blocks.size(), std::move(s));
+  b.plan.blocks.push_back(bp);
+}
+
+// The runs' streams, all runs back to back ([head r][blocks r][tail r][head r + 1] ...): with everything of the
+// broadcast blocks between them fused, one k_block launch walks them all (forward.cpp joined_launch).
+void lay_out_runs(Builder& b) {
+  std::vector<BlockPlan>& blocks = b.plan.blocks;
+  const int Cb = b.wf.Cb;
+  int nms_unused = 0;
+  for (const Run& r : b.runs) {
+    if (r.head_of >= 0) {
+      add_stream(b.ar, r.head, nms_unused, Cb);
+      BlockPlan& fb = blocks[r.blocks.front().first];
+      fb.head_of = r.head_of;
+      fb.head_bytes = r.head.size() * 2;
+      blocks[r.head_of].last_fused = true;
+    }
+    for (const auto& rs : r.blocks) {
+      BlockPlan& bp = blocks[rs.first];
+      bp.stream_off = add_stream(b.ar, rs.second, bp.nms, Cb);
+      bp.stream_bytes = rs.second.size() * 2;
+    }
+    if (r.tail_of >= 0) {
+      add_stream(b.ar, r.tail, nms_unused, Cb);
+      BlockPlan& lb = blocks[r.blocks.back().first];
+      lb.tail_of = r.tail_of;
+      lb.tail_bytes = r.tail.size() * 2;
+    }
+  }
+}
+
+// k_blockw: per run of consecutive btl blocks, the weight stream in the order the kernel consumes it and the parameter
+// table.  The BN in front of a conv's consumer rides in the conv: its folded scale times log2(e) is multiplied into
+// the fp16 weights, its shift times log2(e) is the accumulators' initial value (the kernel's exp2-based mish takes
+// log2(e) * y, as bn_mish8_l2 does).
+//   block stream: reduce: x halves (quarters 0, 1 / 2, 3); in a half set A's four k32 granules, then set B's
+//                 layer j: phases (A, lo) (B, lo) (A, hi) (B, hi), each (ky, q32, kx) over its 64 input channels
+//                 expand: output quarters 0..3, k32 steps 0..3 (unscaled: the residual add follows)
+//   block table:  bn0 scale[256] shift[256] (times log2 e) | conv j = 0 .. L: shift[128] of bn j + 1 (times log2 e)
+void pack_blockw_runs(Builder& b) {
+  const WeightFile& wf = b.wf;
+  Arena& ar = b.ar;
+  std::vector<BlockPlan>& blocks = b.plan.blocks;
+  const int C = wf.C, Cb = wf.Cb, L = wf.inner;
+  const float kLog2e = 1.4426950408889634f;
+  for (size_t bi = 0; bi < blocks.size();) {
+    if (blocks[bi].kind != 0) { ++bi; continue; }
+    size_t n = 1;
+    while (bi + n < blocks.size() && blocks[bi + n].kind == 0) ++n;
+    std::vector<_Float16> ws;
+    std::vector<float> prm;
+    for (size_t k = bi; k < bi + n; ++k) {
+      // block index in the weight file = plan index (one BlockPlan per trunk block)
+      const int i = (int)k;
+      const BlockPlan& bp = blocks[k];
+      auto bn_row = [&](int j, bool shift) {
+        const float* v = reinterpret_cast<const float*>(ar.host.data() + (shift ? bp.bn[j].shift_off : bp.bn[j].scale_off));
+        std::vector<float> r((size_t)(j == 0 ? C : Cb));
+        for (size_t c = 0; c < r.size(); ++c) r[c] = v[c] * kLog2e;
+        return r;
+      };
+      const float* w0 = conv_w(wf, i, 0, 1, C, Cb);
+      const std::vector<float> s1 = bn_row(1, false);
+      for (int half = 0; half < 2; ++half)
+        for (int s0 = 0; s0 < 128; s0 += 64)
+          for (int st = 0; st < 4; ++st) pack_granule(ws, w0, C, Cb, 0, 128 * half + 32 * st, s0, s1.data());
+      for (int j = 1; j <= L; ++j) {
+        const float* wj = conv_w(wf, i, j, 3, Cb, Cb);
+        const std::vector<float> sj = bn_row(j + 1, false);
+        for (int ph = 0; ph < 4; ++ph) {
+          const int s0 = (ph & 1) * 64, half = ph >> 1;
+          for (int ky = 0; ky < 3; ++ky)
+            for (int q = 0; q < 2; ++q)
+              for (int kx = 0; kx < 3; ++kx) pack_granule(ws, wj, Cb, Cb, ky * 3 + kx, 64 * half + 32 * q, s0, sj.data());
+        }
+      }
+      const float* we = conv_w(wf, i, L + 1, 1, Cb, C);
+      for (int qo = 0; qo < 4; ++qo)
+        for (int c = 0; c < 4; ++c) pack_granule(ws, we, Cb, C, 0, 32 * c, 64 * qo, nullptr);
+      for (int sh = 0; sh < 2; ++sh) {
+        const std::vector<float> r = bn_row(0, sh == 1);
+        prm.insert(prm.end(), r.begin(), r.end());
+      }
+      for (int j = 1; j <= L + 1; ++j) {
+        const std::vector<float> r = bn_row(j, true);
+        prm.insert(prm.end(), r.begin(), r.end());
+      }
+    }
+    BlockwRun run;
+    run.first = bi;
+    run.nblk = (int)n;
+    run.stream_off = ar.add(ws.data(), ws.size() * 2);
+    run.prm_off = ar.add(prm.data(), prm.size() * 4);
+    if (ws.size() * 2 != n * (size_t)(32 + 72 * L) * 4096 || prm.size() != n * (size_t)(512 + 128 * (L + 1))) ar.bad_stream = true;
+    blocks[bi].bw_run = (int)b.plan.bw_runs.size();
+    b.plan.bw_runs.push_back(run);
+    bi += n;
+  }
+}
+
+// heads: conv_p | conv_g | value.conv -> [C][96], then the small tensors of kHeadTensors
+bool pack_heads(Builder& b, std::string& err) {
+  const WeightFile& wf = b.wf;
+  Arena& ar = b.ar;
+  Plan& plan = b.plan;
+  const int C = wf.C, CB = plan.choice.CB;
+  std::vector<float> w((size_t)C * 96);
+  const float* wp = wf.get("policy.conv_p.w", (size_t)C * 32).data;
+  const float* wg = wf.get("policy.conv_g.w", (size_t)C * 32).data;
+  const float* wv = wf.get("value.conv.w", (size_t)C * 32).data;
+  for (int c = 0; c < C; ++c)
+    for (int o = 0; o < 32; ++o) {
+      w[(size_t)c * 96 + o] = wp[c * 32 + o];
+      w[(size_t)c * 96 + 32 + o] = wg[c * 32 + o];
+      w[(size_t)c * 96 + 64 + o] = wv[c * 32 + o];
+    }
+  if (is_f32(plan.choice.path)) {
+    std::vector<float> w32;
+    p3::pack_conv_f32(w32, w.data(), 1, C, 96, C, 128);
+    plan.heads_w32_off = ar.add(w32.data(), w32.size() * 4);
+  } else {
+    std::vector<_Float16> s;
+    for (int cp = 0; cp < 2; ++cp)
+      for (int ip = 0; ip < C / CB; ++ip) pack_segment(s, w.data(), 1, 1, C, 96, ip * CB, CB, cp * 64, 64);
+    plan.heads_stream_off = add_stream(ar, s, plan.heads_nms, 64);
+  }
+  // the same weights as MFMA 16x16x32 A fragments for k_headsx (the convs inside the heads kernel):
+  // [cout tile ct][k32 step][lane (n = lane & 15, q = lane >> 4)][8] = w[cin = 32 step + 8 q + e][cout = 16 ct + n]
+  if (plan.choice.heads_image) {
+    std::vector<_Float16> af;
+    pack_afrag(af, w.data(), C, 96, 96, 0);
+    plan.heads_conv_a_off = ar.add(af.data(), af.size() * 2);
+  }
+  plan.heads_gbn = fold_bn(ar, wf, "policy.gpool_bn", 32);
+  const float* data[kNumHeadTensors];
+  size_t size[kNumHeadTensors];
+  for (int k = 0; k < kNumHeadTensors; ++k) {   // sizes k_heads reads (kernels.h HeadsArgs)
+    size[k] = (size_t)kHeadTensors[k].n0 + (size_t)kHeadTensors[k].nV * wf.V;
+    const Tensor& t = wf.get(kHeadTensors[k].name, size[k]);
+    data[k] = t.data;
+    plan.head_tensor_off[k] = ar.add(t.data, t.size() * 4);
+  }
+  // k_headsx takes the same tensors as one image in its LDS order (kernels.h heads_image_floats): the weights, the
+  // folded gpool BN, the biases, and two floats of padding behind oq_out.b
+  if (plan.choice.heads_image && wf.missing.empty()) {
+    std::vector<float> img;
+    for (int rank = 0; rank <= 16; ++rank) {
+      for (int k = 0; k < kNumHeadTensors; ++k)
+        if (kHeadTensors[k].image_rank == rank) img.insert(img.end(), data[k], data[k] + size[k]);
+      if (rank == 11)
+        for (size_t off : {plan.heads_gbn.scale_off, plan.heads_gbn.shift_off}) {
+          const float* bn = reinterpret_cast<const float*>(ar.host.data() + off);
+          img.insert(img.end(), bn, bn + 32);
+        }
+    }
+    img.insert(img.end(), 2, 0.0f);
+    if ((int)img.size() != p3::heads_image_floats(32, wf.V)) {
+      err = "internal error: heads image size";
+      return false;
+    }
+    plan.heads_image_off = ar.add(img.data(), img.size() * 4);
+  }
+  return true;
+}
+
+}  // namespace
+
+// The spiral RoPE tables of python/model_transformer.py spiral_rope_cos_sin_table(num_rotations = 4, embed_dim = D,
+// grid_len = 19), ROPE_THETA = 100, restated: [361 tokens][D] each, token s = 19 row + col (meshgrid indexing "ij":
+// the first coordinate is the row).  Channel i belongs to rotation partition k = i / per (direction k pi / 4), per = D / 4,
+// and takes the frequency theta^(-t / nth), nth = D / 4, t = min(nth - 1, 2 (k % 2) + 4 ((i % per) / 4) + (i % per) / 2 % 2):
+// both channels of a pair share it.  At D = 32: per = nth = 8.
+// Any head width D that is a multiple of 8 (the engine uses 32 and 64): per = nth = D / 4.
+void spiral_rope_table(int D, double* cos_out, double* sin_out) {
+  const int K = 4, per = D / K, nth = D / 4;
+  const double kPi = 3.14159265358979323846;
+  std::vector<double> theta(D);
+  for (int i = 0; i < D; ++i) {
+    const int k = i / per, r = (i % per) / 2;
+    int t = 2 * (k % (K / 2)) + (r / 2) * K + (r % 2);
+    if (t > nth - 1) t = nth - 1;
+    theta[i] = std::pow(100.0, -(double)t / nth);
+  }
+  for (int s = 0; s < kNLoc; ++s)
+    for (int i = 0; i < D; ++i) {
+      const double ang = (i / per) * (kPi / K);
+      const double proj = (s / 19) * std::cos(ang) + (s % 19) * std::sin(ang);
+      cos_out[s * D + i] = std::cos(theta[i] * proj);
+      sin_out[s * D + i] = std::sin(theta[i] * proj);
+    }
+}
+
+bool build_plan(const WeightFile& wf, uint32_t flags, const Options& opt, Plan& plan, Arena& ar, std::string& err) {
+  plan.choice = choose_plan(wf, flags, opt, err);
+  const Path path = plan.choice.path;
+  if (path == Path::Refused) return false;
+  Builder b{wf, opt, plan, ar};
+  pack_stem(b);
+  if (is_tfm(path)) pack_rope(b);
+  for (int i = 0; i < wf.nblocks; ++i) {
+    if (path == Path::Tfm) pack_tfm_block<_Float16>(b, i, pack_afrag);
+    else if (path == Path::TfmF32) pack_tfm_block<float>(b, i, p3::pack_tfm_f32);
+    else {
+      if (is_layerwise(path)) b.flush_run();
+      if (wf.is_broadcast(i)) pack_broadcast_block(b, i);
+      else if (is_layerwise(path)) pack_layerwise_block(b, i);
+      else pack_fused_block(b, i);
+    }
+  }
+  b.flush_run();
+  lay_out_runs(b);
+  if (path == Path::Blockw) pack_blockw_runs(b);
+  if (!pack_heads(b, err)) return false;
+  if (!wf.missing.empty()) {
+    err = "weight file lacks tensors of the architecture its header names: " + wf.missing;
+    return false;
+  }
+  if (ar.bad_stream) {
+    err = "internal error: a packed weight stream is not a whole number of ring macro-steps";
+    return false;
+  }
+  return true;
+}
+
+}  // namespace eng

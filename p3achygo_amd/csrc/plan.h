@@ -1,0 +1,168 @@
+// plan.h — the host-side plan of an engine: which trunk path it runs (choose_plan), and the weights of that path repacked
+// into one arena image with the offsets the forward pass needs (build_plan).  Nothing here calls the HIP runtime: a bad
+// file or a refused flag set fails before any device call, GPU or not.
+#pragma once
+
+#include <cstdint>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "kernels.h"
+#include "weights.h"
+
+namespace eng {
+
+constexpr int kNLoc = 361;
+
+// Every P3HIP_* environment switch of the engine, read once at the top of p3hip_create.
+struct Options {
+  bool c128_wg8 = false;   // P3HIP_C128_WG8: C = 128 blocks as one 8-wave workgroup per CU (A/B timing)
+  bool bcast_fuse = true;  // P3HIP_NO_BFUSE clears it: broadcast 1x1 convs as their own launches (A/B, tests)
+  bool dense_fuse = true;  // P3HIP_NO_DFUSE clears it: the broadcast dense as its own launch (k_bdense)
+  bool heads_fuse = true;  // P3HIP_NO_HFUSE clears it: the head convs as their own launch in front of k_heads
+  int stop_block = -1;     // P3HIP_DEBUG_STOP_BLOCK: the forward pass ends in front of plan block n (debugging, tests)
+  bool fuse = true, join = true;   // P3HIP_NO_FUSE clears both: one k_block launch per block; P3HIP_NO_JOIN join: one per run
+  int stagger = -1;        // P3HIP_STAGGER: block launches' start-up stagger in cycles (-1: the launch decides)
+  bool pair_turns = true;  // P3HIP_NO_PAIR_TURNS clears it: C = 128 workgroup pairs leave the wave priorities alone
+  bool direct_results = true;   // P3HIP_NO_DIRECT_RESULTS clears it: p3hip_run copies the results strided from d_out
+  bool time_run = false;   // P3HIP_TIME_RUN: p3hip_run times its stages (a measurement aid)
+  bool blockw = false;     // P3HIP_BLOCKW=1: C = 256 / C_b = 128 btl runs through k_blockw (csrc/asm/blockw_gen.py)
+  bool blockw_diag = false;   // P3HIP_BLOCKW_DIAG: the _diag twin, which writes the engine's d_bw_stamps
+  bool conv_any = false;   // P3HIP_CONV_ANY=1: the templated layer-wise shapes through conv_any.hip too
+  static Options from_env();
+};
+
+// The trunk path of an engine: the one decision the packers, the buffer sizing, the forward pass, the timing and the
+// debug read-backs switch on.
+enum class Path {
+  Refused,        // choose_plan filled the error text
+  Fused,          // k_block: btl and nbt at C = 256 / 128 and 128 / 64, broadcast convs and dense fused into the runs
+  Blockw,         // k_blockw runs (P3HIP_BLOCKW) at C = 256 / 128 btl; broadcast blocks as their own launches
+  Layerwise,      // templated k_lconv: C = 384 / C_b = 192 btl and nbt, classic C = 192
+  ConvAny,        // conv_any.hip, widths as launch arguments: every other trunk of P3HIP_CONV_SET (and P3HIP_CONV_ANY=1)
+  Int8,           // P3HIP_FLAG_INT8: k_lconv_i8 on the templated layer-wise shapes
+  Int8Fused256,   // P3HIP_FLAG_INT8_FUSED: k_block_i8 per btl block at C = 256 / C_b = 128
+  Int8Fused128,   // P3HIP_FLAG_INT8_C128: the same at C = 128 / C_b = 64 (block_i8_c128.hip)
+  F32Conv,        // P3HIP_FLAG_FP32: every conv trunk layer by layer through conv_f32.hip
+  Tfm,            // transformer trunk, fp16
+  TfmF32,         // P3HIP_FLAG_FP32_TFM: transformer trunk through transformer_f32.hip
+};
+inline bool is_tfm(Path p) { return p == Path::Tfm || p == Path::TfmF32; }
+inline bool is_f32(Path p) { return p == Path::F32Conv || p == Path::TfmF32; }
+inline bool is_int8_fused(Path p) { return p == Path::Int8Fused256 || p == Path::Int8Fused128; }
+// (an INT8 engine calibrates through the fp16 layer-wise plan: `calibrating` is a run-time state of the engine)
+inline bool is_int8(Path p) { return p == Path::Int8 || is_int8_fused(p); }
+// conv blocks planned conv by conv (BlockPlan kind 4)
+inline bool is_layerwise(Path p) { return p == Path::Layerwise || p == Path::ConvAny || is_int8(p) || p == Path::F32Conv; }
+inline size_t act_bytes(Path p) { return is_f32(p) ? 4 : 2; }   // bytes per activation element of d_x, d_t, d_u, d_qkv
+
+struct PlanChoice {
+  Path path = Path::Refused;
+  int CB = 0;    // slice width of the per-position kernels that stage C channels (k_conv1x1 family)
+  int CPI = 0;   // output pass width of the init conv
+  bool heads_image = false;   // the arena holds k_headsx's weight fragments and tensor image (C <= 256, fp16)
+  bool heads_fused = false;   // k_headsx runs: the head convs inside the heads kernel (P3HIP_NO_HFUSE, conv_any clear it)
+  int tfm_heads = 0, tfm_D = 0;   // transformer: head count and head width (model width wf.model_C = heads x D)
+};
+
+// Pure: every refusal of an engine's creation that depends on the file's architecture and the flags, in their order of
+// precedence, and the path of an engine that is served.
+PlanChoice choose_plan(const WeightFile& wf, uint32_t flags, const Options& opt, std::string& err);
+
+// ---- device arena -----------------------------------------------------------------
+struct Arena {
+  std::vector<unsigned char> host;
+  bool bad_stream = false;
+  size_t add(const void* p, size_t bytes) {
+    size_t off = (host.size() + 255) & ~size_t(255);
+    host.resize(off + bytes);
+    memcpy(host.data() + off, p, bytes);
+    return off;
+  }
+};
+
+struct FoldedBN { size_t scale_off, shift_off; };
+
+// One conv launch of a layer-wise block (kind 4).  Regions: 0 = x; 1, 2 = the two C_b-channel
+// halves of the scratch buffer t; 3, 4 = those of u (3 also names u as a whole C-channel buffer).
+struct LayerPlan {
+  int kw, cin, cout;
+  bool pre, act, res, dual;   // see p3::LConvArgs
+  FoldedBN pre_bn, out_bn;    // prologue / epilogue BN (epilogue: of act or of dual's second output)
+  int in_buf, out_buf, out2_buf;
+  size_t stream_off = 0;
+  int nms = 0;
+  // INT8 paths: the quantized weights (lconv_i8.h pack_lconv_i8), their per-output-channel scales, and the index of
+  // this layer's input among the engine's quantized tensors (its output, when quantized, is the next one: its consumer)
+  size_t q_off = 0, qs_off = 0;
+  int qidx = -1;
+  size_t w32_off = 0;   // F32Conv: the fp32 weight image (conv_f32.h pack_conv_f32)
+};
+
+// One transformer block (kind 5): arena offsets of its tensors, the GEMM weights as MFMA A fragments (transformer.h)
+struct TfmPlan { size_t rms_in = 0, rms_out = 0, wqkv = 0, wo = 0, wgu = 0, wdown = 0; };
+
+struct BlockPlan {
+  int kind;  // 0 btl, 1 nbt, 3 broadcast, 4 layer-wise, 5 transformer
+  TfmPlan tfm;
+  std::vector<LayerPlan> layers;
+  size_t stream_off = 0;
+  int nms = 0;
+  size_t stream_bytes = 0;   // fused blocks: the launch picks the macro-step size (kernels.h block_macro_step_bytes)
+  FoldedBN bn[p3::kMaxBlockLayers];
+  // broadcast extras
+  size_t stream2_off = 0, stream3_off = 0;
+  int nms2 = 0, nms3 = 0;
+  size_t dense_bias_off = 0;
+  size_t w32_first = 0, w32_dense = 0, w32_last = 0;   // F32Conv: conv_first, the dense, conv_last in fp32
+  // Broadcast 1x1 convs taken into the neighbouring block launches (k_block's BC form).
+  //   on a broadcast block: its conv_first runs at the tail of the launch before it / its conv_last
+  //   at the head of the launch after it;
+  //   on a fused block: the run's first block carries the head conv (head_of = that broadcast block,
+  //   its stream lies right before stream_off), the run's last block the tail conv (right after).
+  bool first_fused = false, last_fused = false;
+  bool dense_fused = false;   // C = 256: the dense runs in that tail as well (no k_bdense launch, t never stored)
+  int head_of = -1, tail_of = -1;
+  size_t head_bytes = 0, tail_bytes = 0;
+  int bw_run = -1;   // Blockw: the k_blockw run (Plan::bw_runs) that starts at this block
+};
+
+// The small tensors of the heads (kernels.h HeadsArgs), in the order they are uploaded to the arena.  The one table
+// serves the upload, the order of k_headsx's image and the HeadsArgs the engine fills once at create.
+struct HeadTensor {
+  const char* name;
+  const float* p3::HeadsArgs::*arg;
+  int n0, nV;       // floats: n0 + nV * V (the head width H is 32)
+  int image_rank;   // position in k_headsx's image (kernels.h heads_image_floats), -1: not in it
+};
+constexpr int kNumHeadTensors = 21;
+extern const HeadTensor kHeadTensors[kNumHeadTensors];
+
+// A run of k_blockw: consecutive btl blocks, their weight stream and parameter table
+struct BlockwRun { size_t first; int nblk; size_t stream_off, prm_off; };
+
+// What build_plan leaves for the engine: the path and arena offsets
+struct Plan {
+  PlanChoice choice;
+  std::vector<BlockPlan> blocks;
+  size_t init_stream_off = 0; int init_nms = 0;
+  size_t init_w32_off = 0;   // F32Conv, TfmF32: the init conv in fp32
+  size_t game_w_off = 0, game_b_off = 0;
+  size_t rope_cos_off = 0, rope_sin_off = 0;   // transformer
+  int n_q = 0;   // INT8 paths: quantized tensors (activation scales)
+  std::vector<BlockwRun> bw_runs;
+  size_t heads_stream_off = 0; int heads_nms = 0;
+  size_t heads_w32_off = 0;
+  size_t heads_conv_a_off = 0, heads_image_off = 0;
+  FoldedBN heads_gbn{};                     // policy.gpool_bn
+  size_t head_tensor_off[kNumHeadTensors] = {};   // by kHeadTensors index
+};
+
+// Packs the weights of `wf` for the path choose_plan picks into `ar` and fills `plan`.  The order of Arena::add calls is
+// part of the behaviour: joined launches rely on streams lying back to back.
+bool build_plan(const WeightFile& wf, uint32_t flags, const Options& opt, Plan& plan, Arena& ar, std::string& err);
+
+void spiral_rope_table(int D, double* cos_out, double* sin_out);
+
+}  // namespace eng

@@ -70,7 +70,7 @@ def outputs(cfg, W, pos, fp16):
 
 
 def pad_weights(cfg, W):
-    """(cfg, W) with C and C_b zero-padded to multiples of 64 by the engine's rule (engine.cpp WeightFile::pad_conv):
+    """(cfg, W) with C and C_b zero-padded to multiples of 64 by the engine's rule (weights.h WeightFile::pad_conv):
     zero conv rows and columns, zero stem weights and bias, BN gamma = beta = mean = var = 0"""
     import dataclasses
     from p3achygo_amd import netspec

@@ -32,7 +32,7 @@ import tfm_restatement  # noqa: E402
 DT = torch.float64
 FP16_WEIGHTS = ("init_conv.w", "policy.conv_p.w", "policy.conv_g.w", "value.conv.w")
 
-# the layer-wise trunks (engine.cpp build_plan: C = 384 / C_b = 192 btl or nbt, C = 192 classic)
+# the layer-wise trunks (plan.cpp choose_plan: C = 384 / C_b = 192 btl or nbt, C = 192 classic)
 LAYERWISE = ("test_b3c384btl3", "test_b3c384nbt", "test_b3c192classic", "b14c384btl3", "b10c384nbt", "b15c192_classic")
 
 

@@ -1,6 +1,6 @@
 """Results that do not depend on where a position lands in a batch, at the batch sizes where the launch geometry changes.
 
-The launchers switch forms on the batch size and the device's CU count n (csrc/kernels.hip, engine.cpp block_args):
+The launchers switch forms on the batch size and the device's CU count n (csrc/kernels.hip, forward.cpp block_args):
 k_block's grid cap (n workgroups for C = 256, 2n for C = 128), k_lconv's pair_split (grid > n), the start-up stagger
 (from 3n positions for C = 256, 6n for C = 128), the C = 128 pair turns (from 4n), grid_for's cap at n, and the ragged
 tails of k_heads (4 positions per workgroup) and k_headsx (2).  The sweep runs every trunk family on both sides of each

@@ -19,7 +19,7 @@ Modes (`Tfm(cfg, W, fp16=..., twin=...)`):
     torch.rsqrt and SiLU as x / (1 + exp(-x)) in fp32.  It is the benign stand-in for the GPU that sets BOUNDS.
 
 fp16 points, kernel by kernel (every accumulation is fp32 on the MFMAs; weights of the six GEMMs are fp16 A fragments,
-engine.cpp pack_afrag; the RMSNorm scales and the RoPE tables are fp32):
+plan.cpp pack_afrag; the RMSNorm scales and the RoPE tables are fp32):
   k_tfm_qkv   * the source rows are the stored fp16 x, widened to fp32; RMSNorm_in in fp32 (sum of squares, rsqrtf of
                 mean + 1e-6, times scale) and its result the fp16 LDS tile xs (rms_rows, `dst[..] = (_Float16)(..)`).
               * q, k, v = xs . [Wq | Wk | Wv] in fp32; RoPE on q and k in fp32 on the accumulators; one rounding at the
@@ -146,7 +146,7 @@ class Tfm:
         self.dt = torch.float32 if twin else F64
         self._stem = te.Trunk(cfg, W, fp16=self.fp16, twin=twin)
         cos, sin = tfm.rope_tables(head_dim=self.D)
-        # the engine's tables are fp32 (engine.cpp: spiral_rope_table in double, stored as float)
+        # the engine's tables are fp32 (plan.cpp: spiral_rope_table in double, stored as float)
         self.cos, self.sin = (torch.from_numpy(a.astype(np.float32) if twin else a).to(self.dt) for a in (cos, sin))
 
     # ---- helpers --------------------------------------------------------------------------------------------------

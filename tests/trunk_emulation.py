@@ -10,15 +10,15 @@ Modes (`Trunk(cfg, W, fp16=..., twin=...)`):
   * fp16=True: round-to-nearest-even to fp16 at the storage points below, every other value in float64 (accumulation,
     the folded BN scale and shift, mish).  This is the scheme the engine computes, without its fp32 arithmetic.
   * twin=True (implies fp16): the same storage points with the engine's fp32 arithmetic done another way: float32
-    torch convolutions (another summation order than the MFMA K loops), the BN fold in fp32 as engine.cpp fold_bn does,
+    torch convolutions (another summation order than the MFMA K loops), the BN fold in fp32 as plan.cpp fold_bn does,
     and mish in fp32 by the engine's formulas (conv_core.h mish_t2 in the fused block kernel, mish_f elsewhere).  It is
     a benign stand-in for the GPU: the checker's thresholds are set so that it passes on every fixture and block.
 
 Storage points (where the engine writes fp16; every accumulation is fp32 on the MFMAs):
-  * weights of every trunk conv and of the broadcast dense (engine.cpp build_plan packs them as _Float16 streams); the
+  * weights of every trunk conv and of the broadcast dense (plan.cpp build_plan packs them as _Float16 streams); the
     head convs conv_p, conv_g and value.conv likewise (k_headsx stages them as fp16 A fragments).  The dense biases,
     the game-state dense of the stem and the BN parameters stay fp32.
-  * the folded BN: scale = gamma / sqrt(var + eps), shift = beta - mean * scale in fp32 (engine.cpp fold_bn, about
+  * the folded BN: scale = gamma / sqrt(var + eps), shift = beta - mean * scale in fp32 (plan.cpp fold_bn, about
     line 413); the fused block kernel multiplies both by log2(e) once more (conv_core.h scale_log2e).
   * x after the stem: fp16(conv5x5(planes) + game dense) (kernels.hip k_init epilogue, `o[i] = (_Float16)(acc + bias)`).
   * x after every residual block: fp16(x16 + branch) with the branch and the sum in fp32 (conv_core.h epilogue_store,
@@ -76,7 +76,7 @@ HEADS_TOL = 2e-4   # |raw| of the engine's heads against heads() on the engine's
 
 
 def is_layerwise(cfg) -> bool:
-    """engine.cpp build_plan: the trunks whose blocks run conv by conv through k_lconv."""
+    """plan.cpp choose_plan: the trunks whose blocks run conv by conv through k_lconv."""
     return cfg.channels in (192, 384)
 
 
@@ -152,7 +152,7 @@ class Trunk:
     def bn(self, prefix):
         if prefix not in self._bn:
             g, b, m, v = (np.asarray(self.W[f"{prefix}.{f}"]) for f in ("gamma", "beta", "mean", "var"))
-            if self.twin:   # engine.cpp fold_bn, in fp32
+            if self.twin:   # plan.cpp fold_bn, in fp32
                 g, b, m, v = (a.astype(np.float32) for a in (g, b, m, v))
                 sc = (g / np.sqrt(v + np.float32(tr.BN_EPS))).astype(np.float32)
                 sh = (b - m * sc).astype(np.float32)
