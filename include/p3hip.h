@@ -249,6 +249,61 @@ int p3hip_int8_set_scales(p3hip_engine* e, const float* scales, int n);
 int p3hip_set_symmetries(p3hip_engine* e, uint32_t mask);
 void p3hip_symmetry_maps(uint16_t fwd[8][361], uint16_t inv[8][361]);
 
+/* ---- scoring against labels on the device (nn::Benchmark + DefaultStats, cc/nn/engine/benchmark_engine.cc:25-109) ----
+ * The reference judges an engine on labelled positions of a recorded chunk (GoDataset, go_dataset.cc:32-123) by fetching
+ * every NNInferResult and updating DefaultStats on the host.  Here the labels go to the device and two small kernels
+ * (csrc/score.hip) compute the per-position terms and their sums from the output rows the heads left in HBM: a scoring
+ * run needs no p3hip_get_slot per position and no host loop.  The output rows are fp32 in every precision plan.
+ *
+ * p3hip_labels mirrors nn::GoLabels as far as DefaultStats reads it (go_dataset.h; did_win = score_margin >= 0).
+ * The six terms of one position are exactly DefaultStats::Update (benchmark_engine.cc:25-61), quirks included:
+ *   argmax        the sequential scan of benchmark_engine.cc:11-22: starts at -FLT_MAX, index 0, advances on strict >.
+ *                 So: the lowest index among the largest non-NaN values above -FLT_MAX; index 0 if there is none
+ *                 (an all-NaN row, a row of -FLT_MAX or -inf).
+ *   [0] policy_loss   -log(p) rounded to float once (taken in double on the device), p = move_probs[argmax(labels.policy)];
+ *                     16 when p == 0 (:37-39)
+ *   [1] outcome_loss  the same on value_probs[did_win] (:40-43)
+ *   [2] policy_hit    1 when argmax(move_probs) == argmax(labels.policy), else 0 (:54-55)
+ *   [3] outcome_hit   1 when argmax(value_probs) == did_win, else 0 (:56-58)
+ *   [4] score_diff    fabsf(score_margin - (float)score_pred) (:59-60)
+ *   [5] score_pred    `int score_pred = Argmax(score_probs) + 0.5 - kScoreInflectionPoint` (:30-31): the double is
+ *                     truncated toward zero, so argmax 400 gives 0 and argmax 399 gives 0 as well (-0.5 truncates to 0),
+ *                     argmax 0 gives -399, argmax 799 gives 399.  Kept as the reference has it.
+ * The reference keeps running means (:45-60); p3hip_score returns sums in double and the count, mean = sum / n.
+ *
+ *   p3hip_load_labels  the labels of the position last loaded into `slot`.  They belong to that load: a new
+ *                      p3hip_load_slot / p3hip_load_slot_keyed of the slot clears them.  Same threading as load_slot.
+ *   p3hip_score        scores the rows of the LAST p3hip_run (or p3hip_int8_calibrate) whose slot has labels: gathers
+ *                      the labels by output row, uploads them, launches k_score_rows and k_score_sum on the engine's
+ *                      stream, waits, and copies back the six sums and the term rows.  Works whether or not the slots
+ *                      have been fetched already, until the next run; composes with compaction (row != slot),
+ *                      P3HIP_FLAG_RUN_ALL_SLOTS (slots without labels are left out), the NN cache (rows served from
+ *                      the table are scored like evaluated ones) and P3HIP_FLAG_SYMMETRY_AVG (the averaged rows are
+ *                      scored).  *n_scored = 0 and all sums 0 when no evaluated slot has labels.  The sums are a
+ *                      fixed-order reduction: the same rows give the same bits.  Called like p3hip_run: by one thread,
+ *                      never overlapping a run.  Fetches nothing: the slots stay pending for p3hip_get_slot.
+ *                      A slot that was loaded again after the run is left out (its labels would be the new
+ *                      position's, its row the old one's).  The hooks that overwrite the output rows without a run
+ *                      (p3hip_forward_resident, p3hip_time_trunk_kernel, p3hip_debug_score_rows) end the last run's
+ *                      scoring like a run does: p3hip_score then scores nothing until the next p3hip_run.
+ *   p3hip_get_score    the six terms of `slot` from the last p3hip_score; 2 if that call did not score the slot (no
+ *                      labels, not evaluated, or a run since).
+ *   p3hip_debug_score_rows  test hook: writes n synthetic rows (move_probs [n][362], value_probs [n][2], score_probs
+ *                      [n][800]) into output rows 0 .. n - 1 of the engine, scores them against labels[0 .. n - 1] and
+ *                      returns terms [n][6] and the six sums.  1 <= n <= batch size.  It overwrites the last run's
+ *                      results on the device: run again before fetching ownership or raw outputs. */
+typedef struct p3hip_labels {
+  float policy[P3HIP_NUM_MOVES];
+  float score_margin;
+  int32_t did_win;
+} p3hip_labels;
+#define P3HIP_NUM_SCORE_TERMS 6 /* policy_loss, outcome_loss, policy_hit, outcome_hit, score_diff, score_pred */
+int p3hip_load_labels(p3hip_engine* e, int slot, const p3hip_labels* labels);
+int p3hip_score(p3hip_engine* e, double sums[P3HIP_NUM_SCORE_TERMS], int* n_scored);
+int p3hip_get_score(p3hip_engine* e, int slot, float terms[P3HIP_NUM_SCORE_TERMS]);
+int p3hip_debug_score_rows(p3hip_engine* e, const float* move_probs, const float* value_probs, const float* score_probs,
+                           const p3hip_labels* labels, int n, float* terms, double sums[P3HIP_NUM_SCORE_TERMS]);
+
 /* ---- measurement / test hooks (not part of the reference surface) ------------------ */
 
 /* Device-resident benchmark step: runs the forward pass on whatever is already staged in

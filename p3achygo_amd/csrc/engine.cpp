@@ -173,6 +173,9 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
   e->slots = p3::SlotStates((int)B);
   e->slot_sym.assign(B, 0);
   e->row_sym.assign(B, 0);
+  e->has_labels.assign(B, 0);
+  e->load_seq.assign(B, 0);
+  e->run_load_seq.assign(B, 0);
   return e;
 }
 
@@ -187,6 +190,7 @@ void p3hip_destroy(p3hip_engine* e) {
   hipFree(e->d_amax); hipFree(e->d_ascale);
   if (e->bw_mod) hipModuleUnload(e->bw_mod);
   free_cache(e->cache);
+  free_scoring(e);
   if (e->h_feats) hipHostFree(e->h_feats);
   if (e->h_feats_compact) hipHostFree(e->h_feats_compact);
   if (e->h_out) hipHostFree(e->h_out);
@@ -205,6 +209,8 @@ int p3hip_load_slot(p3hip_engine* e, int slot, const p3hip_features* f) {
   if (slot < 0 || slot >= e->batch) return 1;
   memcpy(e->h_feats + (size_t)slot * kFeatBytes, f, kFeatBytes);
   e->slot_sym[slot] = 0;
+  e->has_labels[slot] = 0;   // labels belong to one load (p3hip_load_labels)
+  ++e->load_seq[slot];
   if (e->cache.on) e->cache.h_slot_keys[slot] = p3::CacheKey{0, 0, 0};   // no key: evaluated, never cached
   e->slots.loaded(slot);
   return 0;
@@ -215,6 +221,8 @@ int p3hip_load_slot_keyed(p3hip_engine* e, int slot, const p3hip_features* f, ui
   if (symmetry < 0 || symmetry > 7) return 1;
   memcpy(e->h_feats + (size_t)slot * kFeatBytes, f, kFeatBytes);
   e->slot_sym[slot] = (unsigned char)symmetry;
+  e->has_labels[slot] = 0;
+  ++e->load_seq[slot];
   if (e->cache.on) e->cache.h_slot_keys[slot] = p3::CacheKey{key_lo, key_hi, (unsigned long long)symmetry};
   e->slots.loaded(slot);
   return 0;
@@ -267,6 +275,7 @@ int p3hip_cache_stats(const p3hip_engine* e, uint64_t out[4]) {
 // Compacts every dirty slot (loaded and not yet fetched, slot_state.h) into the dense upload.
 static int gather_loaded(p3hip_engine* e) {
   const bool all = (e->flags & P3HIP_FLAG_RUN_ALL_SLOTS) != 0;
+  e->gather_seq = ++e->run_seq;   // the rows change hands: the last p3hip_score's terms are no longer the slots'
   // When every slot of the static batch is evaluated (the common case: NNInterface fills the whole batch, the self-play
   // scheduler always does) the dense upload IS h_feats: no second host copy of 1.9 MB per run.
   std::vector<std::pair<int, int>> moved;
@@ -275,6 +284,7 @@ static int gather_loaded(p3hip_engine* e) {
     if (s != row) identity = false;
     moved.emplace_back(s, row);
     e->row_sym[row] = e->slot_sym[s];
+    e->run_load_seq[s] = e->load_seq[s];
     if (e->cache.on) {
       e->cache.h_keys[row] = e->cache.h_slot_keys[s];
       e->cache.out_row[row] = row;   // p3hip_run re-maps (misses first, then hits)
@@ -357,6 +367,7 @@ int p3hip_upload(p3hip_engine* e) {
 
 int p3hip_forward_resident(p3hip_engine* e, int n_positions) {
   if (n_positions < 1 || n_positions > e->batch || !e->bind() || !int8_ready(e)) return 1;
+  ++e->run_seq;   // d_out is overwritten without a gather: the last p3hip_score no longer answers for the slots
   return run_pass(e, Pass{upload_buffer(e), n_positions, e->d_out}) ? 0 : 1;
 }
 
@@ -555,6 +566,7 @@ double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
     }
   }
   if (n_positions < 1 || n_positions > e->batch || iters < 1 || !e->bind() || !int8_ready(e)) return -1.0;
+  ++e->run_seq;   // as p3hip_forward_resident
   // The timed kernel (enqueue_forward records an event pair around each of its launches) and its launches per forward
   // pass: the attention kernel of transformer trunks, the block kernel (k_block, k_blockw; k_block_i8: one launch per
   // btl block), or else the 3x3 layer conv of the layer-wise trunks

@@ -4,6 +4,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -118,6 +120,29 @@ struct p3hip_engine {
     std::vector<unsigned char> was_hit;                  // by row of the run
     unsigned long long lookups = 0, hits = 0, inserts = 0;
   } cache;
+  // Scoring against labels (include/p3hip.h; scoring.cpp, score.hip).  The labels live per slot in pinned memory and
+  // belong to the slot's current load (has_labels[slot], cleared by p3hip_load_slot*).  p3hip_score gathers those of the
+  // last run's rows into h_dense / h_rows (entry k scores output row h_rows[k]), uploads, and reads back terms and sums.
+  // The buffers are made by the first p3hip_load_labels (many threads may race for it) or p3hip_debug_score_rows.
+  struct Scoring {
+    std::mutex mu;
+    std::atomic<bool> ready{false};
+    p3hip_labels *h_slot = nullptr, *h_dense = nullptr, *d_labels = nullptr;   // pinned [batch] by slot / dense; device
+    int *h_rows = nullptr, *d_rows = nullptr;
+    float *h_terms = nullptr, *d_terms = nullptr;   // [batch][P3HIP_NUM_SCORE_TERMS]
+    double *h_sums = nullptr, *d_sums = nullptr;
+    std::vector<int> entry_of_slot;   // slot -> entry of the last p3hip_score (-1: not scored)
+    long scored_run = -1;             // run_seq that p3hip_score scored
+  } scoring;
+  std::vector<unsigned char> has_labels;   // [batch]
+  // load_seq[slot] counts the slot's loads, run_load_seq[slot] is its value when the last run gathered the slot:
+  // p3hip_score leaves out a slot that was loaded again since (its labels are the new position's, its row the old one's)
+  std::vector<unsigned> load_seq, run_load_seq;
+  // counts whatever hands the output rows to someone else: every gather (p3hip_run, p3hip_int8_calibrate, p3hip_upload)
+  // and the hooks that write d_out without one (p3hip_forward_resident, p3hip_time_trunk_kernel, p3hip_debug_score_rows)
+  long run_seq = 0;
+  long gather_seq = 0;   // run_seq of the last gather: while they are equal, d_out still holds that run's rows
+
   // row of d_out / h_out that holds `slot`'s result (-1: not evaluated by the last run)
   int out_row_of(int slot) const {
     const int row = slots.row(slot);
@@ -145,5 +170,7 @@ bool enqueue_forward(p3hip_engine* e, const Pass& p);
 bool expand_sym(p3hip_engine* e, const unsigned char* src, int n);
 bool run_pass(p3hip_engine* e, const Pass& p);
 void drop_graph(p3hip_engine* e);
+// scoring.cpp
+void free_scoring(p3hip_engine* e);
 
 }  // namespace eng

@@ -17,7 +17,7 @@ import os
 
 import numpy as np
 
-from .features import RAW_LEN, Features, Result
+from .features import NUM_MOVES, RAW_LEN, Features, Result
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # P3HIP_LIB lets tools/gpu_ab.py time two builds of the kernels side by side.
@@ -32,6 +32,7 @@ EXPORTS = [
     "p3hip_blockw_stamps", "p3hip_debug_x", "p3hip_debug_tfm", "p3hip_rope_table", "p3hip_rope_table_dim",
     "p3hip_int8_calibrate", "p3hip_int8_scales", "p3hip_int8_set_scales",
     "p3hip_set_symmetries", "p3hip_symmetry_maps",
+    "p3hip_load_labels", "p3hip_score", "p3hip_get_score", "p3hip_debug_score_rows",
 ]
 
 FLAG_RUN_ALL_SLOTS = 2
@@ -43,7 +44,17 @@ FLAG_INT8_C128 = 128   # the same for the C = 128 / C_b = 64 btl trunks (b12c128
 FLAG_FP32 = 256   # the conv trunks layer by layer in fp32, weights and activations included
 FLAG_FP32_TFM = 512   # the transformer trunks in fp32, weights and activations included
 FLAG_FP32_ANY = FLAG_FP32 | FLAG_FP32_TFM   # full precision whatever the trunk
+NUM_SCORE_TERMS = 6
+SCORE_TERMS = ("policy_loss", "outcome_loss", "policy_hit", "outcome_hit", "score_diff", "score_pred")
 FLAG_SYMMETRY_AVG = 32  # every slot averaged over a set of the eight symmetries on the device
+
+
+def labels_dtype() -> np.dtype:
+    """numpy mirror of p3hip_labels (include/p3hip.h): the part of nn::GoLabels that DefaultStats reads."""
+    return np.dtype([("policy", np.float32, (NUM_MOVES,)), ("score_margin", np.float32), ("did_win", np.int32)])
+
+
+assert labels_dtype().itemsize == 4 * (NUM_MOVES + 2)
 
 
 class EngineError(RuntimeError):
@@ -100,6 +111,11 @@ def lib():
         L.p3hip_set_symmetries.argtypes = [C.c_void_p, C.c_uint32]
         L.p3hip_symmetry_maps.argtypes = [C.c_void_p, C.c_void_p]
         L.p3hip_symmetry_maps.restype = None
+        L.p3hip_load_labels.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.p3hip_score.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]
+        L.p3hip_get_score.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.p3hip_debug_score_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                             C.c_void_p, C.POINTER(C.c_double)]
         L.p3hip_time_trunk_kernel.restype = C.c_double
         L.p3hip_time_trunk_kernel.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double),
                                               C.POINTER(C.c_char_p)]
@@ -221,6 +237,46 @@ class HipEngine:
         if not 0 <= int(mask) < 1 << 32:
             raise EngineError(f"set_symmetries: mask {mask} is not a uint32")
         self._ck(self._L.p3hip_set_symmetries(self._h, int(mask)), "set_symmetries")
+
+    # -- scoring against labels on the device (include/p3hip.h; DefaultStats, benchmark_engine.cc:25-61) ----
+    def load_labels(self, batch_id: int, labels) -> None:
+        """The labels (one labels_dtype() record, or its address) of the position last loaded into the slot; a new
+        LoadBatch of the slot clears them."""
+        ptr = labels.ctypes.data if isinstance(labels, np.ndarray) else labels
+        self._ck(self._L.p3hip_load_labels(self._h, batch_id, ptr), "load_labels")
+
+    def score(self):
+        """Scores the rows of the last run whose slot has labels: (sums, n_scored), sums a float64 array in the order
+        of SCORE_TERMS.  Fetches nothing."""
+        sums = (C.c_double * NUM_SCORE_TERMS)()
+        n = C.c_int(0)
+        self._ck(self._L.p3hip_score(self._h, sums, C.byref(n)), "score")
+        return np.array(sums[:], np.float64), n.value
+
+    def get_score(self, batch_id: int):
+        """The six terms of the slot from the last score(), or None when that call did not score the slot."""
+        out = np.zeros(NUM_SCORE_TERMS, np.float32)
+        rc = self._L.p3hip_get_score(self._h, batch_id, out.ctypes.data)
+        if rc == 2:
+            return None
+        self._ck(rc, "get_score")
+        return out
+
+    def debug_score_rows(self, move_probs, value_probs, score_probs, labels):
+        """Test hook: scores n synthetic rows ([n][362], [n][2], [n][800] floats) against labels (labels_dtype()[n]);
+        returns (terms [n][6] float32, sums [6] float64).  Overwrites the last run's rows on the device."""
+        mp = np.ascontiguousarray(move_probs, np.float32)
+        vp = np.ascontiguousarray(value_probs, np.float32)
+        sp = np.ascontiguousarray(score_probs, np.float32)
+        lab = np.ascontiguousarray(labels, labels_dtype())
+        n = len(lab)
+        if mp.shape != (n, NUM_MOVES) or vp.shape != (n, 2) or sp.shape != (n, 800):
+            raise EngineError("debug_score_rows: rows must be [n][362], [n][2] and [n][800] for n labels")
+        terms = np.zeros((n, NUM_SCORE_TERMS), np.float32)
+        sums = (C.c_double * NUM_SCORE_TERMS)()
+        self._ck(self._L.p3hip_debug_score_rows(self._h, mp.ctypes.data, vp.ctypes.data, sp.ctypes.data, lab.ctypes.data,
+                                                n, terms.ctypes.data, sums), "debug_score_rows")
+        return terms, np.array(sums[:], np.float64)
 
     # -- measurement / test hooks -------------------------------------------------------
     def load_all(self, feats_rec: np.ndarray) -> None:

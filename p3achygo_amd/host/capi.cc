@@ -9,6 +9,7 @@
 #include "features.h"
 #include "rng.h"
 #include "symmetry.h"
+#include "tf_reader.h"
 
 using namespace p3;
 
@@ -614,4 +615,34 @@ int p3host_test_batch_search_ex(int batch, int budget, int mode, int q_fn, int n
   out[7] = bad_n; out[8] = bad_if; out[9] = evals;
   return 0;
 }
+}
+
+// ---- chunk reader (tf_reader.h): the rows of a recorded .tfrecord / .tfrecord.zz chunk ----------------------
+
+extern "C" {
+// mode 0: plain or zlib by the first bytes, 1: plain TFRecord, 2: one zlib stream.  Returns the dataset, or null with
+// the reason (which names the record index and what failed) in err[0 .. errlen).  Never a partly read dataset.
+void* p3host_dataset_open(const char* path, int mode, char* err, int errlen) {
+  auto fail = [&](const std::string& m) {
+    if (err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", m.c_str());
+    return (void*)nullptr;
+  };
+  if (err && errlen > 0) err[0] = 0;
+  if (!path || mode < 0 || mode > 2) return fail("p3host_dataset_open: bad arguments");
+  GoDataset* ds = new GoDataset();
+  const ReadStatus st = ds->Open(path, mode);
+  if (st.ok()) return ds;
+  delete ds;
+  return fail(st.msg);
+}
+long p3host_dataset_size(void* ds) { return ds ? (long)((GoDataset*)ds)->size() : -1; }
+// Copies row i; either pointer may be null.  1: no such row (nothing is written).
+int p3host_dataset_row(void* ds, long i, p3hip_features* f, p3hip_labels* l) {
+  if (!ds || i < 0 || (size_t)i >= ((GoDataset*)ds)->size()) return 1;
+  const DatasetRow& r = ((GoDataset*)ds)->row((size_t)i);
+  if (f) *f = r.features;
+  if (l) *l = r.labels;
+  return 0;
+}
+void p3host_dataset_close(void* ds) { delete (GoDataset*)ds; }
 }

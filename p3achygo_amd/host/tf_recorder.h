@@ -27,32 +27,11 @@
 #include <vector>
 
 #include "board.h"
+#include "crc32c.h"
 #include "rng.h"
 #include "search.h"
 
 namespace p3 {
-
-// ---- CRC32C (Castagnoli, reflected 0x82F63B78), masked as TFRecord wants it --------------
-inline uint32_t Crc32c(const void* data, size_t n, uint32_t crc = 0) {
-  static uint32_t table[256];
-  static bool init = false;
-  if (!init) {
-    for (uint32_t i = 0; i < 256; ++i) {
-      uint32_t c = i;
-      for (int k = 0; k < 8; ++k) c = (c & 1) ? (c >> 1) ^ 0x82F63B78u : c >> 1;
-      table[i] = c;
-    }
-    init = true;
-  }
-  crc = ~crc;
-  const uint8_t* p = (const uint8_t*)data;
-  for (size_t i = 0; i < n; ++i) crc = table[(crc ^ p[i]) & 0xff] ^ (crc >> 8);
-  return ~crc;
-}
-inline uint32_t MaskedCrc32c(const void* data, size_t n) {   // crc32.h:38-43
-  const uint32_t crc = Crc32c(data, n);
-  return ((crc >> 15) | (crc << 17)) + 0xa282ead8u;
-}
 
 // ---- protobuf wire helpers ---------------------------------------------------------------
 inline void PbVarint(std::string& o, uint64_t v) {

@@ -42,6 +42,8 @@ def lib():
             "p3host_game_play": (i32, [vp, i32, i32, i32]), "p3host_game_num_moves": (i32, [vp]),
             "p3host_game_features": (None, [vp, i32, i32, vp]),
             "p3host_unapply_symmetry": (None, [i32, vp]),
+            "p3host_dataset_open": (vp, [C.c_char_p, i32, C.c_char_p, i32]), "p3host_dataset_size": (C.c_long, [vp]),
+            "p3host_dataset_row": (i32, [vp, C.c_long, vp, vp]), "p3host_dataset_close": (None, [vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -124,6 +126,36 @@ class Board:
 
     def hash(self) -> int:
         return self._L.p3host_board_hash(self._h)
+
+
+class DatasetError(RuntimeError):
+    """A chunk that cannot be read; the message names the record index and what failed."""
+
+
+DATASET_AUTO, DATASET_PLAIN, DATASET_ZLIB = 0, 1, 2
+
+
+def dataset_open(path: str, mode: int = DATASET_AUTO):
+    """p3host_dataset_open: handle of the rows of one recorded chunk (plain TFRecord or .tfrecord.zz)."""
+    err = C.create_string_buffer(512)
+    h = lib().p3host_dataset_open(os.fsencode(path), int(mode), err, len(err))
+    if not h:
+        raise DatasetError(err.value.decode(errors="replace"))
+    return h
+
+
+def dataset_size(h) -> int:
+    return int(lib().p3host_dataset_size(h))
+
+
+def dataset_row(h, i: int, features_ptr, labels_ptr) -> None:
+    """Copies row i into a p3hip_features and a p3hip_labels (addresses; either may be None)."""
+    if lib().p3host_dataset_row(h, int(i), features_ptr, labels_ptr) != 0:
+        raise IndexError(f"dataset row {i} out of range")
+
+
+def dataset_close(h) -> None:
+    lib().p3host_dataset_close(h)
 
 
 class SelfPlayStats(C.Structure):
