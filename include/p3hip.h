@@ -146,6 +146,14 @@ typedef struct p3hip_engine p3hip_engine;
                                        conv trunk takes the plan of P3HIP_FLAG_FP32 (bit-identical to that flag alone), a
                                        transformer trunk the plan of P3HIP_FLAG_FP32_TFM */
 
+#define P3HIP_FLAG_AUX 1024u        /* every forward pass also computes the fifteen outputs of the model (python/model.py:1269-1295)
+                                       that p3hip_result and p3hip_get_raw do not carry, on the device, one record per
+                                       position: p3hip_get_aux below (csrc/heads_aux.hip).  Everything
+                                       else the engine returns keeps its bits.  Composes with every trunk and precision plan
+                                       (the record is fp32 in all of them), P3HIP_FLAG_RUN_ALL_SLOTS, P3HIP_FLAG_SHARED_DEVICE
+                                       and P3HIP_FLAG_LAUNCH_GRAPH.  p3hip_create returns NULL together with
+                                       P3HIP_FLAG_SYMMETRY_AVG, and p3hip_cache_enable fails on such an engine */
+
 /* Transformer trunks (python/model_transformer.py TransformerBlock, a generic_arch of "transformer" blocks) the engine
  * runs: every block has the same embed_dim d and num_heads h, d equals the stem's channels, d is a multiple of 32 with
  * 64 <= d <= 384, the head width d / h is 32 or 64; any block count the .p3w header allows; H = 32 and V what the heads
@@ -248,6 +256,29 @@ int p3hip_int8_set_scales(p3hip_engine* e, const float* scales, int n);
  *   p3hip_symmetry_maps   the forward and inverse index maps of the 19 x 19 board the kernels use.  Needs no device. */
 int p3hip_set_symmetries(p3hip_engine* e, uint32_t mask);
 void p3hip_symmetry_maps(uint16_t fwd[8][361], uint16_t inv[8][361]);
+
+/* ---- the model's other fifteen outputs (P3HIP_FLAG_AUX) -------------------------------------------------------
+ * The network has 25 named outputs (python/model.py:1269-1295, exported by python/scripts/convert_to_onnx.py:462-488 as
+ * "00:pi_logits" .. "24:mcts_dist_probs").  Ten reach the caller through p3hip_result and p3hip_get_raw (00-07, 12, 22);
+ * an engine created with P3HIP_FLAG_AUX computes the other fifteen in every forward pass (k_heads_aux, fp32 in every
+ * precision plan) and keeps one record of P3HIP_AUX_LEN floats per position on the device:
+ *   [0..361]    08:pi_logits_aux     channel 1 of policy.out_moves over the activated p; [361] the pass, out_pass[1] - 3
+ *   [362..723]  21:pi_logits_soft    policy.soft_moves over p; [723] the pass, soft_pass - 3
+ *   [724..726]  09:q6 10:q16 11:q50  tanh(go[2..4]), go = oq_out(mish(oq_embed(pooled v)))
+ *   [727..728]  13:q16_err 14:q50_err                    4 sigmoid(go[6..7])   (12:q6_err stays where it is: p3hip_result
+ *                                                                              err2_outcome, p3hip_get_raw [1887])
+ *   [729..731]  15:q6_score 16:q16_score 17:q50_score    go[8..10]
+ *   [732..734]  18:q6_score_err 19:q16_score_err 20:q50_score_err   |go[11..13]|
+ *   [735..785]  23:mcts_dist_logits  value.mcts_dist(emb), 51 bins
+ *   [786..836]  24:mcts_dist_probs   their softmax
+ *   p3hip_get_aux  the record of `slot` from the last run.  1 on an engine without the flag and for a bad slot; 2 when
+ *                  the last run did not evaluate the slot (`out` is left untouched), which includes every run of an engine
+ *                  stopped in front of the heads (P3HIP_DEBUG_STOP_BLOCK).  Like p3hip_get_raw it maps the slot to its row
+ *                  of the run (compaction, P3HIP_FLAG_RUN_ALL_SLOTS) and does not mark the slot fetched.
+ * Symmetry averaging is refused: a mean of tanh, |.| and softmax outputs over symmetries is nothing the reference
+ * defines.  The NN cache is refused: its table holds output rows that have no room for the record. */
+#define P3HIP_AUX_LEN 837
+int p3hip_get_aux(p3hip_engine* e, int slot, float out[P3HIP_AUX_LEN]);
 
 /* ---- scoring against labels on the device (nn::Benchmark + DefaultStats, cc/nn/engine/benchmark_engine.cc:25-109) ----
  * The reference judges an engine on labelled positions of a recorded chunk (GoDataset, go_dataset.cc:32-123) by fetching

@@ -94,6 +94,11 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
                      std::to_string(batch_size) + " exceeds the engine's row limit of 65536 (batch size at most 8192)";
     return nullptr;
   }
+  if (sym && (flags & P3HIP_FLAG_AUX)) {
+    g_create_error = "P3HIP_FLAG_AUX cannot be combined with P3HIP_FLAG_SYMMETRY_AVG: the aux record holds tanh, absolute "
+                     "value and softmax outputs, and their average over symmetries is nothing the reference defines";
+    return nullptr;
+  }
   p3hip_engine* e = new p3hip_engine();
   e->path = weights_path;
   e->batch = batch_size;
@@ -150,6 +155,8 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
             e->check(hipMalloc((void**)&e->d_out, B * p3::kOutStride * 4), "hipMalloc out") &&
             (!sym || (e->check(hipMalloc((void**)&e->d_sfeats, B * kFeatBytes), "hipMalloc symmetry upload") &&
                       e->check(hipMalloc((void**)&e->d_cout, R * p3::kOutStride * 4), "hipMalloc copy rows"))) &&
+            (!(flags & P3HIP_FLAG_AUX) || (e->check(hipMalloc((void**)&e->d_aux, R * p3::kAuxStride * 4), "hipMalloc aux") &&
+                                           e->check(hipMemsetAsync(e->d_aux, 0, R * p3::kAuxStride * 4, e->stream), "hipMemset aux"))) &&
             (!is_int8(path) || (e->check(hipMalloc((void**)&e->d_amax, (size_t)e->plan.n_q * 4), "hipMalloc amax") &&
                           e->check(hipMalloc((void**)&e->d_ascale, (size_t)e->plan.n_q * 4), "hipMalloc scales") &&
                           e->check(hipMemsetAsync(e->d_amax, 0, (size_t)e->plan.n_q * 4, e->stream), "hipMemset amax") &&
@@ -170,6 +177,13 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
   e->heads_args.gbn_scale = e->dev<float>(e->plan.heads_gbn.scale_off);
   e->heads_args.gbn_shift = e->dev<float>(e->plan.heads_gbn.shift_off);
   for (int k = 0; k < kNumHeadTensors; ++k) e->heads_args.*kHeadTensors[k].arg = e->dev<float>(e->plan.head_tensor_off[k]);
+  if (flags & P3HIP_FLAG_AUX) {
+    e->aux_args.V = e->wf.V;
+    e->aux_args.gbn_scale = e->heads_args.gbn_scale; e->aux_args.gbn_shift = e->heads_args.gbn_shift;
+    e->aux_args.gd_w = e->heads_args.gd_w; e->aux_args.gd_b = e->heads_args.gd_b;
+    e->aux_args.oq_embed_w = e->heads_args.oq_embed_w; e->aux_args.oq_embed_b = e->heads_args.oq_embed_b;
+    for (int k = 0; k < kNumAuxTensors; ++k) e->aux_args.*kAuxTensors[k].arg = e->dev<float>(e->plan.aux_tensor_off[k]);
+  }
   e->slots = p3::SlotStates((int)B);
   e->slot_sym.assign(B, 0);
   e->row_sym.assign(B, 0);
@@ -185,7 +199,7 @@ void p3hip_destroy(p3hip_engine* e) {
   if (e->stream) hipStreamSynchronize(e->stream);
   hipFree(e->d_arena); hipFree(e->d_feats); hipFree(e->d_x); hipFree(e->d_t); hipFree(e->d_u); hipFree(e->d_s);
   hipFree(e->d_hp); hipFree(e->d_out); hipFree(e->d_res); hipFree(e->d_qkv);
-  hipFree(e->d_sfeats); hipFree(e->d_cout);
+  hipFree(e->d_sfeats); hipFree(e->d_cout); hipFree(e->d_aux);
   hipFree(e->d_bw_stamps);
   hipFree(e->d_amax); hipFree(e->d_ascale);
   if (e->bw_mod) hipModuleUnload(e->bw_mod);
@@ -229,6 +243,11 @@ int p3hip_load_slot_keyed(p3hip_engine* e, int slot, const p3hip_features* f, ui
 }
 
 int p3hip_cache_enable(p3hip_engine* e, int log2_entries) {
+  if (e->flags & P3HIP_FLAG_AUX) {
+    e->err = "p3hip_cache_enable: not available on a P3HIP_FLAG_AUX engine: the table's entries are output rows of "
+             "kOutStride floats with no room for the aux record, so a hit could not serve p3hip_get_aux";
+    return 1;
+  }
   if (!e->bind()) return 1;
   if (e->cache.on) { e->err = "cache already enabled"; return 1; }
   if (log2_entries < 4 || log2_entries > 26) { e->err = "cache size: 2^4 .. 2^26 entries"; return 1; }
@@ -533,6 +552,17 @@ int p3hip_get_raw(p3hip_engine* e, int slot, float* out) {
   out[1887] = rec[p3::kOffErr2];
   out[1888] = rec[p3::kOffGamma];
   return 0;
+}
+
+int p3hip_get_aux(p3hip_engine* e, int slot, float out[P3HIP_AUX_LEN]) {
+  if (!(e->flags & P3HIP_FLAG_AUX) || slot < 0 || slot >= e->batch) return 1;
+  const int row = e->out_row_of(slot);
+  // (a pass stopped in front of the heads, P3HIP_DEBUG_STOP_BLOCK = 0 .. the block count, computes no record)
+  const int stop = e->opt.stop_block;
+  if (row < 0 || (stop >= 0 && stop <= (int)e->plan.blocks.size())) return 2;
+  if (!e->bind()) return 1;
+  return e->check(hipMemcpy(out, e->d_aux + (size_t)row * p3::kAuxStride, p3::kAuxFloats * 4, hipMemcpyDeviceToHost),
+                  "D2H aux") ? 0 : 1;
 }
 
 void p3hip_flops_per_position(const p3hip_engine* e, double* total, double* conv3x3) {

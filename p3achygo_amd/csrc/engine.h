@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/p3hip.h"
+#include "heads_aux.h"
 #include "kernels.h"
 #include "plan.h"
 #include "slot_state.h"
@@ -92,6 +93,10 @@ struct p3hip_engine {
 #endif
   _Float16* d_s = nullptr;   // nbt trunks: the block kernel's inner-stream scratch (t and u carry the broadcast blocks' tensors)
   float* d_hp = nullptr;
+  // P3HIP_FLAG_AUX: k_heads_aux writes one record per row of the pass into d_aux [rows][kAuxStride],
+  // allocated under the flag only; aux_args: its weight pointers, set once at create (a pass fills hp, aux and npos)
+  float* d_aux = nullptr;
+  p3::HeadsAuxArgs aux_args{};
   float* d_out = nullptr;
   float* h_out = nullptr;  // pinned [batch][kResultFloats]
   float* d_res = nullptr;  // [batch][kResultFloats] dense: the heads kernel writes the result records a second time there

@@ -468,10 +468,22 @@ bool enqueue_heads(p3hip_engine* e, const Pass& p) {
     c.wstream = e->d_arena + e->plan.heads_stream_off; c.nms_total = e->plan.heads_nms;
     if (!e->check(launch_conv1x1(e, 2, c), "launch head convs")) return false;
   }
+  const bool aux = (e->flags & P3HIP_FLAG_AUX) != 0;
+  if (aux && e->plan.choice.heads_fused) {
+    // k_headsx keeps the head convs' output to itself: the launch the unfused path makes, for k_heads_aux alone
+    p3::Conv1x1Args c{};
+    c.in = e->d_x; c.out32 = e->d_hp; c.npos = p.npos;
+    c.wstream = e->d_arena + e->plan.heads_stream_off; c.nms_total = e->plan.heads_nms;
+    if (!e->check(launch_conv1x1(e, 2, c), "launch head convs (aux)")) return false;
+  }
   p3::HeadsArgs h = e->heads_args;   // the weight pointers never change after create
   h.x = e->d_x; h.hp = e->d_hp; h.out = p.out; h.res = p.res; h.npos = p.npos;
-  if (e->plan.choice.heads_fused) return e->check(p3::launch_headsx(C, h, e->n_cu, e->stream), "launch k_headsx");
-  return e->check(p3::launch_heads(h, p.npos, e->stream), "launch k_heads");
+  if (!(e->plan.choice.heads_fused ? e->check(p3::launch_headsx(C, h, e->n_cu, e->stream), "launch k_headsx")
+                                   : e->check(p3::launch_heads(h, p.npos, e->stream), "launch k_heads"))) return false;
+  if (!aux) return true;
+  p3::HeadsAuxArgs x = e->aux_args;
+  x.hp = e->d_hp; x.aux = e->d_aux; x.npos = p.npos;
+  return e->check(p3::launch_heads_aux(x, e->n_cu, e->stream), "launch k_heads_aux");
 }
 
 }  // namespace

@@ -167,6 +167,18 @@ const HeadTensor kHeadTensors[kNumHeadTensors] = {
     {"value.score_out.w", &p3::HeadsArgs::score_out_w, 0, 1, 6},
     {"value.score_out.b", &p3::HeadsArgs::score_out_b, 1, 0, -1}};
 
+const AuxTensor kAuxTensors[kNumAuxTensors] = {
+    {"policy.soft_moves.w", &p3::HeadsAuxArgs::soft_moves_w, 32, 0, 0, 0, {}},
+    {"policy.soft_pass.w", &p3::HeadsAuxArgs::soft_pass_w, 2 * 32, 0, 0, 0, {}},
+    {"policy.soft_pass.b", &p3::HeadsAuxArgs::soft_pass_b, 1, 0, 0, 0, {}},
+    {"value.mcts_dist.w", &p3::HeadsAuxArgs::mcts_w, 0, p3::kAuxBins, 0, 0, {}},
+    {"value.mcts_dist.b", &p3::HeadsAuxArgs::mcts_b, p3::kAuxBins, 0, 0, 0, {}},
+    {"policy.out_moves.w", &p3::HeadsAuxArgs::moves_aux_w, 2 * 32, 0, 2, 1, {1}},
+    {"policy.out_pass.w", &p3::HeadsAuxArgs::pass_aux_w, 4 * 32, 0, 2, 1, {1}},
+    {"policy.out_pass.b", &p3::HeadsAuxArgs::pass_aux_b, 2, 0, 2, 1, {1}},
+    {"value.oq_out.w", &p3::HeadsAuxArgs::oq_aux_w, 0, 14, 14, p3::kAuxGoCols, {2, 3, 4, 6, 7, 8, 9, 10, 11, 12, 13}},
+    {"value.oq_out.b", &p3::HeadsAuxArgs::oq_aux_b, 14, 0, 14, p3::kAuxGoCols, {2, 3, 4, 6, 7, 8, 9, 10, 11, 12, 13}}};
+
 namespace {
 
 constexpr float kBnEps = 1e-3f;  // model.py:231
@@ -691,6 +703,25 @@ bool pack_heads(Builder& b, std::string& err) {
   return true;
 }
 
+// P3HIP_FLAG_AUX: the aux tensors of kAuxTensors behind everything else in the arena (an engine without the flag has the
+// same image as before), fp32 whatever the plan
+void pack_aux(Builder& b) {
+  const WeightFile& wf = b.wf;
+  for (int k = 0; k < kNumAuxTensors; ++k) {
+    const AuxTensor& at = kAuxTensors[k];
+    const size_t n = (size_t)at.n0 + (size_t)at.nV * wf.V;
+    const Tensor& t = wf.get(at.name, n);
+    if (at.cols == 0) {
+      b.plan.aux_tensor_off[k] = b.ar.add(t.data, n * 4);
+      continue;
+    }
+    std::vector<float> w;
+    for (size_t r = 0; r < n / at.cols; ++r)
+      for (int c = 0; c < at.ntake; ++c) w.push_back(t.data[r * at.cols + at.take[c]]);
+    b.plan.aux_tensor_off[k] = b.ar.add(w.data(), w.size() * 4);
+  }
+}
+
 }  // namespace
 
 // The spiral RoPE tables of python/model_transformer.py spiral_rope_cos_sin_table(num_rotations = 4, embed_dim = D,
@@ -739,6 +770,7 @@ bool build_plan(const WeightFile& wf, uint32_t flags, const Options& opt, Plan& 
   lay_out_runs(b);
   if (path == Path::Blockw) pack_blockw_runs(b);
   if (!pack_heads(b, err)) return false;
+  if (flags & P3HIP_FLAG_AUX) pack_aux(b);
   if (!wf.missing.empty()) {
     err = "weight file lacks tensors of the architecture its header names: " + wf.missing;
     return false;

@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "heads_aux.h"
 #include "kernels.h"
 #include "weights.h"
 
@@ -139,6 +140,20 @@ struct HeadTensor {
 constexpr int kNumHeadTensors = 21;
 extern const HeadTensor kHeadTensors[kNumHeadTensors];
 
+// The tensors behind the fifteen outputs of P3HIP_FLAG_AUX (heads_aux.h HeadsAuxArgs), packed as fp32 in every plan and
+// only under the flag: three tensor pairs no other kernel reads, whole, and of three tensors the heads read by column
+// the columns kHeadTensors' kernels leave out.
+struct AuxTensor {
+  const char* name;
+  const float* p3::HeadsAuxArgs::*arg;
+  int n0, nV;       // floats of the tensor in the file: n0 + nV * V, row-major [rows][cols]
+  int cols;         // 0: packed whole; else the tensor's column count, and
+  int ntake;        // the columns packed, in this order: [rows][ntake]
+  int take[p3::kAuxGoCols];
+};
+constexpr int kNumAuxTensors = 10;
+extern const AuxTensor kAuxTensors[kNumAuxTensors];
+
 // A run of k_blockw: consecutive btl blocks, their weight stream and parameter table
 struct BlockwRun { size_t first; int nblk; size_t stream_off, prm_off; };
 
@@ -157,6 +172,7 @@ struct Plan {
   size_t heads_conv_a_off = 0, heads_image_off = 0;
   FoldedBN heads_gbn{};                     // policy.gpool_bn
   size_t head_tensor_off[kNumHeadTensors] = {};   // by kHeadTensors index
+  size_t aux_tensor_off[kNumAuxTensors] = {};     // by kAuxTensors index (P3HIP_FLAG_AUX only)
 };
 
 // Packs the weights of `wf` for the path choose_plan picks into `ar` and fills `plan`.  The order of Arena::add calls is

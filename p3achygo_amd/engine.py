@@ -33,6 +33,7 @@ EXPORTS = [
     "p3hip_int8_calibrate", "p3hip_int8_scales", "p3hip_int8_set_scales",
     "p3hip_set_symmetries", "p3hip_symmetry_maps",
     "p3hip_load_labels", "p3hip_score", "p3hip_get_score", "p3hip_debug_score_rows",
+    "p3hip_get_aux",
 ]
 
 FLAG_RUN_ALL_SLOTS = 2
@@ -46,6 +47,25 @@ FLAG_FP32_TFM = 512   # the transformer trunks in fp32, weights and activations 
 FLAG_FP32_ANY = FLAG_FP32 | FLAG_FP32_TFM   # full precision whatever the trunk
 NUM_SCORE_TERMS = 6
 SCORE_TERMS = ("policy_loss", "outcome_loss", "policy_hit", "outcome_hit", "score_diff", "score_pred")
+FLAG_AUX = 1024   # the model's other fifteen outputs on the device, one record per position
+AUX_LEN = 837
+# The 25 outputs of the network by their ONNX names (python/scripts/convert_to_onnx.py:462-488).  AUX_SEGMENTS: where the
+# fifteen of the aux record lie (include/p3hip.h p3hip_get_aux); RAW_SEGMENTS: where p3hip_get_raw has seven of the other
+# ten; the three distributions 01, 03 and 06 come from the result record (GetBatch).
+AUX_SEGMENTS = {
+    "08:pi_logits_aux": (0, 362), "21:pi_logits_soft": (362, 724),
+    "09:q6": (724, 725), "10:q16": (725, 726), "11:q50": (726, 727),
+    "13:q16_err": (727, 728), "14:q50_err": (728, 729),
+    "15:q6_score": (729, 730), "16:q16_score": (730, 731), "17:q50_score": (731, 732),
+    "18:q6_score_err": (732, 733), "19:q16_score_err": (733, 734), "20:q50_score_err": (734, 735),
+    "23:mcts_dist_logits": (735, 786), "24:mcts_dist_probs": (786, 837),
+}
+RAW_SEGMENTS = {
+    "00:pi_logits": (0, 362), "22:pi_logits_optimistic": (362, 724), "02:outcome_logits": (724, 726),
+    "05:score_logits": (726, 1526), "04:own": (1526, 1887), "12:q6_err": (1887, 1888), "07:gamma": (1888, 1889),
+}
+RESULT_FIELDS = {"01:pi": "move_probs", "03:outcome": "value_probs", "06:score_probs": "score_probs"}
+OUTPUT_NAMES = tuple(sorted(list(AUX_SEGMENTS) + list(RAW_SEGMENTS) + list(RESULT_FIELDS)))
 FLAG_SYMMETRY_AVG = 32  # every slot averaged over a set of the eight symmetries on the device
 
 
@@ -116,6 +136,7 @@ def lib():
         L.p3hip_get_score.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.p3hip_debug_score_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                              C.c_void_p, C.POINTER(C.c_double)]
+        L.p3hip_get_aux.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.p3hip_time_trunk_kernel.restype = C.c_double
         L.p3hip_time_trunk_kernel.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double),
                                               C.POINTER(C.c_char_p)]
@@ -299,6 +320,32 @@ class HipEngine:
         self._ck(self._L.p3hip_get_raw(self._h, batch_id, raw.ctypes.data), "get_raw")
         return raw
 
+    # -- the model's other fifteen outputs (FLAG_AUX) ----------------------------------------
+    def GetAux(self, batch_id: int):
+        """The aux record of the slot from the last run, AUX_LEN floats (aux_outputs splits it); None when the last run
+        did not evaluate the slot.  Fails on an engine created without FLAG_AUX.  Fetches nothing."""
+        out = np.zeros(AUX_LEN, np.float32)
+        rc = self._L.p3hip_get_aux(self._h, batch_id, out.ctypes.data)
+        if rc == 2:
+            return None
+        if rc != 0:
+            raise EngineError(f"GetAux failed (rc={rc}): slot {batch_id} of {self.batch_size}, or the engine was created "
+                              "without FLAG_AUX; " + self._L.p3hip_last_error(self._h).decode())
+        return out
+
+    def all_outputs(self, batch_id: int) -> dict:
+        """All 25 outputs of the network for the slot, keyed by their ONNX names: seven from get_raw, fifteen from
+        GetAux, the three distributions from GetBatch (which marks the slot fetched, so it is read last)."""
+        raw, rec = self.get_raw(batch_id), self.GetAux(batch_id)
+        if rec is None:
+            raise EngineError(f"all_outputs: the last run did not evaluate slot {batch_id}")
+        out = {k: raw[a:b].copy() for k, (a, b) in RAW_SEGMENTS.items()}
+        out.update(aux_outputs(rec))
+        res = self.GetBatch(batch_id)
+        for k, f in RESULT_FIELDS.items():
+            out[k] = np.ctypeslib.as_array(getattr(res, f)).copy()
+        return {k: out[k] for k in OUTPUT_NAMES}
+
     def time_trunk_kernel(self, n_positions: int, iters: int):
         fl = C.c_double(0)
         name = C.c_char_p()
@@ -355,6 +402,14 @@ class HipEngine:
     def _ck(self, rc: int, what: str) -> None:
         if rc != 0:
             raise EngineError(f"{what} failed (rc={rc}): " + self._L.p3hip_last_error(self._h).decode())
+
+
+def aux_outputs(rec) -> dict:
+    """Splits an aux record (GetAux) into its fifteen outputs, keyed by their ONNX names."""
+    rec = np.asarray(rec)
+    if rec.shape[-1] != AUX_LEN:
+        raise ValueError(f"an aux record has {AUX_LEN} floats, not {rec.shape[-1]}")
+    return {k: rec[..., a:b] for k, (a, b) in AUX_SEGMENTS.items()}
 
 
 def rope_table():
