@@ -16,8 +16,7 @@
 // and issues 24 MFMAs.
 #include "block_i8.h"
 #include "block_i8_core.h"
-
-#include <atomic>
+#include "launch_util.h"
 
 namespace p3 {
 
@@ -141,19 +140,10 @@ __global__ void __launch_bounds__(kWgB) k_block_i8(BlockI8Args a) {
   }
 }
 
-// dynamic LDS above 64 KB needs the attribute, once per kernel and device
-struct AttrOnce { std::atomic<bool> done[32]; };
-
 template <int L>
 hipError_t launch_t(const BlockI8Args& a, int n_cu, hipStream_t s) {
-  static AttrOnce once;
-  int dev = 0;
-  const bool known = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 32;
-  if (!known || !once.done[dev].load(std::memory_order_acquire)) {
-    const hipError_t e = hipFuncSetAttribute((const void*)k_block_i8<L>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    if (e != hipSuccess) return e;
-    if (known) once.done[dev].store(true, std::memory_order_release);
-  }
+  static AttrOnce once;   // dynamic LDS above 64 KB needs the attribute, once per kernel and device
+  if (hipError_t e = ensure_lds(once, k_block_i8<L>, kLdsBytes); e != hipSuccess) return e;
   const int grid = a.npos < n_cu ? a.npos : n_cu;
   hipLaunchKernelGGL((k_block_i8<L>), dim3(grid), dim3(kWgB), kLdsBytes, s, a);
   return hipGetLastError();

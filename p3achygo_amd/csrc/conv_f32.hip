@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "conv_core.h"   // mish_f, f32x4, f32x16
+#include "layer_kernels.h"   // FeatOff
 
 namespace p3 {
 
@@ -36,11 +37,6 @@ struct GeoF {
   static constexpr int NT = (NTILES + 3) / 4;        // per wave
   static constexpr int NSLOT = PADTOP + NTILES * 32 + PADTOP;
   static constexpr int PLANE = NSLOT * 32;           // bytes of one 8-channel plane
-};
-
-struct FeatOffF {  // byte offsets inside p3hip_features (include/p3hip.h)
-  static constexpr int color = 4, komi = 8, board = 12, last = 376, atari = 416, two = 777,
-                       three = 1138, ladder = 1499, size = 1860;
 };
 
 __device__ __forceinline__ void lds_zero(char* smem, int bytes) {
@@ -127,22 +123,22 @@ __global__ void __launch_bounds__(256, 2) k_init_f32(InitF32Args a) {
   const int lr = lane & 31, h = lane >> 5;
   for (int item = blockIdx.x; item < items; item += gridDim.x) {
     const int pos = item / ncp, cp = item - pos * ncp;
-    const unsigned char* f = (const unsigned char*)a.feats + (size_t)pos * FeatOffF::size;
-    const int color = (signed char)f[FeatOffF::color];
+    const unsigned char* f = (const unsigned char*)a.feats + (size_t)pos * FeatOff::size;
+    const int color = (signed char)f[FeatOff::color];
     for (int loc = threadIdx.x; loc < kNLoc; loc += 256) {
       f32x4 p[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};   // planes 0 .. 15
       auto our = [&](int off) { return (signed char)f[off + loc] == color ? 1.0f : 0.0f; };
       auto opp = [&](int off) { return (signed char)f[off + loc] == -color ? 1.0f : 0.0f; };
-      p[0][0] = our(FeatOffF::board); p[0][1] = opp(FeatOffF::board);
-      p[1][3] = our(FeatOffF::atari); p[2][0] = opp(FeatOffF::atari);
-      p[2][1] = our(FeatOffF::two); p[2][2] = opp(FeatOffF::two);
-      p[2][3] = our(FeatOffF::three); p[3][0] = opp(FeatOffF::three);
-      p[3][1] = our(FeatOffF::ladder); p[3][2] = opp(FeatOffF::ladder);
+      p[0][0] = our(FeatOff::board); p[0][1] = opp(FeatOff::board);
+      p[1][3] = our(FeatOff::atari); p[2][0] = opp(FeatOff::atari);
+      p[2][1] = our(FeatOff::two); p[2][2] = opp(FeatOff::two);
+      p[2][3] = our(FeatOff::three); p[3][0] = opp(FeatOff::three);
+      p[3][1] = our(FeatOff::ladder); p[3][2] = opp(FeatOff::ladder);
       const int y = loc / kBL, xx = loc - y * kBL;
       float lastm[5];
 #pragma unroll
       for (int m = 0; m < 5; ++m) {
-        const int* lm = (const int*)(f + FeatOffF::last + m * 8);
+        const int* lm = (const int*)(f + FeatOff::last + m * 8);
         lastm[m] = (lm[0] == y && lm[1] == xx) ? 1.0f : 0.0f;   // pass {19,0} / noop never match
       }
       p[0][2] = lastm[0]; p[0][3] = lastm[1]; p[1][0] = lastm[2]; p[1][1] = lastm[3]; p[1][2] = lastm[4];
@@ -158,10 +154,10 @@ __global__ void __launch_bounds__(256, 2) k_init_f32(InitF32Args a) {
       gsv[1] = color == 1 ? 0.0f : 1.0f;
 #pragma unroll
       for (int m = 0; m < 5; ++m) {
-        const int* lm = (const int*)(f + FeatOffF::last + m * 8);
+        const int* lm = (const int*)(f + FeatOff::last + m * 8);
         gsv[2 + m] = (lm[0] == 19 && lm[1] == 0) ? 1.0f : 0.0f;
       }
-      gsv[7] = (color == 1 ? -1.0f : 1.0f) * (*(const float*)(f + FeatOffF::komi)) / 15.0f;
+      gsv[7] = (color == 1 ? -1.0f : 1.0f) * (*(const float*)(f + FeatOff::komi)) / 15.0f;
       const int c = cp * 64 + threadIdx.x;
       float b = a.game_b[c];
 #pragma unroll

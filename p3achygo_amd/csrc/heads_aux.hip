@@ -6,10 +6,9 @@
 // g and v channels once (139 KB) and writes one 3,360 B record; every weight is staged in LDS once per workgroup.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #include "conv_core.h"
 #include "heads_aux.h"
+#include "launch_util.h"
 
 namespace p3 {
 namespace {
@@ -196,21 +195,13 @@ __global__ void __launch_bounds__(kAuxWg) k_heads_aux(HeadsAuxArgs a) {
   }
 }
 
-struct AttrOnce { std::atomic<bool> done[32]; };
-
 }  // namespace
 
 hipError_t launch_heads_aux(const HeadsAuxArgs& a, int n_cu, hipStream_t s) {
   if (a.npos < 1 || (a.V != 32 && a.V != 48 && a.V != 64 && a.V != 80)) return hipErrorInvalidValue;
   const size_t lds = (size_t)AuxLds(80).total * 4;   // the attribute is set once: for the widest V
   static AttrOnce once;
-  int dev = 0;
-  const bool known = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 32;
-  if (!known || !once.done[dev].load(std::memory_order_acquire)) {
-    const hipError_t e = hipFuncSetAttribute((const void*)k_heads_aux, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if (known) once.done[dev].store(true, std::memory_order_release);
-  }
+  if (hipError_t e = ensure_lds(once, k_heads_aux, lds); e != hipSuccess) return e;
   const int grid = a.npos < 2 * n_cu ? a.npos : 2 * n_cu;   // 55 KB of LDS at V = 80: two workgroups per CU
   hipLaunchKernelGGL(k_heads_aux, dim3(grid), dim3(kAuxWg), (size_t)AuxLds(a.V).total * 4, s, a);
   return hipGetLastError();

@@ -20,7 +20,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "p3achygo_amd", "csrc")
-SOURCES = ["kernels.hip", "kernels.h", "conv_core.h", "conv16.h"]
+SOURCES = ["kernels.hip", "kernels.h", "conv_core.h", "conv16.h", "layer_kernels.h", "launch_util.h"]
 HEAD_MFMAS = 384          # the fused conv_last: four segments of 4 k32 steps x 24 MFMAs
 
 
@@ -94,3 +94,23 @@ def test_block_loop_of_the_c256_kernels_with_fused_broadcast_convs_touches_no_sc
         assert not inside, (key, inside[:8])
         assert all(n <= 12 for n in edge.values()), (key, dict(edge))
     assert seen >= 4
+
+
+def test_layer_wise_kernels_use_no_scratch_and_the_4_wave_layer_conv_leaves_room_for_its_pair():
+    """every k_conv1x1, k_lconv and k_bdense instantiation: no scratch; k_lconv<..., 4> runs two workgroups per CU, two
+    waves per SIMD, so 256 VGPRs each"""
+    import shutil
+    if shutil.which("hipcc") is None:
+        pytest.skip("no hipcc")
+    asm = _assembly()
+    seen = collections.Counter()
+    for m in re.finditer(r"^(_ZN2p3\d+(k_conv1x1|k_lconv|k_bdense)I(\w+?)EEEvNS_\d+\w+ArgsE):\s", asm, re.M):
+        end = asm.index(".Lfunc_end", m.start())
+        meta = asm[end:end + 4000]
+        get = lambda key: int(re.search(r"; %s: (\d+)" % key, meta).group(1))
+        seen[m.group(2)] += 1
+        assert get("ScratchSize") == 0 and "scratch_" not in asm[m.start():end], m.group(1)
+        if m.group(2) == "k_lconv" and m.group(3).endswith("ELi4"):
+            seen["k_lconv, 4 waves"] += 1
+            assert get("TotalNumVgprs") <= 256, (m.group(1), get("TotalNumVgprs"))
+    assert seen == {"k_conv1x1": 12, "k_lconv": 26, "k_lconv, 4 waves": 13, "k_bdense": 4}, seen
