@@ -335,6 +335,72 @@ int p3hip_get_score(p3hip_engine* e, int slot, float terms[P3HIP_NUM_SCORE_TERMS
 int p3hip_debug_score_rows(p3hip_engine* e, const float* move_probs, const float* value_probs, const float* score_probs,
                            const p3hip_labels* labels, int n, float* terms, double sums[P3HIP_NUM_SCORE_TERMS]);
 
+/* ---- the trainer's validation losses on the device (python/model.py:1297-1572, python/train.py:1038-1160) -----------
+ * What the reference's trainer logs per generation for a net is P3achyGoModel.compute_losses + v1_loss_terms over
+ * validation batches.  An engine created with P3HIP_FLAG_AUX holds every prediction those read on the device (the output
+ * rows and the aux records, fp32 in every precision plan); with the targets of a recorded position (p3hip_targets, built
+ * by host/tf_reader.h exactly as python/transforms.py _parse_example / _expand_common build GroundTruth) two kernels
+ * (csrc/loss.hip) compute the per-position terms and their sums.  Means, the two batch-level clips, the weights of
+ * python/loss_coeffs.py and the total are the host's (p3achygo_amd/dataset.py loss_from_sums).
+ *
+ * What is not mirrored: the trainer's `expand` draws a random symmetry per example and masks the last moves of 5 % of
+ * them (transforms.py:222, :424); the engine evaluates a position as recorded, so its number is the identity-symmetry
+ * number.  The L2 regulariser (model.losses) needs the raw kernels and is left out.
+ *
+ * The 19 terms of one position (P3HIP_LOSS_*).  KLD(t, p) is keras.metrics.kl_divergence: both arguments clipped to
+ * [1e-7f, 1], then sum t log(t / p); the clip is part of the definition (a peaked softmax has entries below it, a one-hot
+ * target contributes 361 terms of 1e-7 log(1e-7 / p)).  Huber is Keras' default, delta = 1.  The arithmetic is double
+ * on the device, every term rounded to float once.
+ *   [0]  policy             KLD(policy, softmax(pi_logits))                                        model.py:1304-1308
+ *   [1]  policy_aux_dist    has_pi_aux_dist * KLD(policy_aux_dist, softmax(pi_logits_aux))          :1314-1322
+ *   [2]  policy_aux_scalar  (1 - has_pi_aux_dist) * clip(-log_softmax(pi_logits_aux)[policy_aux], 0, 50)  :1325-1327
+ *   [3]  outcome            -sum g log_softmax(outcome_logits); g = [0,1] for score_margin > 0, [1,0] for < 0, else
+ *                           [.5,.5] (transforms.py:413-421)
+ *   [4..6] q6, q16, q50     (target - prediction)^2                                                :1331-1333
+ *   [7]  score_pdf          -log_softmax(score_logits)[k], k = clamp((int)floor(score_margin) + 400, 0, 799)
+ *                           (transforms.py:244-256)
+ *   [8]  score_cdf          sum_j (H[j >= k] - cumsum(softmax(score_logits))_j)^2                   :1340-1348
+ *   [9]  own                mean over 361 points of (own - ownership)^2                            :1351-1352
+ *   [10] gamma_sq           gamma^2 (w_gamma is the host's)                                        :1354-1357
+ *   [11] q_err              mean of three Huber((q_pred - q)^2, q_err_pred)                        :1465-1472
+ *   [12] q_score            mean of three Huber(q_score / 10, q_score_pred / 10)                   :1478-1486
+ *   [13] q_score_err        mean of three Huber((q_score_pred - q_score)^2 / 100, q_score_err_pred / 100)  :1493-1511
+ *   [14] pi_soft            KLD(policy^0.25 / sum policy^0.25, softmax(pi_logits_soft))            :1518-1527
+ *   [15] pi_optimistic      KLD(policy, softmax(pi_logits_optimistic)) * clip(sigmoid(3 (z - 1)), 0, 1), z the weighted
+ *                           mean of (q - q_pred) / sqrt(q_err_pred + 1e-6f) with c = 4/7 {3, 1.5, .75}, over 3  :1531-1564
+ *   [16] mcts_dist          has_mcts_value_dist * KLD(counts / max(sum counts, 1), softmax(mcts_dist_logits))  :1382-1393
+ *   [17] move_hit           argmax(pi_logits) == argmax(policy), the first maximum as argmax has it  train.py:1140-1144
+ *   [18] outcome_hit        (argmax(outcome_logits) == 1) == (score_margin >= 0)                   train.py:1146-1150
+ *
+ *   p3hip_load_targets  the targets of the position last loaded into `slot`; they belong to that load, as labels do
+ *                       (p3hip_load_slot / p3hip_load_slot_keyed clear them).  Accepted on any engine.  1 for a bad slot
+ *                       and for policy_aux outside 0 .. 361.  Same threading as p3hip_load_slot.
+ *   p3hip_loss          the terms of the rows of the LAST p3hip_run (or p3hip_int8_calibrate) whose slot has targets, and
+ *                       their 19 sums in double; everything p3hip_score says about rows, compaction,
+ *                       P3HIP_FLAG_RUN_ALL_SLOTS, reloaded slots, the hooks that end a run's scoring, the fixed-order sums
+ *                       and threading holds here word for word.  Fetches nothing.  Needs P3HIP_FLAG_AUX: 1 on any other
+ *                       engine, with a message that names the flag.
+ *   p3hip_get_loss      the 19 terms of `slot` from the last p3hip_loss; 2 if that call did not handle the slot.
+ *   p3hip_debug_loss_rows  test hook: writes n synthetic raw-output rows (p3hip_get_raw's layout, [n][P3HIP_RAW_LEN]) to
+ *                       their places in output rows 0 .. n - 1 and n aux records ([n][P3HIP_AUX_LEN]), runs the same
+ *                       kernels against targets[0 .. n - 1] and returns terms [n][19] and the sums.  1 <= n <= batch
+ *                       size.  Ends the last run's scoring, as p3hip_debug_score_rows does. */
+typedef struct p3hip_targets {
+  float policy[P3HIP_NUM_MOVES];
+  float policy_aux_dist[P3HIP_NUM_MOVES];
+  float own[P3HIP_NUM_LOCS];            /* from the side to move: negated for white (transforms.py:452) */
+  float mcts_value_dist[51];            /* visit counts per value bucket, as floats */
+  float score_margin, q6, q16, q50, q6_score, q16_score, q50_score;
+  int32_t policy_aux;                   /* 0 .. 361, 361 the pass */
+  int32_t has_pi_aux_dist, has_mcts_value_dist;
+} p3hip_targets;                        /* 1146 x 4 bytes */
+#define P3HIP_NUM_LOSS_TERMS 19
+int p3hip_load_targets(p3hip_engine* e, int slot, const p3hip_targets* targets);
+int p3hip_loss(p3hip_engine* e, double sums[P3HIP_NUM_LOSS_TERMS], int* n);
+int p3hip_get_loss(p3hip_engine* e, int slot, float terms[P3HIP_NUM_LOSS_TERMS]);
+int p3hip_debug_loss_rows(p3hip_engine* e, const float* raw, const float* aux, const p3hip_targets* targets, int n,
+                          float* terms, double sums[P3HIP_NUM_LOSS_TERMS]);
+
 /* ---- measurement / test hooks (not part of the reference surface) ------------------ */
 
 /* Device-resident benchmark step: runs the forward pass on whatever is already staged in

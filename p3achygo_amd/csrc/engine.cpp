@@ -188,6 +188,7 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
   e->slot_sym.assign(B, 0);
   e->row_sym.assign(B, 0);
   e->has_labels.assign(B, 0);
+  e->has_targets.assign(B, 0);
   e->load_seq.assign(B, 0);
   e->run_load_seq.assign(B, 0);
   return e;
@@ -205,6 +206,7 @@ void p3hip_destroy(p3hip_engine* e) {
   if (e->bw_mod) hipModuleUnload(e->bw_mod);
   free_cache(e->cache);
   free_scoring(e);
+  free_loss(e);
   if (e->h_feats) hipHostFree(e->h_feats);
   if (e->h_feats_compact) hipHostFree(e->h_feats_compact);
   if (e->h_out) hipHostFree(e->h_out);
@@ -223,7 +225,8 @@ int p3hip_load_slot(p3hip_engine* e, int slot, const p3hip_features* f) {
   if (slot < 0 || slot >= e->batch) return 1;
   memcpy(e->h_feats + (size_t)slot * kFeatBytes, f, kFeatBytes);
   e->slot_sym[slot] = 0;
-  e->has_labels[slot] = 0;   // labels belong to one load (p3hip_load_labels)
+  e->has_labels[slot] = 0;   // labels and targets belong to one load (p3hip_load_labels, p3hip_load_targets)
+  e->has_targets[slot] = 0;
   ++e->load_seq[slot];
   if (e->cache.on) e->cache.h_slot_keys[slot] = p3::CacheKey{0, 0, 0};   // no key: evaluated, never cached
   e->slots.loaded(slot);
@@ -236,6 +239,7 @@ int p3hip_load_slot_keyed(p3hip_engine* e, int slot, const p3hip_features* f, ui
   memcpy(e->h_feats + (size_t)slot * kFeatBytes, f, kFeatBytes);
   e->slot_sym[slot] = (unsigned char)symmetry;
   e->has_labels[slot] = 0;
+  e->has_targets[slot] = 0;
   ++e->load_seq[slot];
   if (e->cache.on) e->cache.h_slot_keys[slot] = p3::CacheKey{key_lo, key_hi, (unsigned long long)symmetry};
   e->slots.loaded(slot);

@@ -140,6 +140,22 @@ struct p3hip_engine {
     long scored_run = -1;             // run_seq that p3hip_score scored
   } scoring;
   std::vector<unsigned char> has_labels;   // [batch]
+  // The validation losses (include/p3hip.h; loss_abi.cpp, loss.hip): the twin of Scoring.  The targets live per slot in
+  // pinned memory, packed by p3hip_load_targets into the device layout of loss.h, and belong to the slot's current load
+  // (has_targets[slot], cleared by p3hip_load_slot*).  p3hip_loss gathers those of the last run's rows into h_dense /
+  // h_rows (entry k: rows h_rows[k] of d_out and d_aux); when entry k is slot k for all of them the upload comes straight
+  // from h_slot.  The buffers are made by the first p3hip_load_targets or p3hip_debug_loss_rows.
+  struct Loss {
+    std::mutex mu;
+    std::atomic<bool> ready{false};
+    float *h_slot = nullptr, *h_dense = nullptr, *d_targets = nullptr;   // [batch][kTgtStride]: pinned by slot / dense; device
+    int *h_rows = nullptr, *d_rows = nullptr;
+    float *h_terms = nullptr, *d_terms = nullptr;     // [batch][P3HIP_NUM_LOSS_TERMS]
+    double *h_sums = nullptr, *d_sums = nullptr;
+    std::vector<int> entry_of_slot;   // slot -> entry of the last p3hip_loss (-1: not handled)
+    long loss_run = -1;               // run_seq that p3hip_loss handled
+  } loss;
+  std::vector<unsigned char> has_targets;   // [batch]
   // load_seq[slot] counts the slot's loads, run_load_seq[slot] is its value when the last run gathered the slot:
   // p3hip_score leaves out a slot that was loaded again since (its labels are the new position's, its row the old one's)
   std::vector<unsigned> load_seq, run_load_seq;
@@ -177,5 +193,7 @@ bool run_pass(p3hip_engine* e, const Pass& p);
 void drop_graph(p3hip_engine* e);
 // scoring.cpp
 void free_scoring(p3hip_engine* e);
+// loss_abi.cpp
+void free_loss(p3hip_engine* e);
 
 }  // namespace eng

@@ -34,6 +34,7 @@ EXPORTS = [
     "p3hip_set_symmetries", "p3hip_symmetry_maps",
     "p3hip_load_labels", "p3hip_score", "p3hip_get_score", "p3hip_debug_score_rows",
     "p3hip_get_aux",
+    "p3hip_load_targets", "p3hip_loss", "p3hip_get_loss", "p3hip_debug_loss_rows",
 ]
 
 FLAG_RUN_ALL_SLOTS = 2
@@ -75,6 +76,27 @@ def labels_dtype() -> np.dtype:
 
 
 assert labels_dtype().itemsize == 4 * (NUM_MOVES + 2)
+
+# The validation losses on the device (include/p3hip.h, "the trainer's validation losses"): the 19
+# per-position terms of p3hip_loss in order.  The first seventeen are the per-example values of what
+# P3achyGoModel.compute_losses + v1_loss_terms return (python/model.py:1297-1572), the last two train.py val()'s hits.
+NUM_LOSS_TERMS = 19
+LOSS_TERMS = ("policy", "policy_aux_dist", "policy_aux_scalar", "outcome", "q6", "q16", "q50", "score_pdf", "score_cdf",
+              "own", "gamma_sq", "q_err", "q_score", "q_score_err", "pi_soft", "pi_optimistic", "mcts_dist", "move_hit",
+              "outcome_hit")
+NUM_V_BUCKETS = 51
+
+
+def targets_dtype() -> np.dtype:
+    """numpy mirror of p3hip_targets (include/p3hip.h): GroundTruth of python/transforms.py for one position."""
+    f, i = np.float32, np.int32
+    return np.dtype([("policy", f, (NUM_MOVES,)), ("policy_aux_dist", f, (NUM_MOVES,)), ("own", f, (361,)),
+                     ("mcts_value_dist", f, (NUM_V_BUCKETS,)), ("score_margin", f), ("q6", f), ("q16", f), ("q50", f),
+                     ("q6_score", f), ("q16_score", f), ("q50_score", f), ("policy_aux", i), ("has_pi_aux_dist", i),
+                     ("has_mcts_value_dist", i)])
+
+
+assert targets_dtype().itemsize == 4 * 1146 and len(LOSS_TERMS) == NUM_LOSS_TERMS
 
 
 class EngineError(RuntimeError):
@@ -137,6 +159,11 @@ def lib():
         L.p3hip_debug_score_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                              C.c_void_p, C.POINTER(C.c_double)]
         L.p3hip_get_aux.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.p3hip_load_targets.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.p3hip_loss.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]
+        L.p3hip_get_loss.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.p3hip_debug_loss_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                            C.POINTER(C.c_double)]
         L.p3hip_time_trunk_kernel.restype = C.c_double
         L.p3hip_time_trunk_kernel.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double),
                                               C.POINTER(C.c_char_p)]
@@ -297,6 +324,46 @@ class HipEngine:
         sums = (C.c_double * NUM_SCORE_TERMS)()
         self._ck(self._L.p3hip_debug_score_rows(self._h, mp.ctypes.data, vp.ctypes.data, sp.ctypes.data, lab.ctypes.data,
                                                 n, terms.ctypes.data, sums), "debug_score_rows")
+        return terms, np.array(sums[:], np.float64)
+
+    # -- the trainer's validation losses on the device (include/p3hip.h; python/model.py:1297-1572) ----
+    def load_targets(self, batch_id: int, targets) -> None:
+        """The targets (one targets_dtype() record, or its address) of the position last loaded into the slot; a new
+        LoadBatch of the slot clears them.  Accepted on any engine."""
+        ptr = targets.ctypes.data if isinstance(targets, np.ndarray) else targets
+        self._ck(self._L.p3hip_load_targets(self._h, batch_id, ptr), "load_targets")
+
+    def loss(self):
+        """The loss terms of the rows of the last run whose slot has targets: (sums, n), sums a float64 array in the order
+        of LOSS_TERMS (dataset.loss_from_sums turns them into the trainer's losses).  Needs FLAG_AUX.  Fetches nothing."""
+        sums = (C.c_double * NUM_LOSS_TERMS)()
+        n = C.c_int(0)
+        self._ck(self._L.p3hip_loss(self._h, sums, C.byref(n)), "loss")
+        return np.array(sums[:], np.float64), n.value
+
+    def get_loss(self, batch_id: int):
+        """The 19 terms of the slot from the last loss(), or None when that call did not handle the slot."""
+        out = np.zeros(NUM_LOSS_TERMS, np.float32)
+        rc = self._L.p3hip_get_loss(self._h, batch_id, out.ctypes.data)
+        if rc == 2:
+            return None
+        self._ck(rc, "get_loss")
+        return out
+
+    def debug_loss_rows(self, raw, aux, targets):
+        """Test hook: the terms of n synthetic rows (raw [n][RAW_LEN] in get_raw's layout, aux [n][AUX_LEN]) against
+        targets (targets_dtype()[n]); returns (terms [n][19] float32, sums [19] float64).  Overwrites the last run's
+        rows on the device."""
+        rw = np.ascontiguousarray(raw, np.float32)
+        ax = np.ascontiguousarray(aux, np.float32)
+        tg = np.ascontiguousarray(targets, targets_dtype())
+        n = len(tg)
+        if rw.shape != (n, RAW_LEN) or ax.shape != (n, AUX_LEN):
+            raise EngineError(f"debug_loss_rows: rows must be [n][{RAW_LEN}] and [n][{AUX_LEN}] for n targets")
+        terms = np.zeros((n, NUM_LOSS_TERMS), np.float32)
+        sums = (C.c_double * NUM_LOSS_TERMS)()
+        self._ck(self._L.p3hip_debug_loss_rows(self._h, rw.ctypes.data, ax.ctypes.data, tg.ctypes.data, n,
+                                               terms.ctypes.data, sums), "debug_loss_rows")
         return terms, np.array(sums[:], np.float64)
 
     # -- measurement / test hooks -------------------------------------------------------

@@ -644,5 +644,14 @@ int p3host_dataset_row(void* ds, long i, p3hip_features* f, p3hip_labels* l) {
   if (l) *l = r.labels;
   return 0;
 }
+// Copies the trainer's targets of row i (tf_reader.h ParseTargets).  0; 1: no such row; 2: the record has no targets (the
+// trainer's own parse of it would fail).  Nothing is written unless 0 is returned.
+int p3host_dataset_targets(void* ds, long i, p3hip_targets* out) {
+  if (!ds || !out || i < 0 || (size_t)i >= ((GoDataset*)ds)->size()) return 1;
+  const p3hip_targets* t = ((GoDataset*)ds)->targets((size_t)i);
+  if (!t) return 2;
+  *out = *t;
+  return 0;
+}
 void p3host_dataset_close(void* ds) { delete (GoDataset*)ds; }
 }

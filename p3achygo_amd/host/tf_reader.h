@@ -8,8 +8,12 @@
 //     3: Int64List}.  Floats packed (wire type 2) or not (wire type 5), unknown fields skipped by wire type, map
 //     entries in any order, a repeated key: the last one wins (protobuf's map semantics).
 //   * nn::GoDataset rows (cc/nn/engine/go_dataset.cc:32-123): the keys of :60-77 become a p3hip_features and a
-//     p3hip_labels; did_win = score_margin >= 0 (:114); bsize must be 19 (:81).  Every other key (own, pi_aux,
-//     pi_aux_dist, mcts_value_dist, q6 ...) is tolerated and ignored, so old-schema and new-schema records load alike.
+//     p3hip_labels; did_win = score_margin >= 0 (:114); bsize must be 19 (:81).  GoDataset reads no other key, and a
+//     row needs no other key, so old-schema and new-schema records load alike.
+//   * the trainer's targets (python/transforms.py _parse_example / _expand_common, :276-485): the other keys of EX_DESC
+//     (own, pi_aux, pi_aux_dist, mcts_value_dist, q6 .. q50_score) become a p3hip_targets beside the row, when the
+//     trainer's own parse of the record would succeed (ParseTargets below); a row without targets still loads.  No
+//     symmetry is applied and no last moves are masked: the trainer's random ones (:222, :424) are not mirrored.
 //
 // Where this reader differs from the reference, on purpose:
 //   * it never aborts (the reference CHECK-fails on a bad bsize and reads past short strings): every length is checked
@@ -278,8 +282,66 @@ struct DatasetRow {
 // pair, {0,-1} matches neither, and the move sets no plane and no pass scalar.
 inline p3hip_loc DecodeLoc16(int16_t enc) { return p3hip_loc{enc / P3HIP_BOARD_LEN, enc % P3HIP_BOARD_LEN}; }
 
-// Parses one record's payload into `row`, which is written only when the whole record is good.
-inline ReadStatus ParseDatasetRow(const uint8_t* payload, size_t len, long record, DatasetRow* row) {
+// The trainer's targets of one record, and whether it has them.
+struct RowTargets {
+  p3hip_targets targets;
+  bool has = false;
+};
+constexpr int kNumTargetKeys = 10;
+constexpr int kNumValueBuckets = 51;   // python/constants.py NUM_V_BUCKETS
+
+// GroundTruth of transforms.py:276-485 from the target keys (got, in kTargetKeys' order; bad[k]: the key's Feature was
+// malformed), the row's policy, margin and colour.  False, and *out untouched, when the trainer's parse would fail:
+// a FixedLenFeature([]) key of EX_DESC (:18-31) that is absent, of the wrong kind or not exactly one value, own not 361
+// bytes, pi_aux not one int16 in 0 .. 361, or an optional key (VarLenFeature, :23-24) that holds values of the wrong kind
+// or a first value of the wrong length.
+inline bool ParseTargets(const FeatureView* got, const bool* bad, const DatasetRow& row, p3hip_targets* out) {
+  for (int k = 0; k < kNumTargetKeys; ++k)
+    if (bad[k]) return false;
+  const FeatureView &own = got[0], &pi_aux = got[1], &dist = got[2], &mcts = got[3];
+  if (own.kind != 1 || own.n_values != 1 || own.nbytes != P3HIP_NUM_LOCS) return false;
+  if (pi_aux.kind != 1 || pi_aux.n_values != 1 || pi_aux.nbytes != 2) return false;
+  for (int k = 4; k < kNumTargetKeys; ++k)
+    if (got[k].kind != 2 || got[k].n_values != 1) return false;
+  int16_t aux;
+  std::memcpy(&aux, pi_aux.bytes, 2);
+  if (aux < 0 || aux >= P3HIP_NUM_MOVES) return false;
+  // `.values` of a VarLenFeature: empty when the key is absent, unset or an empty list (:312-333)
+  const bool has_dist = dist.kind != 0 && !(dist.kind == 1 && dist.n_values == 0);
+  const bool has_mcts = mcts.kind != 0 && !(mcts.kind == 1 && mcts.n_values == 0);
+  if (has_dist && (dist.kind != 1 || dist.nbytes != P3HIP_NUM_MOVES * 4)) return false;
+  if (has_mcts && (mcts.kind != 1 || mcts.nbytes != kNumValueBuckets * 4)) return false;
+  p3hip_targets t;
+  std::memset(&t, 0, sizeof t);
+  std::memcpy(t.policy, row.labels.policy, sizeof t.policy);
+  if (has_dist) std::memcpy(t.policy_aux_dist, dist.bytes, sizeof t.policy_aux_dist);
+  const bool white = row.features.color != 1;   // :452 `color == BLACK ? own : -own`
+  for (int i = 0; i < P3HIP_NUM_LOCS; ++i) {
+    const int v = (int8_t)own.bytes[i];
+    t.own[i] = (float)(white ? -v : v);
+  }
+  for (int b = 0; has_mcts && b < kNumValueBuckets; ++b) {
+    int32_t c;   // uint32 on the wire, decoded as int32 (:324-331), then cast to float (model.py:1383)
+    std::memcpy(&c, mcts.bytes + 4 * b, 4);
+    t.mcts_value_dist[b] = (float)c;
+  }
+  t.score_margin = row.labels.score_margin;
+  t.q6 = got[4].f0; t.q16 = got[5].f0; t.q50 = got[6].f0;
+  t.q6_score = got[7].f0; t.q16_score = got[8].f0; t.q50_score = got[9].f0;
+  t.policy_aux = aux;
+  t.has_pi_aux_dist = has_dist ? 1 : 0;
+  t.has_mcts_value_dist = has_mcts ? 1 : 0;
+  *out = t;
+  return true;
+}
+
+// Parses one record's payload into `row`, which is written only when the whole record is good; its targets, when asked
+// for, into *tg (tg->has false: the record has none, ParseTargets).
+inline ReadStatus ParseDatasetRow(const uint8_t* payload, size_t len, long record, DatasetRow* row, RowTargets* tg = nullptr) {
+  static const char* const kTargetKeys[kNumTargetKeys] = {"own", "pi_aux", "pi_aux_dist", "mcts_value_dist", "q6", "q16",
+                                                          "q50", "q6_score", "q16_score", "q50_score"};
+  FeatureView tgot[kNumTargetKeys];
+  bool tbad[kNumTargetKeys] = {};
   static const char* const kKeys[11] = {"bsize", "board", "last_moves", "stones_atari", "stones_two_liberties",
                                         "stones_three_liberties", "stones_in_ladder", "color", "pi", "score_margin", "komi"};
   static const size_t kBytes[11] = {1, P3HIP_NUM_LOCS, P3HIP_NUM_LAST_MOVES * 2, P3HIP_NUM_LOCS, P3HIP_NUM_LOCS,
@@ -315,6 +377,10 @@ inline ReadStatus ParseDatasetRow(const uint8_t* payload, size_t len, long recor
         if (key.left() != std::strlen(kKeys[k]) || std::memcmp(key.p, kKeys[k], key.left()) != 0) continue;
         if (!ParseFeature(value, &got[k])) return bad((std::string("Feature '") + kKeys[k] + "' is malformed").c_str());
       }
+      for (int k = 0; tg && k < kNumTargetKeys; ++k) {
+        if (key.left() != std::strlen(kTargetKeys[k]) || std::memcmp(key.p, kTargetKeys[k], key.left()) != 0) continue;
+        tbad[k] = !ParseFeature(value, &tgot[k]);   // a row needs none of these keys: a malformed one costs the targets only
+      }
     }
   }
   for (int k = 0; k < 11; ++k) {
@@ -347,6 +413,7 @@ inline ReadStatus ParseDatasetRow(const uint8_t* payload, size_t len, long recor
   r.labels.did_win = got[9].f0 >= 0 ? 1 : 0;   // go_dataset.cc:114 (a NaN margin is a loss there too)
   r.features.komi = got[10].f0;
   *row = r;
+  if (tg) tg->has = ParseTargets(tgot, tbad, r, &tg->targets);
   return ReadStatus{};
 }
 
@@ -365,10 +432,15 @@ class GoDataset {
   }
   size_t size() const { return rows_.size(); }
   const DatasetRow& row(size_t i) const { return rows_[i]; }
+  // the trainer's targets of row i; null when the record has none
+  const p3hip_targets* targets(size_t i) const { return target_of_[i] < 0 ? nullptr : &targets_[(size_t)target_of_[i]]; }
 
  private:
   ReadStatus Read(RecordReader& rd) {
     std::vector<DatasetRow> rows;
+    std::vector<p3hip_targets> targets;
+    std::vector<long> target_of;
+    RowTargets tg;
     for (;;) {
       const uint8_t* payload;
       size_t len;
@@ -378,14 +450,20 @@ class GoDataset {
       if (!st.ok()) return st;
       if (eof) break;
       DatasetRow row;
-      st = ParseDatasetRow(payload, len, record, &row);
+      st = ParseDatasetRow(payload, len, record, &row, &tg);
       if (!st.ok()) return st;
       rows.push_back(row);
+      target_of.push_back(tg.has ? (long)targets.size() : -1);
+      if (tg.has) targets.push_back(tg.targets);
     }
     rows_.swap(rows);
+    targets_.swap(targets);
+    target_of_.swap(target_of);
     return ReadStatus{};
   }
   std::vector<DatasetRow> rows_;
+  std::vector<p3hip_targets> targets_;   // of the rows that have them
+  std::vector<long> target_of_;          // row -> index into targets_, -1: none
 };
 
 }  // namespace p3

@@ -44,6 +44,7 @@ def lib():
             "p3host_unapply_symmetry": (None, [i32, vp]),
             "p3host_dataset_open": (vp, [C.c_char_p, i32, C.c_char_p, i32]), "p3host_dataset_size": (C.c_long, [vp]),
             "p3host_dataset_row": (i32, [vp, C.c_long, vp, vp]), "p3host_dataset_close": (None, [vp]),
+            "p3host_dataset_targets": (i32, [vp, C.c_long, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -152,6 +153,15 @@ def dataset_row(h, i: int, features_ptr, labels_ptr) -> None:
     """Copies row i into a p3hip_features and a p3hip_labels (addresses; either may be None)."""
     if lib().p3host_dataset_row(h, int(i), features_ptr, labels_ptr) != 0:
         raise IndexError(f"dataset row {i} out of range")
+
+
+def dataset_targets(h, i: int, targets_ptr) -> bool:
+    """Copies the trainer's targets of row i into a p3hip_targets (address); False, and nothing written, when the record
+    has none (a key the trainer's parse needs is missing or has the wrong length)."""
+    rc = lib().p3host_dataset_targets(h, int(i), targets_ptr)
+    if rc == 1:
+        raise IndexError(f"dataset row {i} out of range")
+    return rc == 0
 
 
 def dataset_close(h) -> None:

@@ -4,7 +4,7 @@ RunInference, p3hip_score; at most 1001 batches.  Prints the reference's stats b
 plan to profiles/dataset_benchmark.jsonl.
 
     dataset_benchmark.py WEIGHTS CHUNK... [--batch N] [--plans fp16,fp32,int8] [--calibrate CHUNK...]
-                         [--max-batches 1000] [--host-scoring] [--ab REPS]
+                         [--max-batches 1000] [--host-scoring] [--ab REPS] [--loss {rl,sl}]
 
 WEIGHTS is a .p3w file, or the name of a net of p3achygo_amd.netspec.CONFIGS (random-init weights: the timing is real, the
 accuracy figures mean nothing; this tool is for trained nets).  Plans: fp16, fp32, int8 (the INT8 plan that serves the
@@ -12,7 +12,9 @@ trunk), or int8_lw / int8_fused / int8_c128 by name.  INT8 plans are calibrated 
 dataset.calibrate_from_chunks (default: the scored chunks themselves, which flatters them).  --host-scoring scores through
 p3hip_get_slot and the numpy restatement (dataset.host_score) instead of p3hip_score.  --ab REPS runs both ways REPS
 times, interleaved on one engine, and appends their positions/s and the time of p3hip_score alone to
-profiles/dataset_score_ab.jsonl.
+profiles/dataset_score_ab.jsonl.  --loss rl | sl also prints what the reference's trainer logs for the net, train.py val()
+with LossCoeffs.RLCoeffs() or SLCoeffs() (dataset.loss_chunks: the seventeen losses averaged over batches, p3hip_loss on a
+P3HIP_FLAG_AUX engine; positions as recorded, no random symmetry, no L2 term), and adds it to the JSON line as "val".
 
 Unlike the reference a short last batch holds only the rows read, and the averages are sums / count rather than running
 means.  --warmup, --out and --ab-out only say how many warm-up runs and where the JSON lines go.  Runs on an MI355X; needs
@@ -35,11 +37,11 @@ PLAN_FLAGS = {"fp16": (0,), "fp32": (engine.FLAG_FP32_ANY,),
               "int8_lw": (engine.FLAG_INT8,), "int8_fused": (engine.FLAG_INT8_FUSED,), "int8_c128": (engine.FLAG_INT8_C128,)}
 
 
-def create(path, batch, plan):
+def create(path, batch, plan, extra=0):
     err = None
     for flags in PLAN_FLAGS[plan]:
         try:
-            return engine.HipEngine(path, batch, flags=flags), flags
+            return engine.HipEngine(path, batch, flags=flags | extra), flags | extra
         except engine.EngineError as e:
             err = e
     raise err
@@ -91,6 +93,7 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=10, help="runs of the first batch before the clock (the reference: 100)")
     ap.add_argument("--host-scoring", action="store_true")
     ap.add_argument("--ab", type=int, default=0, metavar="REPS")
+    ap.add_argument("--loss", choices=("rl", "sl"), default=None, help="also the trainer's validation losses (train.py val())")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dataset_benchmark.jsonl"))
     ap.add_argument("--ab-out", default=os.path.join(ROOT, "profiles", "dataset_score_ab.jsonl"))
     args = ap.parse_args(argv)
@@ -107,7 +110,7 @@ def main(argv=None):
     if not batch_list:
         sys.exit("the chunks hold no positions")
     for plan in args.plans.split(","):
-        eng, flags = create(path, args.batch, plan)
+        eng, flags = create(path, args.batch, plan, engine.FLAG_AUX if args.loss else 0)
         common = {"net": os.path.basename(args.weights), "random_init": random_init, "plan": plan, "flags": flags,
                   "batch": args.batch, "chunks": [os.path.basename(c) for c in args.chunks]}
         if plan.startswith("int8"):
@@ -149,7 +152,17 @@ def main(argv=None):
               f"\n  Correct Move Percentage: {st['policy_percent']:.6g}"
               f"\n  Correct Outcome Percentage: {st['outcome_percent']:.6g}"
               f"\n  Mean Score Diff: {st['score_diff']:.6g}")
-        append(args.out, dict(common, scoring="host" if args.host_scoring else "device", stats=st, **leg_record(count, t)))
+        rec = dict(common, scoring="host" if args.host_scoring else "device", stats=st, **leg_record(count, t))
+        if args.loss:
+            coeffs = dataset.LossCoeffs.rl() if args.loss == "rl" else dataset.LossCoeffs.sl()
+            val = dataset.loss_chunks(eng, args.chunks, coeffs, min(args.max_batches, 1001))
+            print(f"Validation losses ({args.loss} coefficients, {val['positions']} positions, {val['batches']} batches; as "
+                  "recorded: no symmetry, no L2 term):")
+            for k in dataset.LOSS_NAMES:
+                print(f"  {k}: {val[k]:.6g}")
+            print(f"  move accuracy: {val['move_accuracy']:.6g}\n  outcome accuracy: {val['outcome_accuracy']:.6g}")
+            rec["val"] = dict(val, coeffs=args.loss)
+        append(args.out, rec)
         eng.close()
 
 
