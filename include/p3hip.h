@@ -118,6 +118,23 @@ typedef struct p3hip_engine p3hip_engine;
                                        section 9, "Fused INT8 blocks at C = 128"); p3hip_int8_* as for
                                        P3HIP_FLAG_INT8_FUSED.  p3hip_create returns NULL for any other trunk (nbt, other
                                        widths, classic, transformers) and for any two of the three INT8 flags together */
+#define P3HIP_FLAG_INT8_ANY 2048u   /* calibrated INT8 inference whatever the conv trunk, as P3HIP_FLAG_FP32_ANY is full precision
+                                       whatever the trunk.  (384, 192) btl / nbt and classic C = 192 take the plan of
+                                       P3HIP_FLAG_INT8, (256, 128) btl with 1, 2 or 3 inner layers that of
+                                       P3HIP_FLAG_INT8_FUSED, (128, 64) btl with 1, 2 or 3 inner layers that of
+                                       P3HIP_FLAG_INT8_C128, each bit-identical to its own flag alone.  Every other trunk of
+                                       P3HIP_CONV_SET (nbt at (128, 64) and (256, 128), classic at any C, every padded or
+                                       runtime width) runs layer by layer on k_lconv_i8_any, the INT8 layer conv with its
+                                       widths as launch arguments, C and C_b zero-padded to multiples of 64 as the fp16 plan
+                                       pads them ("INT8 at any width"): the quantized tensors are the
+                                       inputs of every conv of the btl (inner layers + 2), nbt (6) and classic (2) blocks; the
+                                       raw streams, the stem, the broadcast blocks and the heads are the fp16 engine's.  With
+                                       P3HIP_CONV_ANY=1 in the environment the (384, 192) and classic C = 192 trunks run on
+                                       k_lconv_i8_any too, with the results of P3HIP_FLAG_INT8 bit for bit.  It sets no
+                                       speed target: it is slower than fp16 on every newly served trunk, 0.48-0.62x where
+                                       the fp16 plan is the fused block kernel, 0.86-0.96x elsewhere (README.md).  p3hip_int8_* as for P3HIP_FLAG_INT8; composes with the flags that does.
+                                       p3hip_create returns NULL for a transformer trunk, together with any of the three
+                                       other INT8 flags, and together with P3HIP_FLAG_FP32 / P3HIP_FLAG_FP32_TFM */
 #define P3HIP_FLAG_SYMMETRY_AVG 32u /* every slot a run evaluates is evaluated under each symmetry of the engine's set
                                        (default: all eight) and the results averaged on the device, rotated back into the
                                        orientation the slot was loaded in.  Needs 8 x batch_size <= 65536.  See
@@ -165,7 +182,8 @@ typedef struct p3hip_engine p3hip_engine;
 
 /* Conv trunks the engine runs.  (C, C_b) = (128, 64) and (256, 128) run the fused block kernels, (384, 192) and classic
  * C = 192 the templated layer-wise kernels; every other shape of the set runs layer-wise through kernels that take the
- * widths as launch arguments (csrc/conv_any.hip), in fp16 or fp32 (P3HIP_FLAG_FP32, csrc/conv_f32.hip).  There a file's C and C_b are zero-padded to the next
+ * widths as launch arguments (csrc/conv_any.hip), in fp16, fp32 (P3HIP_FLAG_FP32, csrc/conv_f32.hip) or calibrated INT8
+ * (P3HIP_FLAG_INT8_ANY, csrc/lconv_i8_any.hip).  There a file's C and C_b are zero-padded to the next
  * multiple of 64 when the weights are packed (padded channels are exactly 0 everywhere); p3hip_flops_per_position
  * counts the file's own widths, p3hip_debug_x returns the padded stream.  P3HIP_CONV_ANY=1 in the environment at
  * p3hip_create sends (384, 192) and classic C = 192 through those kernels too, with bit-identical results.
@@ -225,7 +243,7 @@ int p3hip_load_slot_keyed(p3hip_engine* e, int slot, const p3hip_features* f, ui
 int p3hip_get_slot_keyed(p3hip_engine* e, int slot, p3hip_result* out, int* symmetry, int* from_cache);
 int p3hip_cache_stats(const p3hip_engine* e, uint64_t out[4]);
 
-/* ---- calibrated INT8 (P3HIP_FLAG_INT8, P3HIP_FLAG_INT8_FUSED, P3HIP_FLAG_INT8_C128) ------------------------
+/* ---- calibrated INT8 (P3HIP_FLAG_INT8, P3HIP_FLAG_INT8_FUSED, P3HIP_FLAG_INT8_C128, P3HIP_FLAG_INT8_ANY) ------------------------
  * The quantized tensors are the inputs of every conv of the layer-wise blocks (INT8_FUSED, INT8_C128: of the btl blocks), numbered
  * block by block, conv by conv (the order of the block's .p3w convs).  Each has one symmetric activation scale
  * s_a = max |v| / 127.
@@ -421,10 +439,17 @@ int p3hip_get_raw(p3hip_engine* e, int slot, float* out);
  * algorithmic FLOPs of the convs one launch executes (inner 3x3s + 1x1 reduce/expand,
  * unpadded 361 points).  Transformer trunks: times the attention kernel k_tfm_attn and writes the FLOPs of its
  * q.k^T and p.v products over 361 x 361 tokens.  Layer-wise trunks: times the 3x3 layer conv, k_lconv<3,..>, or on an
- * INT8 engine k_lconv_i8<3,..>, and writes the FLOPs of one 3x3 conv.  A P3HIP_FLAG_FP32 engine is layer-wise whatever its
+ * INT8 engine k_lconv_i8<3,..> (P3HIP_FLAG_INT8_ANY on a trunk of its own path: k_lconv_i8_any<3>, and the FLOPs at the file's own
+ * widths), and writes the FLOPs of one 3x3 conv.  A P3HIP_FLAG_FP32 engine is layer-wise whatever its
  * trunk: it times k_lconv_f32<3> and writes the FLOPs of one 3x3 conv at the file's own widths. */
 double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
                                double* flops_per_launch, const char** kernel_name);
+/* Test hook, no device: loads the file and builds the host-side plan of (file, flags, the P3HIP_* environment) as
+ * p3hip_create would.  Returns the name of the trunk path chosen ("Fused", "Layerwise", "ConvAny", "Int8", "Int8Fused256",
+ * "Int8Fused128", "Int8Any", "F32Conv", "Tfm", ..), or NULL with the reason in p3hip_create_error().  n_q: the quantized
+ * tensors of an INT8 plan (0 otherwise); digest: a 64-bit FNV-1a hash over the int8 weight bytes and the weight scales
+ * of every quantized conv, in the plan's order (0 without any).  Either pointer may be NULL. */
+const char* p3hip_debug_plan(const char* weights_path, uint32_t flags, int* n_q, uint64_t* digest);
 /* P3HIP_FLAG_LAUNCH_GRAPH: 1 once the full-batch forward pass has been captured and is being replayed,
  * 0 before (or without the flag), -1 when the capture failed and the engine fell back to plain launches. */
 int p3hip_graph_state(const p3hip_engine* e);
@@ -438,6 +463,11 @@ int p3hip_blockw_stamps(p3hip_engine* e, unsigned long long* out, int n);
  * Transformer trunks: C is the stream's padded width (the model's d channels, then the channels up to 128, 256 or 384
  * that stay zero). */
 int p3hip_debug_x(p3hip_engine* e, float* out, int n_positions);
+/* Test hook, layer-wise INT8 engines (the paths of P3HIP_FLAG_INT8 and of P3HIP_FLAG_INT8_ANY's own plan): the int8
+ * activated copy of x that a layer-wise block stores for the layer-wise block behind it, q(mish(bn0(x))) taken from
+ * the unrounded fp32 sum, [pos][C / 16][361][16] with the padded C.  Meaningful after a pass stopped in front of such a
+ * block (P3HIP_DEBUG_STOP_BLOCK).  Returns 0, 1 on any other engine. */
+int p3hip_debug_act_i8(p3hip_engine* e, int8_t* out, int n_positions);
 /* Test hook of transformer trunks: what the last transformer block that ran left in device memory, as floats.
  * which 0, 1, 2 = q, k, v as [pos][head][384][D], the 23 padding rows 361..383 of every head included; 3 = the
  * attention output o as [pos][361][d].  It only reads buffers the forward pass owns.  The heads take o's buffer as

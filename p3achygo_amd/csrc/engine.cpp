@@ -216,6 +216,34 @@ void p3hip_destroy(p3hip_engine* e) {
   delete e;
 }
 
+const char* p3hip_debug_plan(const char* weights_path, uint32_t flags, int* n_q, uint64_t* digest) {
+  g_create_error.clear();
+  WeightFile wf;
+  Plan plan;
+  Arena ar;
+  std::string err;
+  if (!wf.load(weights_path, err) || !build_plan(wf, flags, Options::from_env(), plan, ar, err)) {
+    g_create_error = err;
+    return nullptr;
+  }
+  uint64_t h = 0;
+  bool any_q = false;
+  auto fold = [&](size_t off, size_t bytes) {
+    for (size_t i = 0; i < bytes; ++i) h = (h ^ ar.host[off + i]) * 1099511628211ull;
+  };
+  for (const BlockPlan& b : plan.blocks)
+    for (const LayerPlan& lp : b.layers)
+      if (lp.qidx >= 0) {
+        if (!any_q) h = 14695981039346656037ull;
+        any_q = true;
+        fold(lp.q_off, (size_t)lp.kw * lp.kw * lp.cin * lp.cout);
+        fold(lp.qs_off, (size_t)lp.cout * 4);
+      }
+  if (n_q) *n_q = plan.n_q;
+  if (digest) *digest = h;
+  return path_name(plan.choice.path);
+}
+
 int p3hip_kind(const p3hip_engine*) { return P3HIP_KIND_HIP; }
 const char* p3hip_path(const p3hip_engine* e) { return e->path.c_str(); }
 int p3hip_batch_size(const p3hip_engine* e) { return e->batch; }
@@ -664,6 +692,10 @@ double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
       flops = conv3 * own3 * own3;
       name = p3::lconv_any_kernel_name(3);
       break;
+    case Path::Int8Any:
+      flops = conv3 * own3 * own3;
+      name = p3::lconv_i8_any_kernel_name(3);
+      break;
     case Path::Int8:
       flops = conv3 * c3 * c3;
       name = p3::lconv_i8_kernel_name(3, c3, c3);
@@ -703,6 +735,19 @@ int p3hip_debug_x(p3hip_engine* e, float* out, int n_positions) {
   if (e->sym) { e->err = "p3hip_debug_x: not available on a P3HIP_FLAG_SYMMETRY_AVG engine"; return 1; }
   if (!e->bind() || n_positions < 1 || n_positions > e->batch) return 1;
   return read_acts(e, e->d_x, 0, (size_t)n_positions * e->wf.C * kNLoc, out);
+}
+
+// test hook (INT8 layer-wise engines): the int8 activated copy q(mish(bn0(x))) that the last layer-wise block of the pass
+// stored for the block behind it (LayerPlan region 3, d_u), [pos][C / 16][361][16]
+int p3hip_debug_act_i8(p3hip_engine* e, int8_t* out, int n_positions) {
+  const Path path = e->trunk_path();
+  if ((path != Path::Int8 && path != Path::Int8Any) || e->sym) {
+    e->err = "p3hip_debug_act_i8: only on a P3HIP_FLAG_INT8 / P3HIP_FLAG_INT8_ANY layer-wise engine without P3HIP_FLAG_SYMMETRY_AVG";
+    return 1;
+  }
+  if (!e->bind() || n_positions < 1 || n_positions > e->batch) return 1;
+  hipStreamSynchronize(e->stream);
+  return e->check(hipMemcpy(out, e->d_u, (size_t)n_positions * e->wf.C * kNLoc, hipMemcpyDeviceToHost), "D2H act") ? 0 : 2;
 }
 
 // test hook: what the last transformer block that ran left in HBM, as floats.  which 0, 1, 2: q, k, v of d_qkv,

@@ -233,7 +233,7 @@ bool timed_launch(p3hip_engine* e, int* timed, Launch&& launch) {
 
 // a 1x1 conv of the k_conv1x1 family: 0 conv_first, 1 conv_last of a broadcast block, 2 the head convs
 hipError_t launch_conv1x1(const p3hip_engine* e, int which, const p3::Conv1x1Args& a) {
-  return e->trunk_path() == Path::ConvAny ? p3::launch_conv1x1_any(e->wf.C, which, a, e->n_cu, e->stream)
+  return runs_conv_any(e->trunk_path()) ? p3::launch_conv1x1_any(e->wf.C, which, a, e->n_cu, e->stream)
                                     : p3::launch_conv1x1(e->wf.C, which, a, e->n_cu, e->stream);
 }
 
@@ -249,7 +249,7 @@ bool enqueue_stem(p3hip_engine* e, const Pass& p) {
   a.feats = p.feats; a.x = e->d_x; a.npos = p.npos;
   a.wstream = e->d_arena + pl.init_stream_off; a.nms_total = pl.init_nms;
   a.game_w = e->dev<float>(pl.game_w_off); a.game_b = e->dev<float>(pl.game_b_off);
-  return e->check(e->trunk_path() == Path::ConvAny ? p3::launch_init_any(C, a, grid_for(e, p.npos, 1), e->stream)
+  return e->check(runs_conv_any(e->trunk_path()) ? p3::launch_init_any(C, a, grid_for(e, p.npos, 1), e->stream)
                                              : p3::launch_init(C, a, grid_for(e, p.npos, 1), e->stream), "launch k_init");
 }
 
@@ -298,7 +298,7 @@ bool enqueue_broadcast_block(p3hip_engine* e, const Pass& p, const BlockPlan& bp
   d.bias = e->dev<float>(bp.dense_bias_off);
   d.scale = e->dev<float>(bp.bn[1].scale_off); d.shift = e->dev<float>(bp.bn[1].shift_off);
   if (!(bp.first_fused && bp.dense_fused) &&
-      !e->check(e->trunk_path() == Path::ConvAny ? p3::launch_bdense_any(C, d, grid_for(e, npos, 1), e->stream)
+      !e->check(runs_conv_any(e->trunk_path()) ? p3::launch_bdense_any(C, d, grid_for(e, npos, 1), e->stream)
                                            : p3::launch_bdense(C, d, grid_for(e, npos, 1), e->stream), "launch bdense")) return false;
   p3::Conv1x1Args c1{};
   c1.in = e->d_u; c1.out16 = e->d_x; c1.npos = npos;
@@ -375,15 +375,20 @@ bool enqueue_block_i8(p3hip_engine* e, const Pass& p, const BlockPlan& bp) {
   return timed_launch(e, p.timed, launch);
 }
 
-// Int8 (its callers check int8_ready): the fp16 plan's regions, an int8 tensor where that stores an activated one
+// Int8, Int8Any (their callers check int8_ready): the fp16 plan's regions, an int8 tensor where that stores an activated
+// one.  Int8Any: the same layers through k_lconv_i8_any, the (padded) widths with the launch
 bool enqueue_layerwise_block_i8(p3hip_engine* e, const Pass& p, const BlockPlan& bp) {
   const Regions<_Float16> r(e);
+  const bool any = e->trunk_path() == Path::Int8Any;
   for (const LayerPlan& lp : bp.layers) {
     p3::LConvI8Args a{};
     fill_layer(e, a, lp, r, p.npos);
     a.w = e->dev<int8_t>(lp.q_off); a.w_scale = e->dev<float>(lp.qs_off);
     a.act_scale = e->d_ascale; a.in_scale = lp.qidx; a.out_scale = lp.qidx + 1;
-    auto launch = [&] { return e->check(p3::launch_lconv_i8(lp.kw, lp.cin, lp.cout, a, e->stream), "launch k_lconv_i8"); };
+    auto launch = [&] {
+      return e->check(any ? p3::launch_lconv_i8_any(lp.kw, lp.cin, lp.cout, a, e->stream)
+                          : p3::launch_lconv_i8(lp.kw, lp.cin, lp.cout, a, e->stream), any ? "launch k_lconv_i8_any" : "launch k_lconv_i8");
+    };
     if (!timed_launch(e, lp.kw == 3 ? p.timed : nullptr, launch)) return false;
   }
   return true;
@@ -393,7 +398,7 @@ bool enqueue_layerwise_block_i8(p3hip_engine* e, const Pass& p, const BlockPlan&
 bool enqueue_layerwise_block(p3hip_engine* e, const Pass& p, const BlockPlan& bp) {
   const Regions<_Float16> r(e);
   // (Int8Fused128 calibrates through the runtime-width kernel: k_lconv has no C = 128 / C_b = 64 instantiations)
-  const bool any = e->trunk_path() == Path::ConvAny || e->trunk_path() == Path::Int8Fused128;
+  const bool any = runs_conv_any(e->trunk_path()) || e->trunk_path() == Path::Int8Fused128;
   for (const LayerPlan& lp : bp.layers) {
     if (e->calibrating) {
       // MinMax calibration: the absmax of this conv's quantized input, the activated tensor (pre: mish(bn0(x)),

@@ -182,7 +182,8 @@ hipError_t launch_bdense(int C, const BDenseArgs& a, int grid, hipStream_t s);
 // layer-wise conv: (kw, cin, cout) in {(1,384,192), (3,192,192), (1,192,384)}; two positions per workgroup
 hipError_t launch_lconv(int kw, int cin, int cout, const LConvArgs& a, int n_cu, hipStream_t s);
 hipError_t launch_heads(const HeadsArgs& a, int grid, hipStream_t s);
-bool heads_fusable(int C, int V);
+// (inline: the host-side plan asks it, and plan.cpp links without any device unit, tools/plan_sanitize_main.cpp)
+inline bool heads_fusable(int C, int V) { return (C == 128 || C == 256) && (V == 32 || V == 48 || V == 64); }
 hipError_t launch_headsx(int C, const HeadsArgs& a, int n_cu, hipStream_t s);
 
 // ---- on-device NN cache (engine.cpp p3hip_cache_*) -------------------------------------------------

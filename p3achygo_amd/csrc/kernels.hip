@@ -1278,7 +1278,6 @@ static hipError_t launch_headsx_t(const HeadsArgs& a, int n_cu, hipStream_t s) {
 }
 
 // heads with their convs inside (a.x, a.conv_a set): C in {128, 256}, V in {32, 48, 64}
-bool heads_fusable(int C, int V) { return (C == 128 || C == 256) && (V == 32 || V == 48 || V == 64); }
 hipError_t launch_headsx(int C, const HeadsArgs& a, int n_cu, hipStream_t s) {
   if (C == 256 && a.V == 64) return launch_headsx_t<256, 64>(a, n_cu, s);
   if (C == 256 && a.V == 48) return launch_headsx_t<256, 48>(a, n_cu, s);

@@ -35,9 +35,15 @@ struct AbsmaxArgs {
   unsigned* amax;
 };
 
+// k_lconv_i8<KW, CIN, COUT, ..>: the ten templated shapes of C = 384 / C_b = 192 and classic C = 192
 hipError_t launch_lconv_i8(int kw, int cin, int cout, const LConvI8Args& a, hipStream_t s);
+// k_lconv_i8_any<KW, ..>: the same body with cin and cout (multiples of 64) as launch arguments, kw 1 or 3 and the flag
+// sets the three block kinds produce; anything else: hipErrorInvalidValue.  Bit for bit the templated kernels' results
+// on their shapes (P3HIP_FLAG_INT8_ANY, DESIGN.md section 9 "INT8 at any width")
+hipError_t launch_lconv_i8_any(int kw, int cin, int cout, const LConvI8Args& a, hipStream_t s);
 hipError_t launch_absmax(const AbsmaxArgs& a, int n_cu, hipStream_t s);
-const char* lconv_i8_kernel_name(int kw, int cin, int cout);
+const char* lconv_i8_kernel_name(int kw, int cin, int cout);   // a shape without an instantiation: the runtime kernel's
+const char* lconv_i8_any_kernel_name(int kw);                  // "k_lconv_i8_any<3>" / "k_lconv_i8_any<1>"
 
 // Symmetric per-output-channel quantization of a conv's weights W (HWIO flattened [taps][cin][cout]):
 //   s_w[c] = max_k |W[k][c]| / 127,  q = clamp(rint(W / s_w[c]), -127, 127)   (s_w = 0: q = 0)

@@ -36,15 +36,67 @@ Options Options::from_env() {
   return o;
 }
 
-PlanChoice choose_plan(const WeightFile& wf, uint32_t flags, const Options& opt, std::string& err) {
+const char* path_name(Path p) {
+  switch (p) {
+    case Path::Refused: return "Refused";
+    case Path::Fused: return "Fused";
+    case Path::Blockw: return "Blockw";
+    case Path::Layerwise: return "Layerwise";
+    case Path::ConvAny: return "ConvAny";
+    case Path::Int8: return "Int8";
+    case Path::Int8Fused256: return "Int8Fused256";
+    case Path::Int8Fused128: return "Int8Fused128";
+    case Path::Int8Any: return "Int8Any";
+    case Path::F32Conv: return "F32Conv";
+    case Path::Tfm: return "Tfm";
+    case Path::TfmF32: return "TfmF32";
+  }
+  return "?";
+}
+
+PlanChoice choose_plan(const WeightFile& wf, uint32_t given_flags, const Options& opt, std::string& err) {
   const int C = wf.C, Cb = wf.Cb;
+  PlanChoice c;
+  // a conv file whose widths were padded (WeightFile::pad_conv) never takes the plan of the shape it was padded to
+  const bool exact = wf.btype == 3 || (wf.model_C == C && wf.model_Cb == Cb);
+  const bool classic = wf.btype == 2 && wf.inner == 2;                 // two 3x3 convs C -> C
+  const bool classic192 = classic && exact && C == 192;                // b15c192_classic
+  const bool bottleneck_ok = wf.btype == 1 || (wf.btype == 0 && wf.inner >= 1 && wf.inner <= 3);
+  const bool fused_shape = exact && ((C == 256 && Cb == 128) || (C == 128 && Cb == 64)) && bottleneck_ok;
+  const bool lw_shape = (exact && C == 384 && Cb == 192 && bottleneck_ok) || classic192;   // the templated k_lconv's shapes
+  // P3HIP_FLAG_INT8_ANY: INT8 whatever the conv trunk.  Its own refusals first; then a trunk one of the three other INT8
+  // flags serves takes that flag's plan (the rest of this function sees that flag, bit-identical to it alone), and every
+  // other conv trunk the path of its own, Int8Any.  P3HIP_CONV_ANY=1 sends the templated layer-wise shapes there too.
+  uint32_t flags = given_flags;
+  bool i8any = false;
+  if (flags & P3HIP_FLAG_INT8_ANY) {
+    if (wf.btype == 3) {
+      err = "P3HIP_FLAG_INT8_ANY serves the conv trunks (" P3HIP_CONV_SET "); the transformer trunks (" P3HIP_TRANSFORMER_SET
+            ") have no INT8 plan";
+      return c;
+    }
+    if (flags & (P3HIP_FLAG_INT8 | P3HIP_FLAG_INT8_FUSED | P3HIP_FLAG_INT8_C128)) {
+      err = "P3HIP_FLAG_INT8_ANY cannot be combined with P3HIP_FLAG_INT8, P3HIP_FLAG_INT8_FUSED or P3HIP_FLAG_INT8_C128: it "
+            "chooses among their plans itself";
+      return c;
+    }
+    if (flags & (P3HIP_FLAG_FP32 | P3HIP_FLAG_FP32_TFM)) {
+      err = "P3HIP_FLAG_INT8_ANY cannot be combined with P3HIP_FLAG_FP32 or P3HIP_FLAG_FP32_TFM: an engine runs one "
+            "precision plan";
+      return c;
+    }
+    flags &= ~P3HIP_FLAG_INT8_ANY;
+    const bool btl123 = wf.btype == 0 && wf.inner >= 1 && wf.inner <= 3;
+    if (lw_shape && !opt.conv_any) flags |= P3HIP_FLAG_INT8;
+    else if (fused_shape && btl123) flags |= C == 256 ? P3HIP_FLAG_INT8_FUSED : P3HIP_FLAG_INT8_C128;
+    else i8any = true;
+  }
   const bool int8 = (flags & (P3HIP_FLAG_INT8 | P3HIP_FLAG_INT8_FUSED | P3HIP_FLAG_INT8_C128)) != 0;
   const bool i8f = (flags & (P3HIP_FLAG_INT8_FUSED | P3HIP_FLAG_INT8_C128)) != 0;
   const bool i8c = (flags & P3HIP_FLAG_INT8_C128) != 0;
   // P3HIP_FLAG_FP32 serves the conv trunks, P3HIP_FLAG_FP32_TFM the transformers; both together: whatever the trunk
   const bool f32_conv = (flags & P3HIP_FLAG_FP32) != 0, f32_tfm = (flags & P3HIP_FLAG_FP32_TFM) != 0;
   const bool f32 = f32_conv || f32_tfm;
-  PlanChoice c;
   if (f32 && wf.btype == 3 && !f32_tfm) {
     err = "P3HIP_FLAG_FP32 serves the conv trunks only (" P3HIP_CONV_SET "); the transformer trunks run in fp16, or in "
           "fp32 with P3HIP_FLAG_FP32_TFM";
@@ -61,26 +113,20 @@ PlanChoice choose_plan(const WeightFile& wf, uint32_t flags, const Options& opt,
           "engine runs one precision plan";
     return c;
   }
-  // a conv file whose widths were padded (WeightFile::pad_conv) never takes the plan of the shape it was padded to
-  const bool exact = wf.btype == 3 || (wf.model_C == C && wf.model_Cb == Cb);
-  const bool fused = !i8f && !f32 && exact && ((C == 256 && Cb == 128) || (C == 128 && Cb == 64));
-  const bool classic = wf.btype == 2 && wf.inner == 2;                 // two 3x3 convs C -> C
-  const bool classic192 = classic && exact && C == 192;                // b15c192_classic
-  const bool bottleneck_ok = wf.btype == 1 || (wf.btype == 0 && wf.inner >= 1 && wf.inner <= 3);
+  const bool fused = !i8any && !i8f && !f32 && exact && ((C == 256 && Cb == 128) || (C == 128 && Cb == 64));
   // P3HIP_FLAG_INT8_FUSED: the btl trunks of the fused block kernel's C = 256 width; P3HIP_FLAG_INT8_C128: those of its
   // C = 128 width; each alone among the three INT8 flags
   const uint32_t i8_flags = flags & (P3HIP_FLAG_INT8 | P3HIP_FLAG_INT8_FUSED | P3HIP_FLAG_INT8_C128);
   const bool i8_alone = (i8_flags & (i8_flags - 1)) == 0;
   const bool i8f_ok = i8f && i8_alone && exact && (i8c ? (C == 128 && Cb == 64) : (C == 256 && Cb == 128)) && wf.btype == 0 &&
                       wf.inner >= 1 && wf.inner <= 3;
-  const bool fused_shape = exact && ((C == 256 && Cb == 128) || (C == 128 && Cb == 64)) && bottleneck_ok;
-  const bool lw_shape = (exact && C == 384 && Cb == 192 && bottleneck_ok) || classic192;   // the templated k_lconv's shapes
-  // every other conv trunk of P3HIP_CONV_SET: layer-wise through conv_any.hip, C and Cb padded to multiples of 64
-  const bool any = !fused_shape && !lw_shape &&
-                   WeightFile::conv_set(wf.model_C, wf.model_Cb, wf.btype, wf.inner, wf.bint) && C % 64 == 0 &&
-                   (wf.btype == 2 || Cb % 64 == 0);
-  // (P3HIP_FLAG_FP32 runs the fused shapes layer by layer too)
-  const bool layerwise = lw_shape || i8f_ok || any || (f32 && fused_shape);
+  // a conv trunk of P3HIP_CONV_SET, C and Cb padded to multiples of 64
+  const bool conv_ok = WeightFile::conv_set(wf.model_C, wf.model_Cb, wf.btype, wf.inner, wf.bint) && C % 64 == 0 &&
+                       (wf.btype == 2 || Cb % 64 == 0);
+  // every other conv trunk of P3HIP_CONV_SET: layer-wise through conv_any.hip
+  const bool any = !fused_shape && !lw_shape && conv_ok;
+  // (P3HIP_FLAG_FP32 runs the fused shapes layer by layer too, and so does Int8Any: the nbt ones, and classic C = 128)
+  const bool layerwise = lw_shape || i8f_ok || any || (f32 && fused_shape) || (i8any && conv_ok);
   const bool v_ok = wf.V == 32 || wf.V == 48 || wf.V == 64 || wf.V == 80;
   // transformer trunk: the file's C is the model width d and Cb the head count (include/p3hip.h: d a multiple of 32,
   // 64 <= d <= 384, head width d / heads 32 or 64); the stream is padded to C = p3::tfm_stream_width(d), and V is what
@@ -126,6 +172,7 @@ PlanChoice choose_plan(const WeightFile& wf, uint32_t flags, const Options& opt,
   // layer-wise; k_blockw serves C = 256 / C_b = 128 btl trunks, whose inner count bottleneck_ok has checked.)
   if (tfm) c.path = f32 ? Path::TfmF32 : Path::Tfm;
   else if (f32) c.path = Path::F32Conv;
+  else if (i8any) c.path = Path::Int8Any;
   else if (i8f) c.path = i8c ? Path::Int8Fused128 : Path::Int8Fused256;
   else if (int8) c.path = Path::Int8;
   else if (any || (opt.conv_any && lw_shape)) c.path = Path::ConvAny;
@@ -136,7 +183,7 @@ PlanChoice choose_plan(const WeightFile& wf, uint32_t flags, const Options& opt,
   c.CB = layerwise ? p3::conv_any_slice(C) : (tfm ? 128 : Cb);
   c.CPI = layerwise ? p3::conv_any_init_pass(C) : 128;
   c.heads_image = !f32 && p3::heads_fusable(C, wf.V);
-  c.heads_fused = c.heads_image && opt.heads_fuse && c.path != Path::ConvAny;
+  c.heads_fused = c.heads_image && opt.heads_fuse && !runs_conv_any(c.path);
   if (tfm) {
     c.tfm_heads = Cb;
     c.tfm_D = wf.model_C / Cb;

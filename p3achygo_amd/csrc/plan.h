@@ -30,7 +30,8 @@ struct Options {
   bool time_run = false;   // P3HIP_TIME_RUN: p3hip_run times its stages (a measurement aid)
   bool blockw = false;     // P3HIP_BLOCKW=1: C = 256 / C_b = 128 btl runs through k_blockw (csrc/asm/blockw_gen.py)
   bool blockw_diag = false;   // P3HIP_BLOCKW_DIAG: the _diag twin, which writes the engine's d_bw_stamps
-  bool conv_any = false;   // P3HIP_CONV_ANY=1: the templated layer-wise shapes through conv_any.hip too
+  bool conv_any = false;   // P3HIP_CONV_ANY=1: the templated layer-wise shapes through conv_any.hip too (and, with
+                           // P3HIP_FLAG_INT8_ANY, through k_lconv_i8_any)
   static Options from_env();
 };
 
@@ -45,6 +46,8 @@ enum class Path {
   Int8,           // P3HIP_FLAG_INT8: k_lconv_i8 on the templated layer-wise shapes
   Int8Fused256,   // P3HIP_FLAG_INT8_FUSED: k_block_i8 per btl block at C = 256 / C_b = 128
   Int8Fused128,   // P3HIP_FLAG_INT8_C128: the same at C = 128 / C_b = 64 (block_i8_c128.hip)
+  Int8Any,        // P3HIP_FLAG_INT8_ANY on every trunk the three above do not serve: k_lconv_i8_any, widths as launch
+                  // arguments; stem, broadcast blocks and heads as ConvAny's
   F32Conv,        // P3HIP_FLAG_FP32: every conv trunk layer by layer through conv_f32.hip
   Tfm,            // transformer trunk, fp16
   TfmF32,         // P3HIP_FLAG_FP32_TFM: transformer trunk through transformer_f32.hip
@@ -53,7 +56,9 @@ inline bool is_tfm(Path p) { return p == Path::Tfm || p == Path::TfmF32; }
 inline bool is_f32(Path p) { return p == Path::F32Conv || p == Path::TfmF32; }
 inline bool is_int8_fused(Path p) { return p == Path::Int8Fused256 || p == Path::Int8Fused128; }
 // (an INT8 engine calibrates through the fp16 layer-wise plan: `calibrating` is a run-time state of the engine)
-inline bool is_int8(Path p) { return p == Path::Int8 || is_int8_fused(p); }
+inline bool is_int8(Path p) { return p == Path::Int8 || p == Path::Int8Any || is_int8_fused(p); }
+// the stem, the broadcast blocks, the head convs and the fp16 layer convs (calibration) through conv_any.hip
+inline bool runs_conv_any(Path p) { return p == Path::ConvAny || p == Path::Int8Any; }
 // conv blocks planned conv by conv (BlockPlan kind 4)
 inline bool is_layerwise(Path p) { return p == Path::Layerwise || p == Path::ConvAny || is_int8(p) || p == Path::F32Conv; }
 inline size_t act_bytes(Path p) { return is_f32(p) ? 4 : 2; }   // bytes per activation element of d_x, d_t, d_u, d_qkv
@@ -66,6 +71,8 @@ struct PlanChoice {
   bool heads_fused = false;   // k_headsx runs: the head convs inside the heads kernel (P3HIP_NO_HFUSE, conv_any clear it)
   int tfm_heads = 0, tfm_D = 0;   // transformer: head count and head width (model width wf.model_C = heads x D)
 };
+
+const char* path_name(Path p);   // "Fused", "Int8Any", ..: the enumerator's name (p3hip_debug_plan)
 
 // Pure: every refusal of an engine's creation that depends on the file's architecture and the flags, in their order of
 // precedence, and the path of an engine that is served.

@@ -35,6 +35,7 @@ EXPORTS = [
     "p3hip_load_labels", "p3hip_score", "p3hip_get_score", "p3hip_debug_score_rows",
     "p3hip_get_aux",
     "p3hip_load_targets", "p3hip_loss", "p3hip_get_loss", "p3hip_debug_loss_rows",
+    "p3hip_debug_plan", "p3hip_debug_act_i8",
 ]
 
 FLAG_RUN_ALL_SLOTS = 2
@@ -43,6 +44,8 @@ FLAG_LAUNCH_GRAPH = 8
 FLAG_INT8 = 16   # calibrated INT8 convs in the layer-wise blocks (include/p3hip.h)
 FLAG_INT8_FUSED = 64   # calibrated INT8 of the C = 256 btl trunks, one fused int8 block kernel per block (section 9)
 FLAG_INT8_C128 = 128   # the same for the C = 128 / C_b = 64 btl trunks (b12c128btl3): k_block_i8<128,64>, two workgroups per CU
+FLAG_INT8_ANY = 2048   # calibrated INT8 whatever the conv trunk: the plan of one of the three flags above where one serves it,
+# else layer by layer on k_lconv_i8_any at the padded widths (include/p3hip.h, DESIGN.md section 9 "INT8 at any width")
 FLAG_FP32 = 256   # the conv trunks layer by layer in fp32, weights and activations included
 FLAG_FP32_TFM = 512   # the transformer trunks in fp32, weights and activations included
 FLAG_FP32_ANY = FLAG_FP32 | FLAG_FP32_TFM   # full precision whatever the trunk
@@ -164,6 +167,8 @@ def lib():
         L.p3hip_get_loss.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.p3hip_debug_loss_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                             C.POINTER(C.c_double)]
+        L.p3hip_debug_plan.restype = C.c_char_p
+        L.p3hip_debug_plan.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]
         L.p3hip_time_trunk_kernel.restype = C.c_double
         L.p3hip_time_trunk_kernel.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double),
                                               C.POINTER(C.c_char_p)]
@@ -256,7 +261,7 @@ class HipEngine:
         self._L.p3hip_cache_stats(self._h, out)
         return {"lookups": out[0], "hits": out[1], "stored": out[2], "entries": out[3]}
 
-    # -- calibrated INT8 (FLAG_INT8, FLAG_INT8_FUSED, FLAG_INT8_C128) --------------------
+    # -- calibrated INT8 (FLAG_INT8, FLAG_INT8_FUSED, FLAG_INT8_C128, FLAG_INT8_ANY) -----
     def int8_calibrate(self) -> None:
         """RunInference on the fp16 plan that also folds every quantized tensor's max |v| into the engine's running
         maxima (MinMax calibration): load a calibration batch, call this, fetch results as usual if wanted.  Any of
@@ -445,6 +450,14 @@ class HipEngine:
             raise EngineError("no k_blockw stamps (engine not created with P3HIP_BLOCKW_DIAG)")
         return out.reshape(8, 16, 4, 24)
 
+    def debug_act_i8(self, n: int, channels: int) -> np.ndarray:
+        """INT8 layer-wise engines: the int8 activated copy of x the last layer-wise block of the pass stored for the
+        block behind it, as codes [n][channels][361] (channels: the padded C)"""
+        out = np.zeros(n * channels * 361, np.int8)
+        self._L.p3hip_debug_act_i8.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        self._ck(self._L.p3hip_debug_act_i8(self._h, out.ctypes.data, n), "debug_act_i8")
+        return out.reshape(n, channels // 16, 361, 16).transpose(0, 1, 3, 2).reshape(n, channels, 361)
+
     def graph_state(self) -> int:
         """P3HIP_FLAG_LAUNCH_GRAPH: 1 replaying the captured forward pass, 0 not (yet), -1 capture failed."""
         self._L.p3hip_graph_state.argtypes = [C.c_void_p]
@@ -477,6 +490,18 @@ def aux_outputs(rec) -> dict:
     if rec.shape[-1] != AUX_LEN:
         raise ValueError(f"an aux record has {AUX_LEN} floats, not {rec.shape[-1]}")
     return {k: rec[..., a:b] for k, (a, b) in AUX_SEGMENTS.items()}
+
+
+def debug_plan(path: str, flags: int = 0):
+    """(trunk path name, quantized tensors, digest of the int8 weights and weight scales) of the host-side plan that
+    p3hip_create would build for (file, flags, the P3HIP_* environment): p3hip_debug_plan, no device needed.  Raises
+    EngineError with p3hip_create's reason where that returns NULL."""
+    L = lib()
+    n_q, dig = C.c_int(0), C.c_uint64(0)
+    name = L.p3hip_debug_plan(path.encode(), flags, C.byref(n_q), C.byref(dig))
+    if name is None:
+        raise EngineError("p3hip_create: " + L.p3hip_create_error().decode())
+    return name.decode(), n_q.value, dig.value
 
 
 def rope_table():
