@@ -171,6 +171,26 @@ typedef struct p3hip_engine p3hip_engine;
                                        and P3HIP_FLAG_LAUNCH_GRAPH.  p3hip_create returns NULL together with
                                        P3HIP_FLAG_SYMMETRY_AVG, and p3hip_cache_enable fails on such an engine */
 
+#define P3HIP_FLAG_LOW_LATENCY 4096u /* a plan for runs of 1 to about 64 positions (a GTP service or an evaluation match with a
+                                       few search threads, cc/gtp/service.cc:708-720): every trunk of P3HIP_CONV_SET runs in
+                                       fp16, layer by layer, through k_sconv (csrc/conv_split.hip), which splits a position
+                                       into row strips and output-channel tiles across many workgroups, where every other
+                                       plan gives a position to one workgroup and leaves the other CUs idle.  The stem, the
+                                       broadcast dense and the heads are those of the runtime-width plan.  Results are fp16
+                                       with the rounding points of the layer-wise plan (DESIGN.md sections 7 and 15), the
+                                       same bits at every batch size, in every slot and for every split.  It costs throughput
+                                       at large batches.  Measured forward-pass time over the default plan's at batch
+                                       1 / 8 / 32, launch graph on both: b12c256btl3 0.84 / 0.87 /
+                                       1.20, b14c384btl3 0.97 / 1.06 / 1.63, b15c192_classic 0.95 / 0.98 / 1.41, b12c128btl3
+                                       1.17 / 1.19 / 1.44; the default plan is the faster one from batch 32, 8, 16 and 1 on,
+                                       by up to 3.8x at batch 256.  Composes with P3HIP_FLAG_RUN_ALL_SLOTS,
+                                       P3HIP_FLAG_SHARED_DEVICE, P3HIP_FLAG_LAUNCH_GRAPH, P3HIP_FLAG_SYMMETRY_AVG, P3HIP_FLAG_AUX, the NN cache,
+                                       p3hip_score and p3hip_loss.  P3HIP_BLOCKW is ignored.  P3HIP_SPLIT="S,T" in the
+                                       environment at p3hip_create forces S row strips (1, 2, 4) and T-channel tiles (16, 32,
+                                       64) for every launch (tests, A/B runs).  p3hip_create returns NULL for a transformer
+                                       trunk, together with any INT8 flag, together with P3HIP_FLAG_FP32 or
+                                       P3HIP_FLAG_FP32_TFM, and for a P3HIP_SPLIT outside those sets */
+
 /* Transformer trunks (python/model_transformer.py TransformerBlock, a generic_arch of "transformer" blocks) the engine
  * runs: every block has the same embed_dim d and num_heads h, d equals the stem's channels, d is a multiple of 32 with
  * 64 <= d <= 384, the head width d / h is 32 or 64; any block count the .p3w header allows; H = 32 and V what the heads
@@ -441,7 +461,8 @@ int p3hip_get_raw(p3hip_engine* e, int slot, float* out);
  * q.k^T and p.v products over 361 x 361 tokens.  Layer-wise trunks: times the 3x3 layer conv, k_lconv<3,..>, or on an
  * INT8 engine k_lconv_i8<3,..> (P3HIP_FLAG_INT8_ANY on a trunk of its own path: k_lconv_i8_any<3>, and the FLOPs at the file's own
  * widths), and writes the FLOPs of one 3x3 conv.  A P3HIP_FLAG_FP32 engine is layer-wise whatever its
- * trunk: it times k_lconv_f32<3> and writes the FLOPs of one 3x3 conv at the file's own widths. */
+ * trunk: it times k_lconv_f32<3> and writes the FLOPs of one 3x3 conv at the file's own widths; so is a
+ * P3HIP_FLAG_LOW_LATENCY engine, with k_sconv<3>. */
 double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
                                double* flops_per_launch, const char** kernel_name);
 /* Test hook, no device: loads the file and builds the host-side plan of (file, flags, the P3HIP_* environment) as
@@ -450,6 +471,13 @@ double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
  * tensors of an INT8 plan (0 otherwise); digest: a 64-bit FNV-1a hash over the int8 weight bytes and the weight scales
  * of every quantized conv, in the plan's order (0 without any).  Either pointer may be NULL. */
 const char* p3hip_debug_plan(const char* weights_path, uint32_t flags, int* n_q, uint64_t* digest);
+/* Test hooks, no device (P3HIP_FLAG_LOW_LATENCY).  p3hip_debug_split: the row strips and the output-channel tile a
+ * k_sconv launch of kernel size kw over npos positions and cout output channels takes on a device of n_cu CUs, the
+ * P3HIP_SPLIT override included; 0, or 1 for a bad argument or a bad P3HIP_SPLIT.  p3hip_debug_pack_sconv: the kernel's
+ * weight image (csrc/conv_split.h pack_sconv) of W[taps][cin][cout] padded to cin_pad x cout_pad (multiples of 64), as
+ * raw fp16 bits; returns the number of elements, writes at most n of them. */
+int p3hip_debug_split(int npos, int kw, int cout, int n_cu, int* strips, int* tile);
+long p3hip_debug_pack_sconv(const float* w, int taps, int cin, int cout, int cin_pad, int cout_pad, uint16_t* out, long n);
 /* P3HIP_FLAG_LAUNCH_GRAPH: 1 once the full-batch forward pass has been captured and is being replayed,
  * 0 before (or without the flag), -1 when the capture failed and the engine fell back to plain launches. */
 int p3hip_graph_state(const p3hip_engine* e);

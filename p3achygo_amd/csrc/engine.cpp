@@ -24,6 +24,7 @@
 #include "block_i8.h"
 #include "conv_any.h"
 #include "conv_f32.h"
+#include "conv_split.h"
 #include "lconv_i8.h"
 #include "transformer.h"
 #include "transformer_f32.h"
@@ -242,6 +243,21 @@ const char* p3hip_debug_plan(const char* weights_path, uint32_t flags, int* n_q,
   if (n_q) *n_q = plan.n_q;
   if (digest) *digest = h;
   return path_name(plan.choice.path);
+}
+
+int p3hip_debug_split(int npos, int kw, int cout, int n_cu, int* strips, int* tile) {
+  const Options opt = Options::from_env();
+  if (npos < 1 || (kw != 1 && kw != 3) || cout < 64 || cout % 64 != 0 || n_cu < 1 || !strips || !tile || opt.split_bad) return 1;
+  if (opt.split_s) { *strips = opt.split_s; *tile = opt.split_t; }
+  else p3::sconv_split(npos, kw, cout, n_cu, strips, tile);
+  return 0;
+}
+
+long p3hip_debug_pack_sconv(const float* w, int taps, int cin, int cout, int cin_pad, int cout_pad, uint16_t* out, long n) {
+  std::vector<_Float16> img;
+  p3::pack_sconv(img, w, taps, cin, cout, cin_pad, cout_pad);
+  for (long i = 0; i < n && i < (long)img.size(); ++i) memcpy(out + i, &img[i], 2);
+  return (long)img.size();
 }
 
 int p3hip_kind(const p3hip_engine*) { return P3HIP_KIND_HIP; }
@@ -691,6 +707,10 @@ double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
     case Path::ConvAny:
       flops = conv3 * own3 * own3;
       name = p3::lconv_any_kernel_name(3);
+      break;
+    case Path::Split:
+      flops = conv3 * own3 * own3;
+      name = p3::sconv_kernel_name(3);
       break;
     case Path::Int8Any:
       flops = conv3 * own3 * own3;

@@ -5,6 +5,7 @@
 #include "block_i8.h"
 #include "conv_any.h"
 #include "conv_f32.h"
+#include "conv_split.h"
 #include "engine.h"
 #include "lconv_i8.h"
 #include "transformer.h"
@@ -284,6 +285,34 @@ bool enqueue_tfm_block_f32(p3hip_engine* e, const Pass& p, const BlockPlan& bp) 
   return e->check(p3::launch_tfm_ffn_f32(f, s), "launch k_tfm_ffn_f32");
 }
 
+// The split of a k_sconv launch: P3HIP_SPLIT's, or the launch's own choice
+void set_split(const p3hip_engine* e, int kw, p3::SConvArgs& a) {
+  if (e->opt.split_s) { a.strips = e->opt.split_s; a.tile = e->opt.split_t; }
+  else p3::sconv_split(a.npos, kw, a.cout, e->n_cu, &a.strips, &a.tile);
+}
+
+// Split: conv_first and conv_last through k_sconv, the dense as ConvAny's
+bool enqueue_broadcast_block_split(p3hip_engine* e, const Pass& p, const BlockPlan& bp) {
+  const int C = e->wf.C, npos = p.npos;
+  p3::SConvArgs c0{};   // t = mish(conv_first(mish(bn0(x))))
+  c0.in = e->d_x; c0.out = e->d_t; c0.npos = npos; c0.cin = c0.cout = C; c0.w = e->d_arena + bp.ws_first;
+  c0.pre = 1; c0.act = 2;
+  c0.scale_in = e->dev<float>(bp.bn[0].scale_off); c0.shift_in = e->dev<float>(bp.bn[0].shift_off);
+  set_split(e, 1, c0);
+  if (!e->check(p3::launch_sconv(1, c0, e->n_cu, e->stream), "launch conv_first (k_sconv)")) return false;
+  p3::BDenseArgs d{};
+  d.t = e->d_t; d.u = e->d_u; d.npos = npos;
+  d.wstream = e->d_arena + bp.stream2_off; d.nms_total = bp.nms2;
+  d.bias = e->dev<float>(bp.dense_bias_off);
+  d.scale = e->dev<float>(bp.bn[1].scale_off); d.shift = e->dev<float>(bp.bn[1].shift_off);
+  if (!e->check(p3::launch_bdense_any(C, d, grid_for(e, npos, 1), e->stream), "launch bdense")) return false;
+  p3::SConvArgs c1{};   // x += conv_last(u)
+  c1.in = e->d_u; c1.out = e->d_x; c1.npos = npos; c1.cin = c1.cout = C; c1.w = e->d_arena + bp.ws_last;
+  c1.res = 1;
+  set_split(e, 1, c1);
+  return e->check(p3::launch_sconv(1, c1, e->n_cu, e->stream), "launch conv_last (k_sconv)");
+}
+
 // A broadcast block in fp16: whatever of conv_first, dense and conv_last the neighbouring block launches did not take
 bool enqueue_broadcast_block(p3hip_engine* e, const Pass& p, const BlockPlan& bp) {
   const int C = e->wf.C, npos = p.npos;
@@ -351,6 +380,19 @@ bool enqueue_layerwise_block_f32(p3hip_engine* e, const Pass& p, const BlockPlan
     fill_layer(e, a, lp, r, p.npos);
     a.cin = lp.cin; a.cout = lp.cout; a.w = e->dev<float>(lp.w32_off);
     auto launch = [&] { return e->check(p3::launch_lconv_f32(lp.kw, a, e->n_cu, e->stream), "launch k_lconv_f32"); };
+    if (!timed_launch(e, lp.kw == 3 ? p.timed : nullptr, launch)) return false;
+  }
+  return true;
+}
+
+bool enqueue_layerwise_block_split(p3hip_engine* e, const Pass& p, const BlockPlan& bp) {
+  const Regions<_Float16> r(e);
+  for (const LayerPlan& lp : bp.layers) {
+    p3::SConvArgs a{};
+    fill_layer(e, a, lp, r, p.npos);
+    a.cin = lp.cin; a.cout = lp.cout; a.w = e->d_arena + lp.ws_off;
+    set_split(e, lp.kw, a);
+    auto launch = [&] { return e->check(p3::launch_sconv(lp.kw, a, e->n_cu, e->stream), "launch k_sconv"); };
     if (!timed_launch(e, lp.kw == 3 ? p.timed : nullptr, launch)) return false;
   }
   return true;
@@ -516,10 +558,12 @@ bool enqueue_forward(p3hip_engine* e, const Pass& p) {
         ok = path == Path::TfmF32 ? enqueue_tfm_block_f32(e, p, bp) : enqueue_tfm_block(e, p, bp);
         break;
       case 3:
-        ok = path == Path::F32Conv ? enqueue_broadcast_block_f32(e, p, bp) : enqueue_broadcast_block(e, p, bp);
+        ok = path == Path::F32Conv ? enqueue_broadcast_block_f32(e, p, bp)
+             : path == Path::Split ? enqueue_broadcast_block_split(e, p, bp) : enqueue_broadcast_block(e, p, bp);
         break;
       case 4:
         if (path == Path::F32Conv) ok = enqueue_layerwise_block_f32(e, p, bp);
+        else if (path == Path::Split) ok = enqueue_layerwise_block_split(e, p, bp);
         else if (is_int8(path) && !e->calibrating)
           ok = is_int8_fused(path) ? enqueue_block_i8(e, p, bp) : enqueue_layerwise_block_i8(e, p, bp);
         else ok = enqueue_layerwise_block(e, p, bp);

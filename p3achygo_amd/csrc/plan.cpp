@@ -3,12 +3,14 @@
 #include "plan.h"
 
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <utility>
 
 #include "../../include/p3hip.h"
 #include "conv_any.h"
 #include "conv_f32.h"
+#include "conv_split.h"
 #include "lconv_i8.h"
 #include "transformer.h"
 #include "transformer_f32.h"
@@ -33,6 +35,13 @@ Options Options::from_env() {
   o.blockw = num("P3HIP_BLOCKW", 0) != 0;
   o.blockw_diag = set("P3HIP_BLOCKW_DIAG");
   o.conv_any = num("P3HIP_CONV_ANY", 0) != 0;
+  if (const char* sp = getenv("P3HIP_SPLIT")) {
+    char tail = 0;
+    if (sscanf(sp, "%d,%d%c", &o.split_s, &o.split_t, &tail) != 2 || !p3::sconv_split_valid(o.split_s, o.split_t)) {
+      o.split_s = o.split_t = 0;
+      o.split_bad = true;
+    }
+  }
   return o;
 }
 
@@ -48,6 +57,7 @@ const char* path_name(Path p) {
     case Path::Int8Fused128: return "Int8Fused128";
     case Path::Int8Any: return "Int8Any";
     case Path::F32Conv: return "F32Conv";
+    case Path::Split: return "Split";
     case Path::Tfm: return "Tfm";
     case Path::TfmF32: return "TfmF32";
   }
@@ -68,6 +78,29 @@ PlanChoice choose_plan(const WeightFile& wf, uint32_t given_flags, const Options
   // flags serves takes that flag's plan (the rest of this function sees that flag, bit-identical to it alone), and every
   // other conv trunk the path of its own, Int8Any.  P3HIP_CONV_ANY=1 sends the templated layer-wise shapes there too.
   uint32_t flags = given_flags;
+  // P3HIP_FLAG_LOW_LATENCY: every conv trunk in fp16 through k_sconv, and nothing else
+  const bool split = (flags & P3HIP_FLAG_LOW_LATENCY) != 0;
+  if (split) {
+    if (wf.btype == 3) {
+      err = "P3HIP_FLAG_LOW_LATENCY serves the conv trunks (" P3HIP_CONV_SET "); the transformer trunks (" P3HIP_TRANSFORMER_SET
+            ") have no low-latency plan";
+      return c;
+    }
+    if (flags & (P3HIP_FLAG_INT8 | P3HIP_FLAG_INT8_FUSED | P3HIP_FLAG_INT8_C128 | P3HIP_FLAG_INT8_ANY)) {
+      err = "P3HIP_FLAG_LOW_LATENCY cannot be combined with P3HIP_FLAG_INT8, P3HIP_FLAG_INT8_FUSED, P3HIP_FLAG_INT8_C128 or "
+            "P3HIP_FLAG_INT8_ANY: its kernel runs in fp16";
+      return c;
+    }
+    if (flags & (P3HIP_FLAG_FP32 | P3HIP_FLAG_FP32_TFM)) {
+      err = "P3HIP_FLAG_LOW_LATENCY cannot be combined with P3HIP_FLAG_FP32 or P3HIP_FLAG_FP32_TFM: its kernel runs in fp16";
+      return c;
+    }
+    if (opt.split_bad) {
+      err = "P3HIP_FLAG_LOW_LATENCY: P3HIP_SPLIT must be \"S,T\" with S row strips of 1, 2 or 4 and output tiles of T = 16, 32 "
+            "or 64 channels";
+      return c;
+    }
+  }
   bool i8any = false;
   if (flags & P3HIP_FLAG_INT8_ANY) {
     if (wf.btype == 3) {
@@ -113,7 +146,7 @@ PlanChoice choose_plan(const WeightFile& wf, uint32_t given_flags, const Options
           "engine runs one precision plan";
     return c;
   }
-  const bool fused = !i8any && !i8f && !f32 && exact && ((C == 256 && Cb == 128) || (C == 128 && Cb == 64));
+  const bool fused = !split && !i8any && !i8f && !f32 && exact && ((C == 256 && Cb == 128) || (C == 128 && Cb == 64));
   // P3HIP_FLAG_INT8_FUSED: the btl trunks of the fused block kernel's C = 256 width; P3HIP_FLAG_INT8_C128: those of its
   // C = 128 width; each alone among the three INT8 flags
   const uint32_t i8_flags = flags & (P3HIP_FLAG_INT8 | P3HIP_FLAG_INT8_FUSED | P3HIP_FLAG_INT8_C128);
@@ -126,7 +159,7 @@ PlanChoice choose_plan(const WeightFile& wf, uint32_t given_flags, const Options
   // every other conv trunk of P3HIP_CONV_SET: layer-wise through conv_any.hip
   const bool any = !fused_shape && !lw_shape && conv_ok;
   // (P3HIP_FLAG_FP32 runs the fused shapes layer by layer too, and so does Int8Any: the nbt ones, and classic C = 128)
-  const bool layerwise = lw_shape || i8f_ok || any || (f32 && fused_shape) || (i8any && conv_ok);
+  const bool layerwise = lw_shape || i8f_ok || any || ((f32 || split) && fused_shape) || (i8any && conv_ok);
   const bool v_ok = wf.V == 32 || wf.V == 48 || wf.V == 64 || wf.V == 80;
   // transformer trunk: the file's C is the model width d and Cb the head count (include/p3hip.h: d a multiple of 32,
   // 64 <= d <= 384, head width d / heads 32 or 64); the stream is padded to C = p3::tfm_stream_width(d), and V is what
@@ -172,6 +205,7 @@ PlanChoice choose_plan(const WeightFile& wf, uint32_t given_flags, const Options
   // layer-wise; k_blockw serves C = 256 / C_b = 128 btl trunks, whose inner count bottleneck_ok has checked.)
   if (tfm) c.path = f32 ? Path::TfmF32 : Path::Tfm;
   else if (f32) c.path = Path::F32Conv;
+  else if (split) c.path = Path::Split;
   else if (i8any) c.path = Path::Int8Any;
   else if (i8f) c.path = i8c ? Path::Int8Fused128 : Path::Int8Fused256;
   else if (int8) c.path = Path::Int8;
@@ -450,7 +484,16 @@ void pack_broadcast_block(Builder& b, int i) {
   }
   const int CPb = (CB == 128) ? 128 : 64;
   std::vector<_Float16> s0, s1, s2;
-  for (int cp = 0; cp < C / CPb; ++cp)
+  const bool split = b.plan.choice.path == Path::Split;   // the two 1x1 convs as k_sconv images, no streams of them
+  if (split) {
+    std::vector<_Float16> ws;
+    p3::pack_sconv(ws, conv_w(wf, i, 0, 1, C, C), 1, C, C, C, C);
+    bp.ws_first = ar.add(ws.data(), ws.size() * 2);
+    ws.clear();
+    p3::pack_sconv(ws, conv_w(wf, i, 1, 1, C, C), 1, C, C, C, C);
+    bp.ws_last = ar.add(ws.data(), ws.size() * 2);
+  }
+  for (int cp = 0; cp < (split ? 0 : C / CPb); ++cp)
     for (int ip = 0; ip < C / CB; ++ip) {
       pack_segment(s0, conv_w(wf, i, 0, 1, C, C), 1, 1, C, C, ip * CB, CB, cp * CPb, CPb);
       pack_segment(s2, conv_w(wf, i, 1, 1, C, C), 1, 1, C, C, ip * CB, CB, cp * CPb, CPb);
@@ -492,9 +535,9 @@ void pack_broadcast_block(Builder& b, int i) {
     b.cur.head = f2;
     b.cur.head_of = i;   // last_fused is set when the run is laid out
   }
-  bp.stream_off = add_stream(ar, s0, bp.nms, CPb);
+  if (!split) bp.stream_off = add_stream(ar, s0, bp.nms, CPb);
   bp.stream2_off = add_stream(ar, s1, bp.nms2, 128);
-  bp.stream3_off = add_stream(ar, s2, bp.nms3, CPb);
+  if (!split) bp.stream3_off = add_stream(ar, s2, bp.nms3, CPb);
   bp.dense_bias_off = ar.add(wf.get(p + ".dense.b", (size_t)kNLoc).data, kNLoc * 4);
   b.plan.blocks.push_back(bp);
 }
@@ -529,6 +572,10 @@ void pack_layerwise_block(Builder& b, int i) {
       std::vector<float> w32;
       p3::pack_conv_f32(w32, conv_w(wf, i, j, kw, cin, cout), kw * kw, cin, cout, cin, cout);
       lp.w32_off = ar.add(w32.data(), w32.size() * 4);
+    } else if (path == Path::Split) {
+      std::vector<_Float16> s;
+      p3::pack_sconv(s, conv_w(wf, i, j, kw, cin, cout), kw * kw, cin, cout, cin, cout);
+      lp.ws_off = ar.add(s.data(), s.size() * 2);
     } else {
       std::vector<_Float16> s;
       for (int cp = 0; cp < cout / 64; ++cp)

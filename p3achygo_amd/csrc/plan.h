@@ -32,6 +32,11 @@ struct Options {
   bool blockw_diag = false;   // P3HIP_BLOCKW_DIAG: the _diag twin, which writes the engine's d_bw_stamps
   bool conv_any = false;   // P3HIP_CONV_ANY=1: the templated layer-wise shapes through conv_any.hip too (and, with
                            // P3HIP_FLAG_INT8_ANY, through k_lconv_i8_any)
+  // P3HIP_SPLIT="S,T" (P3HIP_FLAG_LOW_LATENCY engines; tests, A/B runs): every k_sconv launch splits a position into S row
+  // strips and T-channel output tiles.  0, 0: the launch chooses (conv_split.h sconv_split).  split_bad: the variable is
+  // set to something else than a pair of the kernel's sets, which fails the creation of such an engine
+  int split_s = 0, split_t = 0;
+  bool split_bad = false;
   static Options from_env();
 };
 
@@ -49,6 +54,8 @@ enum class Path {
   Int8Any,        // P3HIP_FLAG_INT8_ANY on every trunk the three above do not serve: k_lconv_i8_any, widths as launch
                   // arguments; stem, broadcast blocks and heads as ConvAny's
   F32Conv,        // P3HIP_FLAG_FP32: every conv trunk layer by layer through conv_f32.hip
+  Split,          // P3HIP_FLAG_LOW_LATENCY: every conv trunk layer by layer through k_sconv (conv_split.hip), a position
+                  // split across workgroups; stem, broadcast dense and heads as ConvAny's
   Tfm,            // transformer trunk, fp16
   TfmF32,         // P3HIP_FLAG_FP32_TFM: transformer trunk through transformer_f32.hip
 };
@@ -58,9 +65,12 @@ inline bool is_int8_fused(Path p) { return p == Path::Int8Fused256 || p == Path:
 // (an INT8 engine calibrates through the fp16 layer-wise plan: `calibrating` is a run-time state of the engine)
 inline bool is_int8(Path p) { return p == Path::Int8 || p == Path::Int8Any || is_int8_fused(p); }
 // the stem, the broadcast blocks, the head convs and the fp16 layer convs (calibration) through conv_any.hip
-inline bool runs_conv_any(Path p) { return p == Path::ConvAny || p == Path::Int8Any; }
+// (Split: all of these but the layer convs and the broadcast blocks' two 1x1 convs, which run through k_sconv)
+inline bool runs_conv_any(Path p) { return p == Path::ConvAny || p == Path::Int8Any || p == Path::Split; }
 // conv blocks planned conv by conv (BlockPlan kind 4)
-inline bool is_layerwise(Path p) { return p == Path::Layerwise || p == Path::ConvAny || is_int8(p) || p == Path::F32Conv; }
+inline bool is_layerwise(Path p) {
+  return p == Path::Layerwise || p == Path::ConvAny || is_int8(p) || p == Path::F32Conv || p == Path::Split;
+}
 inline size_t act_bytes(Path p) { return is_f32(p) ? 4 : 2; }   // bytes per activation element of d_x, d_t, d_u, d_qkv
 
 struct PlanChoice {
@@ -106,6 +116,7 @@ struct LayerPlan {
   size_t q_off = 0, qs_off = 0;
   int qidx = -1;
   size_t w32_off = 0;   // F32Conv: the fp32 weight image (conv_f32.h pack_conv_f32)
+  size_t ws_off = 0;    // Split: k_sconv's fragment image (conv_split.h pack_sconv)
 };
 
 // One transformer block (kind 5): arena offsets of its tensors, the GEMM weights as MFMA A fragments (transformer.h)
@@ -124,6 +135,7 @@ struct BlockPlan {
   int nms2 = 0, nms3 = 0;
   size_t dense_bias_off = 0;
   size_t w32_first = 0, w32_dense = 0, w32_last = 0;   // F32Conv: conv_first, the dense, conv_last in fp32
+  size_t ws_first = 0, ws_last = 0;                    // Split: conv_first and conv_last as k_sconv images
   // Broadcast 1x1 convs taken into the neighbouring block launches (k_block's BC form).
   //   on a broadcast block: its conv_first runs at the tail of the launch before it / its conv_last
   //   at the head of the launch after it;

@@ -36,6 +36,7 @@ EXPORTS = [
     "p3hip_get_aux",
     "p3hip_load_targets", "p3hip_loss", "p3hip_get_loss", "p3hip_debug_loss_rows",
     "p3hip_debug_plan", "p3hip_debug_act_i8",
+    "p3hip_debug_split", "p3hip_debug_pack_sconv",
 ]
 
 FLAG_RUN_ALL_SLOTS = 2
@@ -70,6 +71,9 @@ RAW_SEGMENTS = {
 }
 RESULT_FIELDS = {"01:pi": "move_probs", "03:outcome": "value_probs", "06:score_probs": "score_probs"}
 OUTPUT_NAMES = tuple(sorted(list(AUX_SEGMENTS) + list(RAW_SEGMENTS) + list(RESULT_FIELDS)))
+# runs of 1 to about 64 positions: every conv trunk layer by layer through k_sconv, a position split across workgroups
+# (include/p3hip.h)
+FLAG_LOW_LATENCY = 4096
 FLAG_SYMMETRY_AVG = 32  # every slot averaged over a set of the eight symmetries on the device
 
 
@@ -502,6 +506,32 @@ def debug_plan(path: str, flags: int = 0):
     if name is None:
         raise EngineError("p3hip_create: " + L.p3hip_create_error().decode())
     return name.decode(), n_q.value, dig.value
+
+
+def debug_split(npos: int, kw: int, cout: int, n_cu: int = 256):
+    """(row strips, output-channel tile) of a k_sconv launch of a FLAG_LOW_LATENCY engine, P3HIP_SPLIT included:
+    p3hip_debug_split, no device needed.  ValueError for a bad argument or a bad P3HIP_SPLIT."""
+    L = lib()
+    L.p3hip_debug_split.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    s, t = C.c_int(0), C.c_int(0)
+    if L.p3hip_debug_split(npos, kw, cout, n_cu, C.byref(s), C.byref(t)) != 0:
+        raise ValueError("p3hip_debug_split: bad argument or bad P3HIP_SPLIT")
+    return s.value, t.value
+
+
+def pack_sconv(w: np.ndarray, cin_pad: int, cout_pad: int) -> np.ndarray:
+    """k_sconv's weight image of w [taps][cin][cout] (csrc/conv_split.h pack_sconv) as float16
+    [cout_pad / 16][cin_pad / 32][taps][64][8]; no device needed."""
+    w = np.ascontiguousarray(w, np.float32)
+    taps, cin, cout = w.shape
+    L = lib()
+    L.p3hip_debug_pack_sconv.restype = C.c_long
+    L.p3hip_debug_pack_sconv.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_long]
+    out = np.zeros(taps * cin_pad * cout_pad, np.float16)
+    n = L.p3hip_debug_pack_sconv(w.ctypes.data, taps, cin, cout, cin_pad, cout_pad, out.ctypes.data, out.size)
+    if n != out.size:
+        raise ValueError(f"pack_sconv: the image has {n} elements, expected {out.size}")
+    return out.reshape(cout_pad // 16, cin_pad // 32, taps, 64, 8)
 
 
 def rope_table():

@@ -97,6 +97,10 @@ struct EvalPlayerConfig {   // PlayerSearchConfig (player_config.h:20-108), same
   // extension: the player's engine runs its trunk's fp32 plan (P3HIP_FLAG_FP32_ANY: conv and transformer trunks).  0 = the fp16 plan.  A net
   // against itself with one player in fp32 measures what fp16 costs in play.
   int nn_fp32 = 0;
+  // extension: the player's engine runs the low-latency plan (P3HIP_FLAG_LOW_LATENCY: conv trunks, a position split across
+  // workgroups).  For players whose engines see few positions at a time: a timed search turns the forward pass's latency
+  // into visits per move.
+  int nn_low_latency = 0;
 };
 
 // nn_symmetry_mask: decimal or 0x hex, 0 .. 255
@@ -232,6 +236,13 @@ inline bool ParsePlayerConfigStream(std::istream& in, EvalPlayerConfig* cfg, std
           return false;
         }
         cfg->nn_fp32 = val == "1";
+      }
+      else if (key == "nn_low_latency") {
+        if (val != "0" && val != "1") {
+          if (err) *err = "nn_low_latency must be 0 or 1: " + line;
+          return false;
+        }
+        cfg->nn_low_latency = val == "1";
       }
       // unknown keys are ignored (player_config.h:243)
     }
