@@ -682,7 +682,7 @@ double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
   }
   double flops = 0.0;
   const char* name = nullptr;
-  // a 3x3 layer conv (conv_any, fp32: the file's own width, not the padded one the kernel runs)
+  // a 3x3 layer conv
   const double own3 = wf.btype == 2 ? wf.model_C : wf.model_Cb;
   const double conv3 = 2.0 * n_positions * kNLoc * 9.0;
   // every conv of one btl / nbt block: the inner 3x3s plus the 1x1 reduce and expand
@@ -701,29 +701,18 @@ double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
       name = path == Path::Int8Fused128 ? p3::block_i8_c128_kernel_name() : p3::block_i8_kernel_name();
       break;
     case Path::F32Conv:
-      flops = conv3 * own3 * own3;
-      name = p3::lconv_f32_kernel_name(3);
-      break;
     case Path::ConvAny:
-      flops = conv3 * own3 * own3;
-      name = p3::lconv_any_kernel_name(3);
-      break;
     case Path::Split:
-      flops = conv3 * own3 * own3;
-      name = p3::sconv_kernel_name(3);
-      break;
     case Path::Int8Any:
-      flops = conv3 * own3 * own3;
-      name = p3::lconv_i8_any_kernel_name(3);
-      break;
     case Path::Int8:
-      flops = conv3 * c3 * c3;
-      name = p3::lconv_i8_kernel_name(3, c3, c3);
+    case Path::Layerwise: {
+      // the runtime-width kernels: the file's own width, not the padded one the kernel runs; the templated: the layer's
+      const LayerKernel lk = layer_kernel(e);
+      const double w3 = lk == LayerKernel::Lconv || lk == LayerKernel::LconvI8 ? c3 : own3;
+      flops = conv3 * w3 * w3;
+      name = layer_kernel_name(lk, 3, c3, c3);
       break;
-    case Path::Layerwise:
-      flops = conv3 * c3 * c3;
-      name = c3 == 192 ? "k_lconv<3,192,192>" : "k_lconv<3,64,64>";
-      break;
+    }
     case Path::Fused:
     case Path::Blockw: {
       // a launch covers `nfused / launches-per-forward` blocks on average

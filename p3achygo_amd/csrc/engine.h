@@ -187,6 +187,10 @@ struct p3hip_engine {
 namespace eng {
 
 // forward.cpp
+// The kernel that runs the convs of the layer-wise blocks in the engine's present state, and its name in a profile
+enum class LayerKernel { Lconv, LconvAny, LconvI8, LconvI8Any, LconvF32, Sconv };
+LayerKernel layer_kernel(const p3hip_engine* e);
+const char* layer_kernel_name(LayerKernel k, int kw, int cin, int cout);
 bool enqueue_forward(p3hip_engine* e, const Pass& p);
 bool expand_sym(p3hip_engine* e, const unsigned char* src, int n);
 bool run_pass(p3hip_engine* e, const Pass& p);

@@ -1,5 +1,5 @@
-// forward.cpp — the forward pass of an engine: the launch arguments of the block kernels, one enqueue function per
-// (block family, path), symmetry expand / reduce, and the captured graph.
+// forward.cpp — the forward pass of an engine: the launch arguments of the block kernels, the one launcher of a layer
+// conv, one enqueue function per block family, symmetry expand / reduce, and the captured graph.
 #include <cstdlib>
 
 #include "block_i8.h"
@@ -230,7 +230,7 @@ bool timed_launch(p3hip_engine* e, int* timed, Launch&& launch) {
   return true;
 }
 
-// ---- the enqueue functions: stem, one per (block family, path), heads -------------------------------
+// ---- the enqueue functions: stem, one per block family, heads ---------------------------------------
 
 // a 1x1 conv of the k_conv1x1 family: 0 conv_first, 1 conv_last of a broadcast block, 2 the head convs
 hipError_t launch_conv1x1(const p3hip_engine* e, int which, const p3::Conv1x1Args& a) {
@@ -242,13 +242,13 @@ bool enqueue_stem(p3hip_engine* e, const Pass& p) {
   const Plan& pl = e->plan;
   const int C = e->wf.C;
   if (is_f32(e->trunk_path())) {
-    const p3::InitF32Args a{p.feats, (float*)e->d_x, p.npos, C, e->dev<float>(pl.init_w32_off), e->dev<float>(pl.game_w_off),
+    const p3::InitF32Args a{p.feats, (float*)e->d_x, p.npos, C, e->dev<float>(pl.init_w_off), e->dev<float>(pl.game_w_off),
                             e->dev<float>(pl.game_b_off)};
     return e->check(p3::launch_init_f32(a, e->n_cu, e->stream), "launch k_init_f32");
   }
   p3::InitArgs a{};
   a.feats = p.feats; a.x = e->d_x; a.npos = p.npos;
-  a.wstream = e->d_arena + pl.init_stream_off; a.nms_total = pl.init_nms;
+  a.wstream = e->d_arena + pl.init_w_off; a.nms_total = pl.init_nms;
   a.game_w = e->dev<float>(pl.game_w_off); a.game_b = e->dev<float>(pl.game_b_off);
   return e->check(runs_conv_any(e->trunk_path()) ? p3::launch_init_any(C, a, grid_for(e, p.npos, 1), e->stream)
                                              : p3::launch_init(C, a, grid_for(e, p.npos, 1), e->stream), "launch k_init");
@@ -285,73 +285,6 @@ bool enqueue_tfm_block_f32(p3hip_engine* e, const Pass& p, const BlockPlan& bp) 
   return e->check(p3::launch_tfm_ffn_f32(f, s), "launch k_tfm_ffn_f32");
 }
 
-// The split of a k_sconv launch: P3HIP_SPLIT's, or the launch's own choice
-void set_split(const p3hip_engine* e, int kw, p3::SConvArgs& a) {
-  if (e->opt.split_s) { a.strips = e->opt.split_s; a.tile = e->opt.split_t; }
-  else p3::sconv_split(a.npos, kw, a.cout, e->n_cu, &a.strips, &a.tile);
-}
-
-// Split: conv_first and conv_last through k_sconv, the dense as ConvAny's
-bool enqueue_broadcast_block_split(p3hip_engine* e, const Pass& p, const BlockPlan& bp) {
-  const int C = e->wf.C, npos = p.npos;
-  p3::SConvArgs c0{};   // t = mish(conv_first(mish(bn0(x))))
-  c0.in = e->d_x; c0.out = e->d_t; c0.npos = npos; c0.cin = c0.cout = C; c0.w = e->d_arena + bp.ws_first;
-  c0.pre = 1; c0.act = 2;
-  c0.scale_in = e->dev<float>(bp.bn[0].scale_off); c0.shift_in = e->dev<float>(bp.bn[0].shift_off);
-  set_split(e, 1, c0);
-  if (!e->check(p3::launch_sconv(1, c0, e->n_cu, e->stream), "launch conv_first (k_sconv)")) return false;
-  p3::BDenseArgs d{};
-  d.t = e->d_t; d.u = e->d_u; d.npos = npos;
-  d.wstream = e->d_arena + bp.stream2_off; d.nms_total = bp.nms2;
-  d.bias = e->dev<float>(bp.dense_bias_off);
-  d.scale = e->dev<float>(bp.bn[1].scale_off); d.shift = e->dev<float>(bp.bn[1].shift_off);
-  if (!e->check(p3::launch_bdense_any(C, d, grid_for(e, npos, 1), e->stream), "launch bdense")) return false;
-  p3::SConvArgs c1{};   // x += conv_last(u)
-  c1.in = e->d_u; c1.out = e->d_x; c1.npos = npos; c1.cin = c1.cout = C; c1.w = e->d_arena + bp.ws_last;
-  c1.res = 1;
-  set_split(e, 1, c1);
-  return e->check(p3::launch_sconv(1, c1, e->n_cu, e->stream), "launch conv_last (k_sconv)");
-}
-
-// A broadcast block in fp16: whatever of conv_first, dense and conv_last the neighbouring block launches did not take
-bool enqueue_broadcast_block(p3hip_engine* e, const Pass& p, const BlockPlan& bp) {
-  const int C = e->wf.C, npos = p.npos;
-  p3::Conv1x1Args c0{};
-  c0.in = e->d_x; c0.out16 = e->d_t; c0.npos = npos;
-  c0.wstream = e->d_arena + bp.stream_off; c0.nms_total = bp.nms;
-  c0.scale = e->dev<float>(bp.bn[0].scale_off); c0.shift = e->dev<float>(bp.bn[0].shift_off);
-  if (!bp.first_fused && !e->check(launch_conv1x1(e, 0, c0), "launch conv_first")) return false;
-  p3::BDenseArgs d{};
-  d.t = e->d_t; d.u = e->d_u; d.npos = npos;
-  d.wstream = e->d_arena + bp.stream2_off; d.nms_total = bp.nms2;
-  d.bias = e->dev<float>(bp.dense_bias_off);
-  d.scale = e->dev<float>(bp.bn[1].scale_off); d.shift = e->dev<float>(bp.bn[1].shift_off);
-  if (!(bp.first_fused && bp.dense_fused) &&
-      !e->check(runs_conv_any(e->trunk_path()) ? p3::launch_bdense_any(C, d, grid_for(e, npos, 1), e->stream)
-                                           : p3::launch_bdense(C, d, grid_for(e, npos, 1), e->stream), "launch bdense")) return false;
-  p3::Conv1x1Args c1{};
-  c1.in = e->d_u; c1.out16 = e->d_x; c1.npos = npos;
-  c1.wstream = e->d_arena + bp.stream3_off; c1.nms_total = bp.nms3;
-  return bp.last_fused || e->check(launch_conv1x1(e, 1, c1), "launch conv_last");
-}
-
-bool enqueue_broadcast_block_f32(p3hip_engine* e, const Pass& p, const BlockPlan& bp) {
-  const int C = e->wf.C, npos = p.npos;
-  float *x = (float*)e->d_x, *t = (float*)e->d_t, *u = (float*)e->d_u;
-  p3::LConvF32Args c0{};   // t = mish(conv_first(mish(bn0(x))))
-  c0.in = x; c0.out = t; c0.npos = npos; c0.cin = c0.cout = C; c0.w = e->dev<float>(bp.w32_first);
-  c0.pre = 1; c0.act = 2;
-  c0.scale_in = e->dev<float>(bp.bn[0].scale_off); c0.shift_in = e->dev<float>(bp.bn[0].shift_off);
-  if (!e->check(p3::launch_lconv_f32(1, c0, e->n_cu, e->stream), "launch conv_first (fp32)")) return false;
-  const p3::BDenseF32Args d{t, u, npos, C, e->dev<float>(bp.w32_dense), e->dev<float>(bp.dense_bias_off),
-                            e->dev<float>(bp.bn[1].scale_off), e->dev<float>(bp.bn[1].shift_off)};
-  if (!e->check(p3::launch_bdense_f32(d, e->n_cu, e->stream), "launch k_bdense_f32")) return false;
-  p3::LConvF32Args c1{};   // x += conv_last(u)
-  c1.in = u; c1.out = x; c1.npos = npos; c1.cin = c1.cout = C; c1.w = e->dev<float>(bp.w32_last);
-  c1.res = 1;
-  return e->check(p3::launch_lconv_f32(1, c1, e->n_cu, e->stream), "launch conv_last (fp32)");
-}
-
 // The regions of a layer-wise block (LayerPlan) in buffers of element type T
 template <class T>
 struct Regions {
@@ -370,32 +303,112 @@ void fill_layer(const p3hip_engine* e, Args& a, const LayerPlan& lp, const Regio
   a.out2 = lp.out2_buf >= 0 ? reinterpret_cast<decltype(a.out2)>(r.buf[lp.out2_buf]) : nullptr;
   a.pre = lp.pre; a.act = lp.act; a.res = lp.res; a.dual = lp.dual;
   if (a.pre) { a.scale_in = e->dev<float>(lp.pre_bn.scale_off); a.shift_in = e->dev<float>(lp.pre_bn.shift_off); }
-  if (a.act || a.dual) { a.scale_out = e->dev<float>(lp.out_bn.scale_off); a.shift_out = e->dev<float>(lp.out_bn.shift_off); }
+  if (a.act == 1 || a.dual) { a.scale_out = e->dev<float>(lp.out_bn.scale_off); a.shift_out = e->dev<float>(lp.out_bn.shift_off); }
 }
 
-bool enqueue_layerwise_block_f32(p3hip_engine* e, const Pass& p, const BlockPlan& bp) {
-  const Regions<float> r(e);
+// The conv of one LayerPlan through the kernel the engine's state selects (layer_kernel).  `what`: the name e->check
+// reports a failed launch under, the kernel's own by default
+bool launch_layer(p3hip_engine* e, const Pass& p, const LayerPlan& lp, const char* what = nullptr) {
+  const LayerKernel k = layer_kernel(e);
+  switch (k) {
+    case LayerKernel::LconvF32: {
+      p3::LConvF32Args a{};
+      fill_layer(e, a, lp, Regions<float>(e), p.npos);
+      a.cin = lp.cin; a.cout = lp.cout; a.w = e->dev<float>(lp.w_off);
+      return e->check(p3::launch_lconv_f32(lp.kw, a, e->n_cu, e->stream), what ? what : "launch k_lconv_f32");
+    }
+    case LayerKernel::Sconv: {
+      p3::SConvArgs a{};
+      fill_layer(e, a, lp, Regions<_Float16>(e), p.npos);
+      a.cin = lp.cin; a.cout = lp.cout; a.w = e->d_arena + lp.w_off;
+      // the split: P3HIP_SPLIT's, or the launch's own choice
+      if (e->opt.split_s) { a.strips = e->opt.split_s; a.tile = e->opt.split_t; }
+      else p3::sconv_split(a.npos, lp.kw, a.cout, e->n_cu, &a.strips, &a.tile);
+      return e->check(p3::launch_sconv(lp.kw, a, e->n_cu, e->stream), what ? what : "launch k_sconv");
+    }
+    case LayerKernel::LconvI8:
+    case LayerKernel::LconvI8Any: {
+      // (the callers check int8_ready) the fp16 plan's regions, an int8 tensor where that stores an activated one
+      p3::LConvI8Args a{};
+      fill_layer(e, a, lp, Regions<_Float16>(e), p.npos);
+      a.w = e->dev<int8_t>(lp.q_off); a.w_scale = e->dev<float>(lp.qs_off);
+      a.act_scale = e->d_ascale; a.in_scale = lp.qidx; a.out_scale = lp.qidx + 1;
+      return k == LayerKernel::LconvI8Any
+                 ? e->check(p3::launch_lconv_i8_any(lp.kw, lp.cin, lp.cout, a, e->stream), what ? what : "launch k_lconv_i8_any")
+                 : e->check(p3::launch_lconv_i8(lp.kw, lp.cin, lp.cout, a, e->stream), what ? what : "launch k_lconv_i8");
+    }
+    case LayerKernel::Lconv:
+    case LayerKernel::LconvAny: {
+      p3::LConvArgs a{};
+      fill_layer(e, a, lp, Regions<_Float16>(e), p.npos);
+      a.wstream = e->d_arena + lp.w_off; a.nms_total = lp.nms;
+      return k == LayerKernel::LconvAny
+                 ? e->check(p3::launch_lconv_any(lp.kw, lp.cin, lp.cout, a, e->n_cu, e->stream), what ? what : "launch k_lconv_any")
+                 : e->check(p3::launch_lconv(lp.kw, lp.cin, lp.cout, a, e->n_cu, e->stream), what ? what : "launch k_lconv");
+    }
+  }
+  return false;
+}
+
+// A layer-wise block on every path but the fused INT8 ones' runs (enqueue_block_i8); the calibration runs of the INT8
+// paths are the fp16 plan + absmax
+bool enqueue_layerwise_block(p3hip_engine* e, const Pass& p, const BlockPlan& bp) {
   for (const LayerPlan& lp : bp.layers) {
-    p3::LConvF32Args a{};
-    fill_layer(e, a, lp, r, p.npos);
-    a.cin = lp.cin; a.cout = lp.cout; a.w = e->dev<float>(lp.w32_off);
-    auto launch = [&] { return e->check(p3::launch_lconv_f32(lp.kw, a, e->n_cu, e->stream), "launch k_lconv_f32"); };
-    if (!timed_launch(e, lp.kw == 3 ? p.timed : nullptr, launch)) return false;
+    if (e->calibrating) {
+      // MinMax calibration: the absmax of this conv's quantized input, the activated tensor (pre: mish(bn0(x)),
+      // which the fp16 plan never stores) folded into the running maximum
+      p3::AbsmaxArgs m{};
+      m.in = Regions<_Float16>(e).buf[lp.in_buf]; m.npos = p.npos; m.C = lp.cin; m.amax = e->d_amax + lp.qidx;
+      if (lp.pre) { m.scale = e->dev<float>(lp.pre_bn.scale_off); m.shift = e->dev<float>(lp.pre_bn.shift_off); }
+      if (!e->check(p3::launch_absmax(m, e->n_cu, e->stream), "launch k_absmax")) return false;
+    }
+    if (!timed_launch(e, lp.kw == 3 ? p.timed : nullptr, [&] { return launch_layer(e, p, lp); })) return false;
   }
   return true;
 }
 
-bool enqueue_layerwise_block_split(p3hip_engine* e, const Pass& p, const BlockPlan& bp) {
-  const Regions<_Float16> r(e);
-  for (const LayerPlan& lp : bp.layers) {
-    p3::SConvArgs a{};
-    fill_layer(e, a, lp, r, p.npos);
-    a.cin = lp.cin; a.cout = lp.cout; a.w = e->d_arena + lp.ws_off;
-    set_split(e, lp.kw, a);
-    auto launch = [&] { return e->check(p3::launch_sconv(lp.kw, a, e->n_cu, e->stream), "launch k_sconv"); };
-    if (!timed_launch(e, lp.kw == 3 ? p.timed : nullptr, launch)) return false;
+p3::BDenseArgs bdense_args(const p3hip_engine* e, const BlockPlan& bp, int npos) {
+  p3::BDenseArgs d{};
+  d.t = e->d_t; d.u = e->d_u; d.npos = npos;
+  d.wstream = e->d_arena + bp.dense_off; d.nms_total = bp.dense_nms;
+  d.bias = e->dev<float>(bp.dense_bias_off);
+  d.scale = e->dev<float>(bp.bn[1].scale_off); d.shift = e->dev<float>(bp.bn[1].shift_off);
+  return d;
+}
+
+// A broadcast block of F32Conv and Split: conv_first and conv_last, the block's two layers, through the path's layer
+// kernel; between them the dense in fp32, or (Split) as ConvAny's
+bool enqueue_broadcast_block_layers(p3hip_engine* e, const Pass& p, const BlockPlan& bp) {
+  const int C = e->wf.C, npos = p.npos;
+  const bool f32 = e->trunk_path() == Path::F32Conv;
+  if (!launch_layer(e, p, bp.layers[0], f32 ? "launch conv_first (fp32)" : "launch conv_first (k_sconv)")) return false;
+  if (f32) {
+    const p3::BDenseF32Args d{(float*)e->d_t, (float*)e->d_u, npos, C, e->dev<float>(bp.dense_off), e->dev<float>(bp.dense_bias_off),
+                              e->dev<float>(bp.bn[1].scale_off), e->dev<float>(bp.bn[1].shift_off)};
+    if (!e->check(p3::launch_bdense_f32(d, e->n_cu, e->stream), "launch k_bdense_f32")) return false;
+  } else if (!e->check(p3::launch_bdense_any(C, bdense_args(e, bp, npos), grid_for(e, npos, 1), e->stream), "launch bdense")) {
+    return false;
   }
-  return true;
+  return launch_layer(e, p, bp.layers[1], f32 ? "launch conv_last (fp32)" : "launch conv_last (k_sconv)");
+}
+
+// A broadcast block in fp16: whatever of conv_first, dense and conv_last the neighbouring block launches did not take
+bool enqueue_broadcast_block(p3hip_engine* e, const Pass& p, const BlockPlan& bp) {
+  const int C = e->wf.C, npos = p.npos;
+  const LayerPlan &first = bp.layers[0], &last = bp.layers[1];
+  p3::Conv1x1Args c0{};
+  c0.in = e->d_x; c0.out16 = e->d_t; c0.npos = npos;
+  c0.wstream = e->d_arena + first.w_off; c0.nms_total = first.nms;
+  c0.scale = e->dev<float>(bp.bn[0].scale_off); c0.shift = e->dev<float>(bp.bn[0].shift_off);
+  if (!bp.first_fused && !e->check(launch_conv1x1(e, 0, c0), "launch conv_first")) return false;
+  const p3::BDenseArgs d = bdense_args(e, bp, npos);
+  if (!(bp.first_fused && bp.dense_fused) &&
+      !e->check(runs_conv_any(e->trunk_path()) ? p3::launch_bdense_any(C, d, grid_for(e, npos, 1), e->stream)
+                                           : p3::launch_bdense(C, d, grid_for(e, npos, 1), e->stream), "launch bdense")) return false;
+  p3::Conv1x1Args c1{};
+  c1.in = e->d_u; c1.out16 = e->d_x; c1.npos = npos;
+  c1.wstream = e->d_arena + last.w_off; c1.nms_total = last.nms;
+  return bp.last_fused || e->check(launch_conv1x1(e, 1, c1), "launch conv_last");
 }
 
 // Int8Fused256 / Int8Fused128: one launch runs the block's convs with the activations in LDS; the layers carry its tensors
@@ -415,51 +428,6 @@ bool enqueue_block_i8(p3hip_engine* e, const Pass& p, const BlockPlan& bp) {
                                                     : p3::launch_block_i8(a, e->n_cu, e->stream), "launch k_block_i8");
   };
   return timed_launch(e, p.timed, launch);
-}
-
-// Int8, Int8Any (their callers check int8_ready): the fp16 plan's regions, an int8 tensor where that stores an activated
-// one.  Int8Any: the same layers through k_lconv_i8_any, the (padded) widths with the launch
-bool enqueue_layerwise_block_i8(p3hip_engine* e, const Pass& p, const BlockPlan& bp) {
-  const Regions<_Float16> r(e);
-  const bool any = e->trunk_path() == Path::Int8Any;
-  for (const LayerPlan& lp : bp.layers) {
-    p3::LConvI8Args a{};
-    fill_layer(e, a, lp, r, p.npos);
-    a.w = e->dev<int8_t>(lp.q_off); a.w_scale = e->dev<float>(lp.qs_off);
-    a.act_scale = e->d_ascale; a.in_scale = lp.qidx; a.out_scale = lp.qidx + 1;
-    auto launch = [&] {
-      return e->check(any ? p3::launch_lconv_i8_any(lp.kw, lp.cin, lp.cout, a, e->stream)
-                          : p3::launch_lconv_i8(lp.kw, lp.cin, lp.cout, a, e->stream), any ? "launch k_lconv_i8_any" : "launch k_lconv_i8");
-    };
-    if (!timed_launch(e, lp.kw == 3 ? p.timed : nullptr, launch)) return false;
-  }
-  return true;
-}
-
-// Layerwise, ConvAny, and the calibration runs of the INT8 paths (the fp16 plan + absmax)
-bool enqueue_layerwise_block(p3hip_engine* e, const Pass& p, const BlockPlan& bp) {
-  const Regions<_Float16> r(e);
-  // (Int8Fused128 calibrates through the runtime-width kernel: k_lconv has no C = 128 / C_b = 64 instantiations)
-  const bool any = runs_conv_any(e->trunk_path()) || e->trunk_path() == Path::Int8Fused128;
-  for (const LayerPlan& lp : bp.layers) {
-    if (e->calibrating) {
-      // MinMax calibration: the absmax of this conv's quantized input, the activated tensor (pre: mish(bn0(x)),
-      // which the fp16 plan never stores) folded into the running maximum
-      p3::AbsmaxArgs m{};
-      m.in = r.buf[lp.in_buf]; m.npos = p.npos; m.C = lp.cin; m.amax = e->d_amax + lp.qidx;
-      if (lp.pre) { m.scale = e->dev<float>(lp.pre_bn.scale_off); m.shift = e->dev<float>(lp.pre_bn.shift_off); }
-      if (!e->check(p3::launch_absmax(m, e->n_cu, e->stream), "launch k_absmax")) return false;
-    }
-    p3::LConvArgs a{};
-    fill_layer(e, a, lp, r, p.npos);
-    a.wstream = e->d_arena + lp.stream_off; a.nms_total = lp.nms;
-    auto launch = [&] {
-      return e->check(any ? p3::launch_lconv_any(lp.kw, lp.cin, lp.cout, a, e->n_cu, e->stream)
-                          : p3::launch_lconv(lp.kw, lp.cin, lp.cout, a, e->n_cu, e->stream), any ? "launch k_lconv_any" : "launch k_lconv");
-    };
-    if (!timed_launch(e, lp.kw == 3 ? p.timed : nullptr, launch)) return false;
-  }
-  return true;
 }
 
 // Blockw: the k_blockw run that starts at block bi; *covered: its blocks
@@ -507,12 +475,12 @@ bool enqueue_heads(p3hip_engine* e, const Pass& p) {
   if (is_f32(e->trunk_path())) {
     p3::LConvF32Args hc{};   // the three head convs C -> 96 in fp32, hp in k_heads' layout
     hc.in = (const float*)e->d_x; hc.out = e->d_hp; hc.npos = p.npos; hc.cin = C; hc.cout = 128; hc.hp = 1;
-    hc.w = e->dev<float>(e->plan.heads_w32_off);
+    hc.w = e->dev<float>(e->plan.heads_w_off);
     if (!e->check(p3::launch_lconv_f32(1, hc, e->n_cu, e->stream), "launch head convs (fp32)")) return false;
   } else if (!e->plan.choice.heads_fused) {
     p3::Conv1x1Args c{};
     c.in = e->d_x; c.out32 = e->d_hp; c.npos = p.npos;
-    c.wstream = e->d_arena + e->plan.heads_stream_off; c.nms_total = e->plan.heads_nms;
+    c.wstream = e->d_arena + e->plan.heads_w_off; c.nms_total = e->plan.heads_nms;
     if (!e->check(launch_conv1x1(e, 2, c), "launch head convs")) return false;
   }
   const bool aux = (e->flags & P3HIP_FLAG_AUX) != 0;
@@ -520,7 +488,7 @@ bool enqueue_heads(p3hip_engine* e, const Pass& p) {
     // k_headsx keeps the head convs' output to itself: the launch the unfused path makes, for k_heads_aux alone
     p3::Conv1x1Args c{};
     c.in = e->d_x; c.out32 = e->d_hp; c.npos = p.npos;
-    c.wstream = e->d_arena + e->plan.heads_stream_off; c.nms_total = e->plan.heads_nms;
+    c.wstream = e->d_arena + e->plan.heads_w_off; c.nms_total = e->plan.heads_nms;
     if (!e->check(launch_conv1x1(e, 2, c), "launch head convs (aux)")) return false;
   }
   p3::HeadsArgs h = e->heads_args;   // the weight pointers never change after create
@@ -534,6 +502,29 @@ bool enqueue_heads(p3hip_engine* e, const Pass& p) {
 }
 
 }  // namespace
+
+// The kernel of the layer convs: the path's, and on the INT8 paths while they calibrate the fp16 plan's.  (The fused INT8
+// paths run whole blocks, enqueue_block_i8, once calibrated; Int8Fused128 calibrates through the runtime-width kernel:
+// k_lconv has no C = 128 / C_b = 64 instantiations)
+LayerKernel layer_kernel(const p3hip_engine* e) {
+  const Path path = e->trunk_path();
+  if (path == Path::F32Conv) return LayerKernel::LconvF32;
+  if (path == Path::Split) return LayerKernel::Sconv;
+  if (is_int8(path) && !e->calibrating) return path == Path::Int8Any ? LayerKernel::LconvI8Any : LayerKernel::LconvI8;
+  return runs_conv_any(path) || path == Path::Int8Fused128 ? LayerKernel::LconvAny : LayerKernel::Lconv;
+}
+
+const char* layer_kernel_name(LayerKernel k, int kw, int cin, int cout) {
+  switch (k) {
+    case LayerKernel::Lconv: return cin == 192 ? "k_lconv<3,192,192>" : "k_lconv<3,64,64>";   // (the 3x3 convs: the timed ones)
+    case LayerKernel::LconvAny: return p3::lconv_any_kernel_name(kw);
+    case LayerKernel::LconvI8: return p3::lconv_i8_kernel_name(kw, cin, cout);
+    case LayerKernel::LconvI8Any: return p3::lconv_i8_any_kernel_name(kw);
+    case LayerKernel::LconvF32: return p3::lconv_f32_kernel_name(kw);
+    case LayerKernel::Sconv: return p3::sconv_kernel_name(kw);
+  }
+  return nullptr;
+}
 
 // Enqueues the whole forward pass `p`: stem, blocks, heads.
 bool enqueue_forward(p3hip_engine* e, const Pass& p) {
@@ -558,15 +549,10 @@ bool enqueue_forward(p3hip_engine* e, const Pass& p) {
         ok = path == Path::TfmF32 ? enqueue_tfm_block_f32(e, p, bp) : enqueue_tfm_block(e, p, bp);
         break;
       case 3:
-        ok = path == Path::F32Conv ? enqueue_broadcast_block_f32(e, p, bp)
-             : path == Path::Split ? enqueue_broadcast_block_split(e, p, bp) : enqueue_broadcast_block(e, p, bp);
+        ok = path == Path::F32Conv || path == Path::Split ? enqueue_broadcast_block_layers(e, p, bp) : enqueue_broadcast_block(e, p, bp);
         break;
       case 4:
-        if (path == Path::F32Conv) ok = enqueue_layerwise_block_f32(e, p, bp);
-        else if (path == Path::Split) ok = enqueue_layerwise_block_split(e, p, bp);
-        else if (is_int8(path) && !e->calibrating)
-          ok = is_int8_fused(path) ? enqueue_block_i8(e, p, bp) : enqueue_layerwise_block_i8(e, p, bp);
-        else ok = enqueue_layerwise_block(e, p, bp);
+        ok = is_int8_fused(path) && !e->calibrating ? enqueue_block_i8(e, p, bp) : enqueue_layerwise_block(e, p, bp);
         break;
       default:   // 0 btl, 1 nbt
         ok = path == Path::Blockw ? enqueue_blockw_run(e, p, bi, &covered) : enqueue_fused_run(e, p, bi, &covered);

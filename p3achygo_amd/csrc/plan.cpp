@@ -64,161 +64,187 @@ const char* path_name(Path p) {
   return "?";
 }
 
-PlanChoice choose_plan(const WeightFile& wf, uint32_t given_flags, const Options& opt, std::string& err) {
+namespace {
+
+// What kind of trunk a file holds, as far as the plans tell trunks apart
+enum class Trunk {
+  None,          // nothing the engine serves
+  BlockShape,    // a k_block shape: btl or nbt at C = 256 / C_b = 128 or 128 / 64
+  LconvShape,    // a templated k_lconv shape: C = 384 / C_b = 192 btl or nbt, classic C = 192 (b15c192_classic)
+  OtherConv,     // every other conv trunk of P3HIP_CONV_SET, C and C_b padded to multiples of 64
+  Transformer,   // a transformer of P3HIP_TRANSFORMER_SET whose heads the engine has
+};
+
+// The classification of a file, computed once, and the few other facts the refusals ask about
+struct TrunkClass {
+  Trunk trunk = Trunk::None;
+  bool tfm_file = false;   // the header says transformer, served or not
+  bool btl123 = false;     // btl blocks with 1, 2 or 3 inner layers
+  bool in_set = false;     // a conv trunk of P3HIP_CONV_SET (a k_block or k_lconv shape with a broadcast block at every
+                           // position is none, and runs all the same)
+  bool hv_ok = false;      // H = 32 and V in {32, 48, 64, 80}
+};
+
+TrunkClass classify(const WeightFile& wf) {
+  const int C = wf.C, Cb = wf.Cb;
+  TrunkClass t;
+  t.tfm_file = wf.btype == 3;
+  t.btl123 = wf.btype == 0 && wf.inner >= 1 && wf.inner <= 3;
+  t.in_set = WeightFile::conv_set(wf.model_C, wf.model_Cb, wf.btype, wf.inner, wf.bint) && C % 64 == 0 &&
+             (wf.btype == 2 || Cb % 64 == 0);
+  t.hv_ok = wf.H == 32 && (wf.V == 32 || wf.V == 48 || wf.V == 64 || wf.V == 80);
+  // a conv file whose widths were padded (WeightFile::pad_conv) never takes the plan of the shape it was padded to
+  const bool exact = wf.model_C == C && wf.model_Cb == Cb;
+  const bool bottleneck = wf.btype == 1 || t.btl123;
+  if (exact && bottleneck && ((C == 256 && Cb == 128) || (C == 128 && Cb == 64))) t.trunk = Trunk::BlockShape;
+  else if (exact && ((bottleneck && C == 384 && Cb == 192) || (wf.btype == 2 && wf.inner == 2 && C == 192))) t.trunk = Trunk::LconvShape;
+  else if (t.in_set) t.trunk = Trunk::OtherConv;
+  // transformer: the file's C is the model width d and Cb the head count (include/p3hip.h: d a multiple of 32,
+  // 64 <= d <= 384, head width d / heads 32 or 64); the stream is padded to C = p3::tfm_stream_width(d), and V is what
+  // the heads of that width serve (the fused heads at C = 128 / 256: {32, 48, 64}; the C = 384 heads: hv_ok's)
+  else if (t.tfm_file && p3::tfm_supported(wf.model_C, Cb) && C == p3::tfm_stream_width(wf.model_C) &&
+           (C == 384 || p3::heads_fusable(C, wf.V))) t.trunk = Trunk::Transformer;
+  return t;
+}
+
+// What the precision flags ask for: one plan
+struct Request {
+  enum Kind { Fp16, Int8, Int8Fused, Int8C128, Int8Any, Fp32, LowLatency } kind = Fp16;
+  bool int8_any = false;   // P3HIP_FLAG_INT8_ANY was given (kind is the plan it chose)
+  bool alone = true;       // Int8Fused, Int8C128: no other of the three INT8 flags beside it
+  bool f32_conv = false, f32_tfm = false;   // Fp32: P3HIP_FLAG_FP32 serves the conv trunks, P3HIP_FLAG_FP32_TFM the
+                                            // transformers; both together: whatever the trunk
+  std::string clash;       // the flags cannot be combined: the refusal's text
+};
+
+// P3HIP_FLAG_INT8_ANY: a trunk one of the three other INT8 flags serves takes that flag's plan, bit-identical to the flag
+// alone, and every other conv trunk the path of its own.  P3HIP_CONV_ANY=1 sends the templated layer-wise shapes there too.
+Request::Kind int8_any_choice(const TrunkClass& t, int C, bool conv_any) {
+  if (t.trunk == Trunk::LconvShape && !conv_any) return Request::Int8;
+  if (t.trunk == Trunk::BlockShape && t.btl123) return C == 256 ? Request::Int8Fused : Request::Int8C128;
+  return Request::Int8Any;
+}
+
+// The flags read once.  P3HIP_FLAG_LOW_LATENCY, then P3HIP_FLAG_INT8_ANY, then the fp32 flags name the plan, and whatever
+// else stands beside them is a clash; of the three other INT8 flags together INT8_C128 speaks, then INT8_FUSED.
+Request read_request(uint32_t flags, const TrunkClass& t, int C, const Options& opt) {
+  const uint32_t i8_three = flags & (P3HIP_FLAG_INT8 | P3HIP_FLAG_INT8_FUSED | P3HIP_FLAG_INT8_C128);
+  const bool fp32_flag = (flags & (P3HIP_FLAG_FP32 | P3HIP_FLAG_FP32_TFM)) != 0;
+  Request r;
+  r.f32_conv = (flags & P3HIP_FLAG_FP32) != 0;
+  r.f32_tfm = (flags & P3HIP_FLAG_FP32_TFM) != 0;
+  if (flags & P3HIP_FLAG_LOW_LATENCY) {
+    r.kind = Request::LowLatency;
+    if (i8_three || (flags & P3HIP_FLAG_INT8_ANY))
+      r.clash = "P3HIP_FLAG_LOW_LATENCY cannot be combined with P3HIP_FLAG_INT8, P3HIP_FLAG_INT8_FUSED, P3HIP_FLAG_INT8_C128 or "
+                "P3HIP_FLAG_INT8_ANY: its kernel runs in fp16";
+    else if (fp32_flag)
+      r.clash = "P3HIP_FLAG_LOW_LATENCY cannot be combined with P3HIP_FLAG_FP32 or P3HIP_FLAG_FP32_TFM: its kernel runs in fp16";
+  } else if (flags & P3HIP_FLAG_INT8_ANY) {
+    r.kind = int8_any_choice(t, C, opt.conv_any);
+    r.int8_any = true;
+    if (i8_three)
+      r.clash = "P3HIP_FLAG_INT8_ANY cannot be combined with P3HIP_FLAG_INT8, P3HIP_FLAG_INT8_FUSED or P3HIP_FLAG_INT8_C128: it "
+                "chooses among their plans itself";
+    else if (fp32_flag)
+      r.clash = "P3HIP_FLAG_INT8_ANY cannot be combined with P3HIP_FLAG_FP32 or P3HIP_FLAG_FP32_TFM: an engine runs one "
+                "precision plan";
+  } else if (fp32_flag) {
+    r.kind = Request::Fp32;
+    if (i8_three)
+      r.clash = std::string(r.f32_conv ? (r.f32_tfm ? "P3HIP_FLAG_FP32 | P3HIP_FLAG_FP32_TFM" : "P3HIP_FLAG_FP32") : "P3HIP_FLAG_FP32_TFM") +
+                " cannot be combined with P3HIP_FLAG_INT8, P3HIP_FLAG_INT8_FUSED or P3HIP_FLAG_INT8_C128: an "
+                "engine runs one precision plan";
+  } else if (i8_three) {
+    r.kind = (i8_three & P3HIP_FLAG_INT8_C128) ? Request::Int8C128 : (i8_three & P3HIP_FLAG_INT8_FUSED) ? Request::Int8Fused : Request::Int8;
+    r.alone = (i8_three & (i8_three - 1)) == 0;
+  }
+  return r;
+}
+
+// The path of a request the refusals let through
+Path path_of(const Request& r, const TrunkClass& t, const WeightFile& wf, const Options& opt) {
+  if (t.trunk == Trunk::Transformer) return r.kind == Request::Fp32 ? Path::TfmF32 : Path::Tfm;
+  switch (r.kind) {
+    case Request::Fp32: return Path::F32Conv;
+    case Request::LowLatency: return Path::Split;
+    case Request::Int8Any: return Path::Int8Any;
+    case Request::Int8Fused: return Path::Int8Fused256;
+    case Request::Int8C128: return Path::Int8Fused128;
+    case Request::Int8: return Path::Int8;
+    case Request::Fp16: break;
+  }
+  if (t.trunk == Trunk::OtherConv || (t.trunk == Trunk::LconvShape && opt.conv_any)) return Path::ConvAny;
+  if (t.trunk == Trunk::LconvShape) return Path::Layerwise;
+  // k_blockw serves C = 256 / C_b = 128 btl trunks
+  return (opt.blockw && wf.C == 256 && wf.btype == 0) ? Path::Blockw : Path::Fused;
+}
+
+}  // namespace
+
+PlanChoice choose_plan(const WeightFile& wf, uint32_t flags, const Options& opt, std::string& err) {
   const int C = wf.C, Cb = wf.Cb;
   PlanChoice c;
-  // a conv file whose widths were padded (WeightFile::pad_conv) never takes the plan of the shape it was padded to
-  const bool exact = wf.btype == 3 || (wf.model_C == C && wf.model_Cb == Cb);
-  const bool classic = wf.btype == 2 && wf.inner == 2;                 // two 3x3 convs C -> C
-  const bool classic192 = classic && exact && C == 192;                // b15c192_classic
-  const bool bottleneck_ok = wf.btype == 1 || (wf.btype == 0 && wf.inner >= 1 && wf.inner <= 3);
-  const bool fused_shape = exact && ((C == 256 && Cb == 128) || (C == 128 && Cb == 64)) && bottleneck_ok;
-  const bool lw_shape = (exact && C == 384 && Cb == 192 && bottleneck_ok) || classic192;   // the templated k_lconv's shapes
-  // P3HIP_FLAG_INT8_ANY: INT8 whatever the conv trunk.  Its own refusals first; then a trunk one of the three other INT8
-  // flags serves takes that flag's plan (the rest of this function sees that flag, bit-identical to it alone), and every
-  // other conv trunk the path of its own, Int8Any.  P3HIP_CONV_ANY=1 sends the templated layer-wise shapes there too.
-  uint32_t flags = given_flags;
-  // P3HIP_FLAG_LOW_LATENCY: every conv trunk in fp16 through k_sconv, and nothing else
-  const bool split = (flags & P3HIP_FLAG_LOW_LATENCY) != 0;
-  if (split) {
-    if (wf.btype == 3) {
-      err = "P3HIP_FLAG_LOW_LATENCY serves the conv trunks (" P3HIP_CONV_SET "); the transformer trunks (" P3HIP_TRANSFORMER_SET
-            ") have no low-latency plan";
+  const TrunkClass t = classify(wf);
+  const Request r = read_request(flags, t, C, opt);
+  const Request::Kind k = r.kind;
+  const Trunk tr = t.trunk;
+  // Every refusal, in the order of precedence: the first that applies answers.  (A flag that names the plan first says
+  // which trunks it serves, then what cannot stand beside it; a request has one kind, so the first four never compete.)
+  const struct { bool applies; std::string text; } refusals[] = {
+      {k == Request::LowLatency && t.tfm_file,
+       "P3HIP_FLAG_LOW_LATENCY serves the conv trunks (" P3HIP_CONV_SET "); the transformer trunks (" P3HIP_TRANSFORMER_SET
+       ") have no low-latency plan"},
+      {r.int8_any && t.tfm_file,
+       "P3HIP_FLAG_INT8_ANY serves the conv trunks (" P3HIP_CONV_SET "); the transformer trunks (" P3HIP_TRANSFORMER_SET
+       ") have no INT8 plan"},
+      {k == Request::Fp32 && t.tfm_file && !r.f32_tfm,
+       "P3HIP_FLAG_FP32 serves the conv trunks only (" P3HIP_CONV_SET "); the transformer trunks run in fp16, or in "
+       "fp32 with P3HIP_FLAG_FP32_TFM"},
+      {k == Request::Fp32 && !t.tfm_file && !r.f32_conv,
+       "P3HIP_FLAG_FP32_TFM serves the transformer trunks only (" P3HIP_TRANSFORMER_SET "); the conv trunks have "
+       "P3HIP_FLAG_FP32"},
+      {!r.clash.empty(), r.clash},
+      {k == Request::LowLatency && opt.split_bad,
+       "P3HIP_FLAG_LOW_LATENCY: P3HIP_SPLIT must be \"S,T\" with S row strips of 1, 2 or 4 and output tiles of T = 16, 32 "
+       "or 64 channels"},
+      // (INT8_ANY's own path runs the nbt k_block shapes layer by layer, as conv trunks of the set)
+      {tr == Trunk::None || (k == Request::Int8Any && tr == Trunk::BlockShape && !t.in_set) || !t.hv_ok,
+       "unsupported architecture for the HIP engine (need a conv trunk (" P3HIP_CONV_SET "), or a transformer "
+       "trunk (" P3HIP_TRANSFORMER_SET "); H=32, V in {32,48,64,80} (transformer: V in {32,48,64}, and 80 at "
+       "d > 256))"},
+      // (INT8_C128 answers every trunk it does not serve with its own message, the runtime-width conv trunks included)
+      {k == Request::Int8C128 && !(r.alone && tr == Trunk::BlockShape && C == 128 && t.btl123),
+       "INT8_C128 is available only for C = 128 / C_b = 64 trunks of btl blocks with 1, 2 or 3 inner layers "
+       "(b12c128btl3, b10c128btl3, small and their kin, broadcast blocks at any interval), and not together with "
+       "another INT8 flag; nbt trunks, the other widths (P3HIP_FLAG_INT8_FUSED serves C = 256 / C_b = 128 btl trunks, "
+       "P3HIP_FLAG_INT8 the layer-wise trunks) and the transformer are not served"},
+      {(k == Request::Int8 || k == Request::Int8Fused) && tr == Trunk::OtherConv,
+       std::string(k == Request::Int8Fused ? "INT8_FUSED" : "INT8") + " is not available for this conv trunk: "
+       "P3HIP_FLAG_INT8 serves C = 384 / C_b = 192 btl or nbt blocks and C = 192 classic blocks, P3HIP_FLAG_INT8_FUSED "
+       "serves C = 256 / C_b = 128 btl blocks with 1, 2 or 3 inner layers, P3HIP_FLAG_INT8_C128 serves C = 128 / "
+       "C_b = 64 btl blocks with 1, 2 or 3 inner layers; the other widths run in fp16 only"},
+      {k == Request::Int8Fused && !(r.alone && tr == Trunk::BlockShape && C == 256 && t.btl123),
+       "INT8_FUSED is available only for C = 256 / C_b = 128 trunks of btl blocks with 1, 2 or 3 inner layers "
+       "(b12c256btl3 and its kin, broadcast blocks at any interval), and not together with P3HIP_FLAG_INT8; nbt and "
+       "C = 128 trunks, the layer-wise trunks (P3HIP_FLAG_INT8 serves those) and the transformer are not served"},
+      {k == Request::Int8 && tr != Trunk::LconvShape,
+       "INT8 is available only for layer-wise trunks (C = 384 / C_b = 192 btl or nbt blocks, C = 192 classic "
+       "blocks); this trunk runs fused block kernels or the transformer"},
+  };
+  for (const auto& refusal : refusals)
+    if (refusal.applies) {
+      err = refusal.text;
       return c;
     }
-    if (flags & (P3HIP_FLAG_INT8 | P3HIP_FLAG_INT8_FUSED | P3HIP_FLAG_INT8_C128 | P3HIP_FLAG_INT8_ANY)) {
-      err = "P3HIP_FLAG_LOW_LATENCY cannot be combined with P3HIP_FLAG_INT8, P3HIP_FLAG_INT8_FUSED, P3HIP_FLAG_INT8_C128 or "
-            "P3HIP_FLAG_INT8_ANY: its kernel runs in fp16";
-      return c;
-    }
-    if (flags & (P3HIP_FLAG_FP32 | P3HIP_FLAG_FP32_TFM)) {
-      err = "P3HIP_FLAG_LOW_LATENCY cannot be combined with P3HIP_FLAG_FP32 or P3HIP_FLAG_FP32_TFM: its kernel runs in fp16";
-      return c;
-    }
-    if (opt.split_bad) {
-      err = "P3HIP_FLAG_LOW_LATENCY: P3HIP_SPLIT must be \"S,T\" with S row strips of 1, 2 or 4 and output tiles of T = 16, 32 "
-            "or 64 channels";
-      return c;
-    }
-  }
-  bool i8any = false;
-  if (flags & P3HIP_FLAG_INT8_ANY) {
-    if (wf.btype == 3) {
-      err = "P3HIP_FLAG_INT8_ANY serves the conv trunks (" P3HIP_CONV_SET "); the transformer trunks (" P3HIP_TRANSFORMER_SET
-            ") have no INT8 plan";
-      return c;
-    }
-    if (flags & (P3HIP_FLAG_INT8 | P3HIP_FLAG_INT8_FUSED | P3HIP_FLAG_INT8_C128)) {
-      err = "P3HIP_FLAG_INT8_ANY cannot be combined with P3HIP_FLAG_INT8, P3HIP_FLAG_INT8_FUSED or P3HIP_FLAG_INT8_C128: it "
-            "chooses among their plans itself";
-      return c;
-    }
-    if (flags & (P3HIP_FLAG_FP32 | P3HIP_FLAG_FP32_TFM)) {
-      err = "P3HIP_FLAG_INT8_ANY cannot be combined with P3HIP_FLAG_FP32 or P3HIP_FLAG_FP32_TFM: an engine runs one "
-            "precision plan";
-      return c;
-    }
-    flags &= ~P3HIP_FLAG_INT8_ANY;
-    const bool btl123 = wf.btype == 0 && wf.inner >= 1 && wf.inner <= 3;
-    if (lw_shape && !opt.conv_any) flags |= P3HIP_FLAG_INT8;
-    else if (fused_shape && btl123) flags |= C == 256 ? P3HIP_FLAG_INT8_FUSED : P3HIP_FLAG_INT8_C128;
-    else i8any = true;
-  }
-  const bool int8 = (flags & (P3HIP_FLAG_INT8 | P3HIP_FLAG_INT8_FUSED | P3HIP_FLAG_INT8_C128)) != 0;
-  const bool i8f = (flags & (P3HIP_FLAG_INT8_FUSED | P3HIP_FLAG_INT8_C128)) != 0;
-  const bool i8c = (flags & P3HIP_FLAG_INT8_C128) != 0;
-  // P3HIP_FLAG_FP32 serves the conv trunks, P3HIP_FLAG_FP32_TFM the transformers; both together: whatever the trunk
-  const bool f32_conv = (flags & P3HIP_FLAG_FP32) != 0, f32_tfm = (flags & P3HIP_FLAG_FP32_TFM) != 0;
-  const bool f32 = f32_conv || f32_tfm;
-  if (f32 && wf.btype == 3 && !f32_tfm) {
-    err = "P3HIP_FLAG_FP32 serves the conv trunks only (" P3HIP_CONV_SET "); the transformer trunks run in fp16, or in "
-          "fp32 with P3HIP_FLAG_FP32_TFM";
-    return c;
-  }
-  if (f32 && wf.btype != 3 && !f32_conv) {
-    err = "P3HIP_FLAG_FP32_TFM serves the transformer trunks only (" P3HIP_TRANSFORMER_SET "); the conv trunks have "
-          "P3HIP_FLAG_FP32";
-    return c;
-  }
-  if (f32 && int8) {
-    err = std::string(f32_conv ? (f32_tfm ? "P3HIP_FLAG_FP32 | P3HIP_FLAG_FP32_TFM" : "P3HIP_FLAG_FP32") : "P3HIP_FLAG_FP32_TFM") +
-          " cannot be combined with P3HIP_FLAG_INT8, P3HIP_FLAG_INT8_FUSED or P3HIP_FLAG_INT8_C128: an "
-          "engine runs one precision plan";
-    return c;
-  }
-  const bool fused = !split && !i8any && !i8f && !f32 && exact && ((C == 256 && Cb == 128) || (C == 128 && Cb == 64));
-  // P3HIP_FLAG_INT8_FUSED: the btl trunks of the fused block kernel's C = 256 width; P3HIP_FLAG_INT8_C128: those of its
-  // C = 128 width; each alone among the three INT8 flags
-  const uint32_t i8_flags = flags & (P3HIP_FLAG_INT8 | P3HIP_FLAG_INT8_FUSED | P3HIP_FLAG_INT8_C128);
-  const bool i8_alone = (i8_flags & (i8_flags - 1)) == 0;
-  const bool i8f_ok = i8f && i8_alone && exact && (i8c ? (C == 128 && Cb == 64) : (C == 256 && Cb == 128)) && wf.btype == 0 &&
-                      wf.inner >= 1 && wf.inner <= 3;
-  // a conv trunk of P3HIP_CONV_SET, C and Cb padded to multiples of 64
-  const bool conv_ok = WeightFile::conv_set(wf.model_C, wf.model_Cb, wf.btype, wf.inner, wf.bint) && C % 64 == 0 &&
-                       (wf.btype == 2 || Cb % 64 == 0);
-  // every other conv trunk of P3HIP_CONV_SET: layer-wise through conv_any.hip
-  const bool any = !fused_shape && !lw_shape && conv_ok;
-  // (P3HIP_FLAG_FP32 runs the fused shapes layer by layer too, and so does Int8Any: the nbt ones, and classic C = 128)
-  const bool layerwise = lw_shape || i8f_ok || any || ((f32 || split) && fused_shape) || (i8any && conv_ok);
-  const bool v_ok = wf.V == 32 || wf.V == 48 || wf.V == 64 || wf.V == 80;
-  // transformer trunk: the file's C is the model width d and Cb the head count (include/p3hip.h: d a multiple of 32,
-  // 64 <= d <= 384, head width d / heads 32 or 64); the stream is padded to C = p3::tfm_stream_width(d), and V is what
-  // the heads of that width serve (the fused heads at C = 128 / 256: {32, 48, 64}; the C = 384 heads: v_ok)
-  const bool tfm = wf.btype == 3 && p3::tfm_supported(wf.model_C, Cb) && C == p3::tfm_stream_width(wf.model_C) &&
-                   (C == 384 || p3::heads_fusable(C, wf.V));
-  // (a trunk the fp16 engine serves and INT8_FUSED does not is refused below, with INT8_FUSED's own message)
-  const bool arch_ok = (fused && bottleneck_ok) || layerwise || tfm ||
-                       (i8f && fused_shape);
-  if (!arch_ok || wf.H != 32 || !v_ok) {
-    err = "unsupported architecture for the HIP engine (need a conv trunk (" P3HIP_CONV_SET "), or a transformer "
-          "trunk (" P3HIP_TRANSFORMER_SET "); H=32, V in {32,48,64,80} (transformer: V in {32,48,64}, and 80 at "
-          "d > 256))";
-    return c;
-  }
-  // (INT8_C128 answers every trunk it does not serve with its own message, the runtime-width conv trunks included)
-  if (i8c && !i8f_ok) {
-    err = "INT8_C128 is available only for C = 128 / C_b = 64 trunks of btl blocks with 1, 2 or 3 inner layers "
-          "(b12c128btl3, b10c128btl3, small and their kin, broadcast blocks at any interval), and not together with "
-          "another INT8 flag; nbt trunks, the other widths (P3HIP_FLAG_INT8_FUSED serves C = 256 / C_b = 128 btl trunks, "
-          "P3HIP_FLAG_INT8 the layer-wise trunks) and the transformer are not served";
-    return c;
-  }
-  if (any && int8) {
-    err = std::string(i8f ? "INT8_FUSED" : "INT8") + " is not available for this conv trunk: "
-          "P3HIP_FLAG_INT8 serves C = 384 / C_b = 192 btl or nbt blocks and C = 192 classic blocks, P3HIP_FLAG_INT8_FUSED "
-          "serves C = 256 / C_b = 128 btl blocks with 1, 2 or 3 inner layers, P3HIP_FLAG_INT8_C128 serves C = 128 / "
-          "C_b = 64 btl blocks with 1, 2 or 3 inner layers; the other widths run in fp16 only";
-    return c;
-  }
-  if (i8f && !i8f_ok) {
-    err = "INT8_FUSED is available only for C = 256 / C_b = 128 trunks of btl blocks with 1, 2 or 3 inner layers "
-          "(b12c256btl3 and its kin, broadcast blocks at any interval), and not together with P3HIP_FLAG_INT8; nbt and "
-          "C = 128 trunks, the layer-wise trunks (P3HIP_FLAG_INT8 serves those) and the transformer are not served";
-    return c;
-  }
-  if (int8 && !layerwise) {
-    err = "INT8 is available only for layer-wise trunks (C = 384 / C_b = 192 btl or nbt blocks, C = 192 classic "
-          "blocks); this trunk runs fused block kernels or the transformer";
-    return c;
-  }
-  // What is left is served.  (An INT8 flag left here has a layer-wise trunk that is not `any`; fp32 conv trunks are all
-  // layer-wise; k_blockw serves C = 256 / C_b = 128 btl trunks, whose inner count bottleneck_ok has checked.)
-  if (tfm) c.path = f32 ? Path::TfmF32 : Path::Tfm;
-  else if (f32) c.path = Path::F32Conv;
-  else if (split) c.path = Path::Split;
-  else if (i8any) c.path = Path::Int8Any;
-  else if (i8f) c.path = i8c ? Path::Int8Fused128 : Path::Int8Fused256;
-  else if (int8) c.path = Path::Int8;
-  else if (any || (opt.conv_any && lw_shape)) c.path = Path::ConvAny;
-  else if (lw_shape) c.path = Path::Layerwise;
-  else c.path = (opt.blockw && C == 256 && Cb == 128 && wf.btype == 0) ? Path::Blockw : Path::Fused;
+  c.path = path_of(r, t, wf, opt);
   // (layer-wise: p3::conv_any_slice(C) = 64 at classic C = 192 and at INT8_C128's C = 128, 128 at C = 384 and at
   // INT8_FUSED's C = 256)
-  c.CB = layerwise ? p3::conv_any_slice(C) : (tfm ? 128 : Cb);
-  c.CPI = layerwise ? p3::conv_any_init_pass(C) : 128;
-  c.heads_image = !f32 && p3::heads_fusable(C, wf.V);
+  c.CB = is_layerwise(c.path) ? p3::conv_any_slice(C) : (is_tfm(c.path) ? 128 : Cb);
+  c.CPI = is_layerwise(c.path) ? p3::conv_any_init_pass(C) : 128;
+  c.heads_image = !is_f32(c.path) && p3::heads_fusable(C, wf.V);
   c.heads_fused = c.heads_image && opt.heads_fuse && !runs_conv_any(c.path);
-  if (tfm) {
+  if (is_tfm(c.path)) {
     c.tfm_heads = Cb;
     c.tfm_D = wf.model_C / Cb;
   }
@@ -399,20 +425,33 @@ struct Builder {
   }
 };
 
+// Adds the weight image of one conv W ([kw][kw][cin][cout], zero-padded to cin_pad x cout_pad) for the kernel the path
+// runs it with, and returns its offset: conv_f32.h's image on the fp32 paths; k_sconv's for a trunk conv (`trunk`: a
+// layer conv or a broadcast block's 1x1) of Split; else an fp16 stream of output passes CP wide over K slices CB wide
+// (28 taps for the 25 of the init conv), whose macro-steps go to *nms.
+size_t add_conv_image(Builder& b, const float* W, int kw, int cin, int cout, int cin_pad, int cout_pad, bool trunk, int CB,
+                      int CP, int* nms) {
+  const int taps = kw * kw;
+  if (is_f32(b.plan.choice.path)) {
+    std::vector<float> w32;
+    p3::pack_conv_f32(w32, W, taps, cin, cout, cin_pad, cout_pad);
+    return b.ar.add(w32.data(), w32.size() * 4);
+  }
+  std::vector<_Float16> s;
+  if (trunk && b.plan.choice.path == Path::Split) {
+    p3::pack_sconv(s, W, taps, cin, cout, cin_pad, cout_pad);
+    return b.ar.add(s.data(), s.size() * 2);
+  }
+  for (int cp = 0; cp < cout_pad / CP; ++cp)
+    for (int ip = 0; ip < cin_pad / CB; ++ip) pack_segment(s, W, taps, kw == 5 ? 28 : taps, cin, cout, ip * CB, CB, cp * CP, CP);
+  return add_stream(b.ar, s, *nms, CP);
+}
+
 void pack_stem(Builder& b) {
   const WeightFile& wf = b.wf;
-  const int C = wf.C, CPI = b.plan.choice.CPI;
+  const int C = wf.C;
   const Tensor& w = wf.get("init_conv.w", (size_t)25 * 15 * C);  // [5][5][15][C]
-  if (is_f32(b.plan.choice.path)) {
-    std::vector<float> s32;
-    p3::pack_conv_f32(s32, w.data, 25, 15, C, 16, C);
-    b.plan.init_w32_off = b.ar.add(s32.data(), s32.size() * 4);
-  } else {
-    std::vector<_Float16> s;
-    for (int cp = 0; cp < C / CPI; ++cp)
-      pack_segment(s, w.data, 25, 28, 15, C, 0, 16, cp * CPI, CPI);
-    b.plan.init_stream_off = add_stream(b.ar, s, b.plan.init_nms, CPI);
-  }
+  b.plan.init_w_off = add_conv_image(b, w.data, 5, 15, C, 16, C, false, 16, b.plan.choice.CPI, &b.plan.init_nms);
   b.plan.game_w_off = b.ar.add(wf.get("init_game.w", (size_t)8 * C).data, 8 * C * 4);
   b.plan.game_b_off = b.ar.add(wf.get("init_game.b", (size_t)C).data, C * 4);
 }
@@ -468,40 +507,30 @@ void pack_broadcast_block(Builder& b, int i) {
   b.have_xa = false;
   bp.bn[0] = fold_bn(ar, wf, p + ".bn0", C);
   bp.bn[1] = fold_bn(ar, wf, p + ".bn1", C);
-  if (is_f32(b.plan.choice.path)) {
-    std::vector<float> w32;
-    p3::pack_conv_f32(w32, conv_w(wf, i, 0, 1, C, C), 1, C, C, C, C);
-    bp.w32_first = ar.add(w32.data(), w32.size() * 4);
-    w32.clear();
-    p3::pack_dense_f32(w32, wf.get(p + ".dense.w", (size_t)kNLoc * kNLoc).data);
-    bp.w32_dense = ar.add(w32.data(), w32.size() * 4);
-    w32.clear();
-    p3::pack_conv_f32(w32, conv_w(wf, i, 1, 1, C, C), 1, C, C, C, C);
-    bp.w32_last = ar.add(w32.data(), w32.size() * 4);
-    bp.dense_bias_off = ar.add(wf.get(p + ".dense.b", (size_t)kNLoc).data, kNLoc * 4);
-    b.plan.blocks.push_back(bp);
-    return;
-  }
-  const int CPb = (CB == 128) ? 128 : 64;
-  std::vector<_Float16> s0, s1, s2;
-  const bool split = b.plan.choice.path == Path::Split;   // the two 1x1 convs as k_sconv images, no streams of them
-  if (split) {
-    std::vector<_Float16> ws;
-    p3::pack_sconv(ws, conv_w(wf, i, 0, 1, C, C), 1, C, C, C, C);
-    bp.ws_first = ar.add(ws.data(), ws.size() * 2);
-    ws.clear();
-    p3::pack_sconv(ws, conv_w(wf, i, 1, 1, C, C), 1, C, C, C, C);
-    bp.ws_last = ar.add(ws.data(), ws.size() * 2);
-  }
-  for (int cp = 0; cp < (split ? 0 : C / CPb); ++cp)
-    for (int ip = 0; ip < C / CB; ++ip) {
-      pack_segment(s0, conv_w(wf, i, 0, 1, C, C), 1, 1, C, C, ip * CB, CB, cp * CPb, CPb);
-      pack_segment(s2, conv_w(wf, i, 1, 1, C, C), 1, 1, C, C, ip * CB, CB, cp * CPb, CPb);
-    }
+  const Path path = b.plan.choice.path;
+  const float *w0 = conv_w(wf, i, 0, 1, C, C), *w1 = conv_w(wf, i, 1, 1, C, C);
   const Tensor& dw = wf.get(p + ".dense.w", (size_t)kNLoc * kNLoc);  // [361 i][361 j]
-  pack_dense(s1, dw.data, 19);
+  // t = mish(conv_first(mish(bn0(x)))), u = the dense over t, x += conv_last(u); in the arena conv_first, the dense,
+  // conv_last (Split: the dense behind conv_last) and the dense's bias
+  LayerPlan first{1, C, C, true, 2, false, false, bp.bn[0], FoldedBN{}, 0, 1, -1};
+  LayerPlan last{1, C, C, false, 0, true, false, FoldedBN{}, FoldedBN{}, 3, 0, -1};
+  const int CPb = (CB == 128) ? 128 : 64;
+  first.w_off = add_conv_image(b, w0, 1, C, C, C, C, true, CB, CPb, &first.nms);
+  if (path == Path::Split) last.w_off = add_conv_image(b, w1, 1, C, C, C, C, true, CB, CPb, &last.nms);
+  if (is_f32(path)) {
+    std::vector<float> d32;
+    p3::pack_dense_f32(d32, dw.data);
+    bp.dense_off = ar.add(d32.data(), d32.size() * 4);
+  } else {
+    std::vector<_Float16> d16;
+    pack_dense(d16, dw.data, 19);
+    bp.dense_off = add_stream(ar, d16, bp.dense_nms, 128);
+  }
+  if (path != Path::Split) last.w_off = add_conv_image(b, w1, 1, C, C, C, C, true, CB, CPb, &last.nms);
+  bp.dense_bias_off = ar.add(wf.get(p + ".dense.b", (size_t)kNLoc).data, kNLoc * 4);
+  bp.layers = {first, last};
   // (k_blockw's trunks run their broadcast blocks as their own launches)
-  const bool fused_neighbours = b.plan.choice.path == Path::Fused && b.opt.bcast_fuse;
+  const bool fused_neighbours = path == Path::Fused && b.opt.bcast_fuse;
   // fused copies: output pass 1 takes its K slices in the order (1, 0) — slice 1 is the one
   // still in the act buffer when pass 0 ends (kernels.hip k_block, BC form)
   std::vector<_Float16> f0, f2;
@@ -509,8 +538,8 @@ void pack_broadcast_block(Builder& b, int i) {
     for (int cp = 0; cp < 2; ++cp)
       for (int k = 0; k < 2; ++k) {
         const int ip = cp == 0 ? k : 1 - k;
-        pack_segment(f0, conv_w(wf, i, 0, 1, C, C), 1, 1, C, C, ip * Cb, Cb, cp * Cb, Cb);
-        pack_segment(f2, conv_w(wf, i, 1, 1, C, C), 1, 1, C, C, ip * Cb, Cb, cp * Cb, Cb);
+        pack_segment(f0, w0, 1, 1, C, C, ip * Cb, Cb, cp * Cb, Cb);
+        pack_segment(f2, w1, 1, 1, C, C, ip * Cb, Cb, cp * Cb, Cb);
       }
   if (fused_neighbours && !b.cur.blocks.empty()) {
     b.cur.tail = f0;
@@ -525,7 +554,7 @@ void pack_broadcast_block(Builder& b, int i) {
       pack_dense(dpad, dw.data, 20);
       b.cur.tail.clear();
       for (int cp = 0; cp < 2; ++cp) {
-        for (int ip = 0; ip < 2; ++ip) pack_segment(b.cur.tail, conv_w(wf, i, 0, 1, C, C), 1, 1, C, C, ip * Cb, Cb, cp * Cb, Cb);
+        for (int ip = 0; ip < 2; ++ip) pack_segment(b.cur.tail, w0, 1, 1, C, C, ip * Cb, Cb, cp * Cb, Cb);
         b.cur.tail.insert(b.cur.tail.end(), dpad.begin(), dpad.end());
       }
     }
@@ -535,15 +564,11 @@ void pack_broadcast_block(Builder& b, int i) {
     b.cur.head = f2;
     b.cur.head_of = i;   // last_fused is set when the run is laid out
   }
-  if (!split) bp.stream_off = add_stream(ar, s0, bp.nms, CPb);
-  bp.stream2_off = add_stream(ar, s1, bp.nms2, 128);
-  if (!split) bp.stream3_off = add_stream(ar, s2, bp.nms3, CPb);
-  bp.dense_bias_off = ar.add(wf.get(p + ".dense.b", (size_t)kNLoc).data, kNLoc * 4);
   b.plan.blocks.push_back(bp);
 }
 
-// Layer-wise block i (kind 4): one LayerPlan per conv, with its fp16 stream, or its fp32 image (F32Conv), and on the
-// INT8 paths the quantized weights as well (the fp16 streams are what the calibration runs)
+// Layer-wise block i (kind 4): one LayerPlan per conv, with the weight image of the path's kernel (add_conv_image), and on
+// the INT8 paths the quantized weights as well (the fp16 streams are what the calibration runs)
 void pack_layerwise_block(Builder& b, int i) {
   const WeightFile& wf = b.wf;
   Arena& ar = b.ar;
@@ -567,26 +592,13 @@ void pack_layerwise_block(Builder& b, int i) {
   const FoldedBN none{};
   auto add_layer = [&](int j, int kw, int cin, int cout, bool pre, const FoldedBN& pre_bn, bool act, bool res,
                        bool dual, const FoldedBN& out_bn, int in_buf, int out_buf, int out2_buf) {
-    LayerPlan lp{kw, cin, cout, pre, act, res, dual, pre_bn, out_bn, in_buf, out_buf, out2_buf};
-    if (is_f32(path)) {
-      std::vector<float> w32;
-      p3::pack_conv_f32(w32, conv_w(wf, i, j, kw, cin, cout), kw * kw, cin, cout, cin, cout);
-      lp.w32_off = ar.add(w32.data(), w32.size() * 4);
-    } else if (path == Path::Split) {
-      std::vector<_Float16> s;
-      p3::pack_sconv(s, conv_w(wf, i, j, kw, cin, cout), kw * kw, cin, cout, cin, cout);
-      lp.ws_off = ar.add(s.data(), s.size() * 2);
-    } else {
-      std::vector<_Float16> s;
-      for (int cp = 0; cp < cout / 64; ++cp)
-        for (int ip = 0; ip < cin / 64; ++ip)
-          pack_segment(s, conv_w(wf, i, j, kw, cin, cout), kw * kw, kw * kw, cin, cout, ip * 64, 64, cp * 64, 64);
-      lp.stream_off = add_stream(ar, s, lp.nms, 64);
-    }
+    LayerPlan lp{kw, cin, cout, pre, act ? 1 : 0, res, dual, pre_bn, out_bn, in_buf, out_buf, out2_buf};
+    const float* W = conv_w(wf, i, j, kw, cin, cout);
+    lp.w_off = add_conv_image(b, W, kw, cin, cout, cin, cout, true, 64, 64, &lp.nms);
     if (is_int8(path)) {
       std::vector<int8_t> q;
       std::vector<float> sw;
-      p3::pack_lconv_i8(q, sw, conv_w(wf, i, j, kw, cin, cout), kw * kw, cin, cout);
+      p3::pack_lconv_i8(q, sw, W, kw * kw, cin, cout);
       lp.q_off = ar.add(q.data(), q.size());
       lp.qs_off = ar.add(sw.data(), sw.size() * 4);
       lp.qidx = b.plan.n_q++;
@@ -748,16 +760,7 @@ bool pack_heads(Builder& b, std::string& err) {
       w[(size_t)c * 96 + 32 + o] = wg[c * 32 + o];
       w[(size_t)c * 96 + 64 + o] = wv[c * 32 + o];
     }
-  if (is_f32(plan.choice.path)) {
-    std::vector<float> w32;
-    p3::pack_conv_f32(w32, w.data(), 1, C, 96, C, 128);
-    plan.heads_w32_off = ar.add(w32.data(), w32.size() * 4);
-  } else {
-    std::vector<_Float16> s;
-    for (int cp = 0; cp < 2; ++cp)
-      for (int ip = 0; ip < C / CB; ++ip) pack_segment(s, w.data(), 1, 1, C, 96, ip * CB, CB, cp * 64, 64);
-    plan.heads_stream_off = add_stream(ar, s, plan.heads_nms, 64);
-  }
+  plan.heads_w_off = add_conv_image(b, w.data(), 1, C, 96, C, 128, false, CB, 64, &plan.heads_nms);
   // the same weights as MFMA 16x16x32 A fragments for k_headsx (the convs inside the heads kernel):
   // [cout tile ct][k32 step][lane (n = lane & 15, q = lane >> 4)][8] = w[cin = 32 step + 8 q + e][cout = 16 ct + n]
   if (plan.choice.heads_image) {

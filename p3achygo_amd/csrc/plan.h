@@ -102,21 +102,25 @@ struct Arena {
 
 struct FoldedBN { size_t scale_off, shift_off; };
 
-// One conv launch of a layer-wise block (kind 4).  Regions: 0 = x; 1, 2 = the two C_b-channel
-// halves of the scratch buffer t; 3, 4 = those of u (3 also names u as a whole C-channel buffer).
+// One conv of a layer-wise block (kind 4), or one of the two 1x1 convs of a broadcast block (kind 3).  Regions: 0 = x;
+// 1, 2 = the two C_b-channel halves of the scratch buffer t; 3, 4 = those of u (1 and 3 also name t and u as whole
+// C-channel buffers).
 struct LayerPlan {
   int kw, cin, cout;
-  bool pre, act, res, dual;   // see p3::LConvArgs
+  bool pre;
+  int act;                    // 0, 1 = mish(out_bn(y)), 2 = mish(y) (conv_first of a broadcast block)
+  bool res, dual;             // see p3::LConvArgs
   FoldedBN pre_bn, out_bn;    // prologue / epilogue BN (epilogue: of act or of dual's second output)
   int in_buf, out_buf, out2_buf;
-  size_t stream_off = 0;
+  // The weight image of the kernel the path runs this conv with: an fp16 stream of nms macro-steps (k_lconv and its
+  // runtime-width twin, which the INT8 paths calibrate through; k_conv1x1 on a broadcast block), conv_f32.h
+  // pack_conv_f32 (F32Conv) or conv_split.h pack_sconv (Split)
+  size_t w_off = 0;
   int nms = 0;
   // INT8 paths: the quantized weights (lconv_i8.h pack_lconv_i8), their per-output-channel scales, and the index of
   // this layer's input among the engine's quantized tensors (its output, when quantized, is the next one: its consumer)
   size_t q_off = 0, qs_off = 0;
   int qidx = -1;
-  size_t w32_off = 0;   // F32Conv: the fp32 weight image (conv_f32.h pack_conv_f32)
-  size_t ws_off = 0;    // Split: k_sconv's fragment image (conv_split.h pack_sconv)
 };
 
 // One transformer block (kind 5): arena offsets of its tensors, the GEMM weights as MFMA A fragments (transformer.h)
@@ -125,17 +129,18 @@ struct TfmPlan { size_t rms_in = 0, rms_out = 0, wqkv = 0, wo = 0, wgu = 0, wdow
 struct BlockPlan {
   int kind;  // 0 btl, 1 nbt, 3 broadcast, 4 layer-wise, 5 transformer
   TfmPlan tfm;
+  // layer-wise: one per conv.  broadcast: conv_first {kw 1, C -> C, pre, act 2, x -> t} and conv_last {res, u -> x}
   std::vector<LayerPlan> layers;
+  // fused blocks: the block's stream; the launch picks the macro-step size (kernels.h block_macro_step_bytes)
   size_t stream_off = 0;
   int nms = 0;
-  size_t stream_bytes = 0;   // fused blocks: the launch picks the macro-step size (kernels.h block_macro_step_bytes)
+  size_t stream_bytes = 0;
   FoldedBN bn[p3::kMaxBlockLayers];
-  // broadcast extras
-  size_t stream2_off = 0, stream3_off = 0;
-  int nms2 = 0, nms3 = 0;
+  // broadcast: the dense matrix for the path's kernel (an fp16 stream of dense_nms macro-steps, or conv_f32.h
+  // pack_dense_f32) and its bias
+  size_t dense_off = 0;
+  int dense_nms = 0;
   size_t dense_bias_off = 0;
-  size_t w32_first = 0, w32_dense = 0, w32_last = 0;   // F32Conv: conv_first, the dense, conv_last in fp32
-  size_t ws_first = 0, ws_last = 0;                    // Split: conv_first and conv_last as k_sconv images
   // Broadcast 1x1 convs taken into the neighbouring block launches (k_block's BC form).
   //   on a broadcast block: its conv_first runs at the tail of the launch before it / its conv_last
   //   at the head of the launch after it;
@@ -180,14 +185,12 @@ struct BlockwRun { size_t first; int nblk; size_t stream_off, prm_off; };
 struct Plan {
   PlanChoice choice;
   std::vector<BlockPlan> blocks;
-  size_t init_stream_off = 0; int init_nms = 0;
-  size_t init_w32_off = 0;   // F32Conv, TfmF32: the init conv in fp32
+  size_t init_w_off = 0; int init_nms = 0;   // the init conv: an fp16 stream, or pack_conv_f32's image (F32Conv, TfmF32)
   size_t game_w_off = 0, game_b_off = 0;
   size_t rope_cos_off = 0, rope_sin_off = 0;   // transformer
   int n_q = 0;   // INT8 paths: quantized tensors (activation scales)
   std::vector<BlockwRun> bw_runs;
-  size_t heads_stream_off = 0; int heads_nms = 0;
-  size_t heads_w32_off = 0;
+  size_t heads_w_off = 0; int heads_nms = 0;   // the three head convs C -> 96, as the init conv
   size_t heads_conv_a_off = 0, heads_image_off = 0;
   FoldedBN heads_gbn{};                     // policy.gpool_bn
   size_t head_tensor_off[kNumHeadTensors] = {};   // by kHeadTensors index
