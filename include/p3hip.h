@@ -190,6 +190,28 @@ typedef struct p3hip_engine p3hip_engine;
                                        64) for every launch (tests, A/B runs).  p3hip_create returns NULL for a transformer
                                        trunk, together with any INT8 flag, together with P3HIP_FLAG_FP32 or
                                        P3HIP_FLAG_FP32_TFM, and for a P3HIP_SPLIT outside those sets */
+#define P3HIP_FLAG_LOW_LATENCY_TFM 8192u /* the same for the transformer trunks: every trunk of P3HIP_TRANSFORMER_SET runs
+                                       the fp16 plan with the three launches of a block handed to more workgroups
+                                       (csrc/transformer_split.hip): the attention of a (position, head)
+                                       in S = 1, 2, 3 or 6 parts of its 23 query tiles, qkv and ffn with T = 16, 32 or 64
+                                       tokens per workgroup, chosen per launch from the positions it covers and the CUs.
+                                       Every query row and token row is computed as the default plan computes it: the
+                                       results are the default fp16 plan's, bit for bit, for every split, and where the split
+                                       is (1, 64) (on 256 CUs and d96h3: from 43 positions on) the launches are the default
+                                       plan's.  The arena, the stem, the heads and the buffers are the default plan's.
+                                       Measured forward-pass time over the default plan's at batch 1 / 8 / 16 / 32, launch
+                                       graph on both: b14d96h3_transformer 0.53 / 0.62 / 0.69 / 0.86
+                                       (0.309 ms against 0.587 ms at batch 1), a 14-block d192h6 net 0.50 / 0.56 / 0.79 /
+                                       1.00; equal times from 64 and 32 positions on, where the split is (1, 64).
+                                       Composes with everything the default transformer plan composes with.
+                                       P3HIP_TFM_SPLIT="S,T" in the environment at p3hip_create forces one split for every
+                                       launch (tests, A/B runs).  p3hip_create returns NULL for a conv trunk when
+                                       P3HIP_FLAG_LOW_LATENCY is not set as well, together with any INT8 flag,
+                                       P3HIP_FLAG_FP32 or P3HIP_FLAG_FP32_TFM, and for a P3HIP_TFM_SPLIT outside those sets */
+#define P3HIP_FLAG_LOW_LATENCY_ANY (4096u | 8192u) /* P3HIP_FLAG_LOW_LATENCY | P3HIP_FLAG_LOW_LATENCY_TFM: the low-latency
+                                       plan whatever the trunk.  A conv trunk takes the plan of P3HIP_FLAG_LOW_LATENCY
+                                       (bit-identical to that flag alone), a transformer trunk that of
+                                       P3HIP_FLAG_LOW_LATENCY_TFM */
 
 /* Transformer trunks (python/model_transformer.py TransformerBlock, a generic_arch of "transformer" blocks) the engine
  * runs: every block has the same embed_dim d and num_heads h, d equals the stem's channels, d is a multiple of 32 with
@@ -462,7 +484,8 @@ int p3hip_get_raw(p3hip_engine* e, int slot, float* out);
  * INT8 engine k_lconv_i8<3,..> (P3HIP_FLAG_INT8_ANY on a trunk of its own path: k_lconv_i8_any<3>, and the FLOPs at the file's own
  * widths), and writes the FLOPs of one 3x3 conv.  A P3HIP_FLAG_FP32 engine is layer-wise whatever its
  * trunk: it times k_lconv_f32<3> and writes the FLOPs of one 3x3 conv at the file's own widths; so is a
- * P3HIP_FLAG_LOW_LATENCY engine, with k_sconv<3>. */
+ * P3HIP_FLAG_LOW_LATENCY engine, with k_sconv<3>.  A P3HIP_FLAG_LOW_LATENCY_TFM engine times the attention launch of the
+ * split in force for n_positions: k_tfm_attn_split, or k_tfm_attn where that is one part, with the same FLOPs. */
 double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
                                double* flops_per_launch, const char** kernel_name);
 /* Test hook, no device: loads the file and builds the host-side plan of (file, flags, the P3HIP_* environment) as
@@ -478,6 +501,10 @@ const char* p3hip_debug_plan(const char* weights_path, uint32_t flags, int* n_q,
  * raw fp16 bits; returns the number of elements, writes at most n of them. */
 int p3hip_debug_split(int npos, int kw, int cout, int n_cu, int* strips, int* tile);
 long p3hip_debug_pack_sconv(const float* w, int taps, int cin, int cout, int cin_pad, int cout_pad, uint16_t* out, long n);
+/* Test hook, no device (P3HIP_FLAG_LOW_LATENCY_TFM): the query parts per (position, head) of the attention launch and the
+ * tokens per workgroup of the qkv and ffn launches over npos positions of a trunk with `heads` heads on a device of n_cu
+ * CUs, the P3HIP_TFM_SPLIT override included; 0, or 1 for a bad argument or a bad P3HIP_TFM_SPLIT. */
+int p3hip_debug_tfm_split(int npos, int heads, int n_cu, int* parts, int* tokens);
 /* P3HIP_FLAG_LAUNCH_GRAPH: 1 once the full-batch forward pass has been captured and is being replayed,
  * 0 before (or without the flag), -1 when the capture failed and the engine fell back to plain launches. */
 int p3hip_graph_state(const p3hip_engine* e);

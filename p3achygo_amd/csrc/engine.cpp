@@ -28,6 +28,7 @@
 #include "lconv_i8.h"
 #include "transformer.h"
 #include "transformer_f32.h"
+#include "transformer_split.h"
 
 using namespace eng;
 
@@ -250,6 +251,14 @@ int p3hip_debug_split(int npos, int kw, int cout, int n_cu, int* strips, int* ti
   if (npos < 1 || (kw != 1 && kw != 3) || cout < 64 || cout % 64 != 0 || n_cu < 1 || !strips || !tile || opt.split_bad) return 1;
   if (opt.split_s) { *strips = opt.split_s; *tile = opt.split_t; }
   else p3::sconv_split(npos, kw, cout, n_cu, strips, tile);
+  return 0;
+}
+
+int p3hip_debug_tfm_split(int npos, int heads, int n_cu, int* parts, int* tokens) {
+  const Options opt = Options::from_env();
+  if (npos < 1 || heads < 1 || n_cu < 1 || !parts || !tokens || opt.tfm_split_bad) return 1;
+  if (opt.tfm_split_s) { *parts = opt.tfm_split_s; *tokens = opt.tfm_split_t; }
+  else p3::tfm_split(npos, heads, n_cu, parts, tokens);
   return 0;
 }
 
@@ -691,9 +700,15 @@ double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
   switch (path) {
     case Path::Tfm:
     case Path::TfmF32:
+    case Path::TfmSplit:
       // q.k^T and p.v over the 361 x 361 tokens of every head (algorithmic, not the padded 384 keys)
       flops = 2.0 * n_positions * 2.0 * kNLoc * kNLoc * wf.model_C;
       name = path == Path::TfmF32 ? p3::tfm_attn_f32_kernel_name() : "k_tfm_attn";
+      if (path == Path::TfmSplit) {   // the attention launch of the split in force for these positions
+        int parts = 1, tokens = 64;
+        tfm_split_of(e, n_positions, &parts, &tokens);
+        if (parts > 1) name = "k_tfm_attn_split";
+      }
       break;
     case Path::Int8Fused256:
     case Path::Int8Fused128:

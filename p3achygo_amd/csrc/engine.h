@@ -191,6 +191,7 @@ namespace eng {
 enum class LayerKernel { Lconv, LconvAny, LconvI8, LconvI8Any, LconvF32, Sconv };
 LayerKernel layer_kernel(const p3hip_engine* e);
 const char* layer_kernel_name(LayerKernel k, int kw, int cin, int cout);
+void tfm_split_of(const p3hip_engine* e, int npos, int* parts, int* tokens);   // Path::TfmSplit: the split of a launch
 bool enqueue_forward(p3hip_engine* e, const Pass& p);
 bool expand_sym(p3hip_engine* e, const unsigned char* src, int n);
 bool run_pass(p3hip_engine* e, const Pass& p);

@@ -10,6 +10,7 @@
 #include "lconv_i8.h"
 #include "transformer.h"
 #include "transformer_f32.h"
+#include "transformer_split.h"
 
 namespace eng {
 namespace {
@@ -261,12 +262,16 @@ bool enqueue_tfm_block(p3hip_engine* e, const Pass& p, const BlockPlan& bp) {
   _Float16 *q = e->d_qkv, *k = q + per, *v = k + per, *o = e->d_t;
   p3::TfmQkvArgs a{e->d_x, q, k, v, npos, e->dev<float>(bp.tfm.rms_in), e->d_arena + bp.tfm.wqkv,
                    e->dev<float>(e->plan.rope_cos_off), e->dev<float>(e->plan.rope_sin_off)};
-  if (!e->check(p3::launch_tfm_qkv(d, D, a, s), "launch k_tfm_qkv")) return false;
+  // (TfmSplit: the split of this launch; (1, 64) is the default plan's launches, which launch_tfm_*_split then call)
+  int parts = 1, tokens = 64;
+  if (e->trunk_path() == Path::TfmSplit) tfm_split_of(e, npos, &parts, &tokens);
+  if (!e->check(p3::launch_tfm_qkv_split(d, D, a, tokens, s), "launch k_tfm_qkv")) return false;
   const p3::TfmAttnArgs b{q, k, v, o, npos, e->plan.choice.tfm_heads};
-  if (!timed_launch(e, p.timed, [&] { return e->check(p3::launch_tfm_attn(D, b, s), "launch k_tfm_attn"); })) return false;
+  if (!timed_launch(e, p.timed, [&] { return e->check(p3::launch_tfm_attn_split(D, b, parts, s), "launch k_tfm_attn"); }))
+    return false;
   const p3::TfmFfnArgs f{o, e->d_x, npos, e->d_arena + bp.tfm.wo, e->dev<float>(bp.tfm.rms_out),
                          e->d_arena + bp.tfm.wgu, e->d_arena + bp.tfm.wdown};
-  return e->check(p3::launch_tfm_ffn(d, f, s), "launch k_tfm_ffn");
+  return e->check(p3::launch_tfm_ffn_split(d, f, tokens, s), "launch k_tfm_ffn");
 }
 
 bool enqueue_tfm_block_f32(p3hip_engine* e, const Pass& p, const BlockPlan& bp) {
@@ -502,6 +507,12 @@ bool enqueue_heads(p3hip_engine* e, const Pass& p) {
 }
 
 }  // namespace
+
+// The split of a TfmSplit engine's launches over npos positions: P3HIP_TFM_SPLIT's, or the chooser's
+void tfm_split_of(const p3hip_engine* e, int npos, int* parts, int* tokens) {
+  if (e->opt.tfm_split_s) { *parts = e->opt.tfm_split_s; *tokens = e->opt.tfm_split_t; }
+  else p3::tfm_split(npos, e->plan.choice.tfm_heads, e->n_cu, parts, tokens);
+}
 
 // The kernel of the layer convs: the path's, and on the INT8 paths while they calibrate the fp16 plan's.  (The fused INT8
 // paths run whole blocks, enqueue_block_i8, once calibrated; Int8Fused128 calibrates through the runtime-width kernel:

@@ -14,6 +14,7 @@
 #include "lconv_i8.h"
 #include "transformer.h"
 #include "transformer_f32.h"
+#include "transformer_split.h"
 
 namespace eng {
 
@@ -42,6 +43,13 @@ Options Options::from_env() {
       o.split_bad = true;
     }
   }
+  if (const char* sp = getenv("P3HIP_TFM_SPLIT")) {
+    char tail = 0;
+    if (sscanf(sp, "%d,%d%c", &o.tfm_split_s, &o.tfm_split_t, &tail) != 2 || !p3::tfm_split_valid(o.tfm_split_s, o.tfm_split_t)) {
+      o.tfm_split_s = o.tfm_split_t = 0;
+      o.tfm_split_bad = true;
+    }
+  }
   return o;
 }
 
@@ -60,6 +68,7 @@ const char* path_name(Path p) {
     case Path::Split: return "Split";
     case Path::Tfm: return "Tfm";
     case Path::TfmF32: return "TfmF32";
+    case Path::TfmSplit: return "TfmSplit";
   }
   return "?";
 }
@@ -109,11 +118,13 @@ TrunkClass classify(const WeightFile& wf) {
 
 // What the precision flags ask for: one plan
 struct Request {
-  enum Kind { Fp16, Int8, Int8Fused, Int8C128, Int8Any, Fp32, LowLatency } kind = Fp16;
+  enum Kind { Fp16, Int8, Int8Fused, Int8C128, Int8Any, Fp32, LowLatency, LowLatencyTfm } kind = Fp16;
   bool int8_any = false;   // P3HIP_FLAG_INT8_ANY was given (kind is the plan it chose)
   bool alone = true;       // Int8Fused, Int8C128: no other of the three INT8 flags beside it
   bool f32_conv = false, f32_tfm = false;   // Fp32: P3HIP_FLAG_FP32 serves the conv trunks, P3HIP_FLAG_FP32_TFM the
                                             // transformers; both together: whatever the trunk
+  bool ll_tfm = false;     // LowLatency: P3HIP_FLAG_LOW_LATENCY_TFM stands beside P3HIP_FLAG_LOW_LATENCY (whatever the
+                           // trunk); LowLatencyTfm is that flag alone, which serves the transformers only
   std::string clash;       // the flags cannot be combined: the refusal's text
 };
 
@@ -125,8 +136,8 @@ Request::Kind int8_any_choice(const TrunkClass& t, int C, bool conv_any) {
   return Request::Int8Any;
 }
 
-// The flags read once.  P3HIP_FLAG_LOW_LATENCY, then P3HIP_FLAG_INT8_ANY, then the fp32 flags name the plan, and whatever
-// else stands beside them is a clash; of the three other INT8 flags together INT8_C128 speaks, then INT8_FUSED.
+// The flags read once.  P3HIP_FLAG_LOW_LATENCY, then P3HIP_FLAG_LOW_LATENCY_TFM, then P3HIP_FLAG_INT8_ANY, then the fp32
+// flags name the plan, and whatever else stands beside them is a clash; of the three other INT8 flags together INT8_C128 speaks, then INT8_FUSED.
 Request read_request(uint32_t flags, const TrunkClass& t, int C, const Options& opt) {
   const uint32_t i8_three = flags & (P3HIP_FLAG_INT8 | P3HIP_FLAG_INT8_FUSED | P3HIP_FLAG_INT8_C128);
   const bool fp32_flag = (flags & (P3HIP_FLAG_FP32 | P3HIP_FLAG_FP32_TFM)) != 0;
@@ -135,11 +146,20 @@ Request read_request(uint32_t flags, const TrunkClass& t, int C, const Options& 
   r.f32_tfm = (flags & P3HIP_FLAG_FP32_TFM) != 0;
   if (flags & P3HIP_FLAG_LOW_LATENCY) {
     r.kind = Request::LowLatency;
+    r.ll_tfm = (flags & P3HIP_FLAG_LOW_LATENCY_TFM) != 0;
     if (i8_three || (flags & P3HIP_FLAG_INT8_ANY))
       r.clash = "P3HIP_FLAG_LOW_LATENCY cannot be combined with P3HIP_FLAG_INT8, P3HIP_FLAG_INT8_FUSED, P3HIP_FLAG_INT8_C128 or "
                 "P3HIP_FLAG_INT8_ANY: its kernel runs in fp16";
     else if (fp32_flag)
       r.clash = "P3HIP_FLAG_LOW_LATENCY cannot be combined with P3HIP_FLAG_FP32 or P3HIP_FLAG_FP32_TFM: its kernel runs in fp16";
+  } else if (flags & P3HIP_FLAG_LOW_LATENCY_TFM) {
+    r.kind = Request::LowLatencyTfm;
+    if (i8_three || (flags & P3HIP_FLAG_INT8_ANY))
+      r.clash = "P3HIP_FLAG_LOW_LATENCY_TFM cannot be combined with P3HIP_FLAG_INT8, P3HIP_FLAG_INT8_FUSED, P3HIP_FLAG_INT8_C128 "
+                "or P3HIP_FLAG_INT8_ANY: its kernels run in fp16";
+    else if (fp32_flag)
+      r.clash = "P3HIP_FLAG_LOW_LATENCY_TFM cannot be combined with P3HIP_FLAG_FP32 or P3HIP_FLAG_FP32_TFM: its kernels run in "
+                "fp16";
   } else if (flags & P3HIP_FLAG_INT8_ANY) {
     r.kind = int8_any_choice(t, C, opt.conv_any);
     r.int8_any = true;
@@ -164,7 +184,10 @@ Request read_request(uint32_t flags, const TrunkClass& t, int C, const Options& 
 
 // The path of a request the refusals let through
 Path path_of(const Request& r, const TrunkClass& t, const WeightFile& wf, const Options& opt) {
-  if (t.trunk == Trunk::Transformer) return r.kind == Request::Fp32 ? Path::TfmF32 : Path::Tfm;
+  if (t.trunk == Trunk::Transformer) {
+    if (r.kind == Request::LowLatencyTfm || (r.kind == Request::LowLatency && r.ll_tfm)) return Path::TfmSplit;
+    return r.kind == Request::Fp32 ? Path::TfmF32 : Path::Tfm;
+  }
   switch (r.kind) {
     case Request::Fp32: return Path::F32Conv;
     case Request::LowLatency: return Path::Split;
@@ -172,6 +195,7 @@ Path path_of(const Request& r, const TrunkClass& t, const WeightFile& wf, const 
     case Request::Int8Fused: return Path::Int8Fused256;
     case Request::Int8C128: return Path::Int8Fused128;
     case Request::Int8: return Path::Int8;
+    case Request::LowLatencyTfm:   // (refused on every conv trunk)
     case Request::Fp16: break;
   }
   if (t.trunk == Trunk::OtherConv || (t.trunk == Trunk::LconvShape && opt.conv_any)) return Path::ConvAny;
@@ -192,9 +216,13 @@ PlanChoice choose_plan(const WeightFile& wf, uint32_t flags, const Options& opt,
   // Every refusal, in the order of precedence: the first that applies answers.  (A flag that names the plan first says
   // which trunks it serves, then what cannot stand beside it; a request has one kind, so the first four never compete.)
   const struct { bool applies; std::string text; } refusals[] = {
-      {k == Request::LowLatency && t.tfm_file,
+      // (the text is from before the transformers had a low-latency plan: P3HIP_FLAG_LOW_LATENCY_TFM's)
+      {k == Request::LowLatency && t.tfm_file && !r.ll_tfm,
        "P3HIP_FLAG_LOW_LATENCY serves the conv trunks (" P3HIP_CONV_SET "); the transformer trunks (" P3HIP_TRANSFORMER_SET
        ") have no low-latency plan"},
+      {k == Request::LowLatencyTfm && !t.tfm_file,
+       "P3HIP_FLAG_LOW_LATENCY_TFM serves the transformer trunks only (" P3HIP_TRANSFORMER_SET "); the conv trunks have "
+       "P3HIP_FLAG_LOW_LATENCY"},
       {r.int8_any && t.tfm_file,
        "P3HIP_FLAG_INT8_ANY serves the conv trunks (" P3HIP_CONV_SET "); the transformer trunks (" P3HIP_TRANSFORMER_SET
        ") have no INT8 plan"},
@@ -205,9 +233,12 @@ PlanChoice choose_plan(const WeightFile& wf, uint32_t flags, const Options& opt,
        "P3HIP_FLAG_FP32_TFM serves the transformer trunks only (" P3HIP_TRANSFORMER_SET "); the conv trunks have "
        "P3HIP_FLAG_FP32"},
       {!r.clash.empty(), r.clash},
-      {k == Request::LowLatency && opt.split_bad,
+      {k == Request::LowLatency && !t.tfm_file && opt.split_bad,
        "P3HIP_FLAG_LOW_LATENCY: P3HIP_SPLIT must be \"S,T\" with S row strips of 1, 2 or 4 and output tiles of T = 16, 32 "
        "or 64 channels"},
+      {(k == Request::LowLatencyTfm || (k == Request::LowLatency && t.tfm_file)) && opt.tfm_split_bad,
+       "P3HIP_FLAG_LOW_LATENCY_TFM: P3HIP_TFM_SPLIT must be \"S,T\" with S query parts of 1, 2, 3 or 6 and T = 16, 32 or 64 "
+       "tokens per workgroup"},
       // (INT8_ANY's own path runs the nbt k_block shapes layer by layer, as conv trunks of the set)
       {tr == Trunk::None || (k == Request::Int8Any && tr == Trunk::BlockShape && !t.in_set) || !t.hv_ok,
        "unsupported architecture for the HIP engine (need a conv trunk (" P3HIP_CONV_SET "), or a transformer "
@@ -854,7 +885,7 @@ bool build_plan(const WeightFile& wf, uint32_t flags, const Options& opt, Plan& 
   pack_stem(b);
   if (is_tfm(path)) pack_rope(b);
   for (int i = 0; i < wf.nblocks; ++i) {
-    if (path == Path::Tfm) pack_tfm_block<_Float16>(b, i, pack_afrag);
+    if (path == Path::Tfm || path == Path::TfmSplit) pack_tfm_block<_Float16>(b, i, pack_afrag);
     else if (path == Path::TfmF32) pack_tfm_block<float>(b, i, p3::pack_tfm_f32);
     else {
       if (is_layerwise(path)) b.flush_run();

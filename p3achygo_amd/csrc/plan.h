@@ -37,6 +37,11 @@ struct Options {
   // set to something else than a pair of the kernel's sets, which fails the creation of such an engine
   int split_s = 0, split_t = 0;
   bool split_bad = false;
+  // P3HIP_TFM_SPLIT="S,T" (P3HIP_FLAG_LOW_LATENCY_TFM engines; tests, A/B runs): every launch of a transformer block takes
+  // S query parts per (position, head) and T tokens per workgroup.  0, 0: the launch chooses (transformer_split.h
+  // tfm_split).  tfm_split_bad: set to something else than a pair of the kernels' sets, which fails such an engine's creation
+  int tfm_split_s = 0, tfm_split_t = 0;
+  bool tfm_split_bad = false;
   static Options from_env();
 };
 
@@ -58,8 +63,10 @@ enum class Path {
                   // split across workgroups; stem, broadcast dense and heads as ConvAny's
   Tfm,            // transformer trunk, fp16
   TfmF32,         // P3HIP_FLAG_FP32_TFM: transformer trunk through transformer_f32.hip
+  TfmSplit,       // P3HIP_FLAG_LOW_LATENCY_TFM: Tfm's arena, stem, heads and buffers; the blocks' launches split across more
+                  // workgroups (transformer_split.hip), bit-identical to Tfm
 };
-inline bool is_tfm(Path p) { return p == Path::Tfm || p == Path::TfmF32; }
+inline bool is_tfm(Path p) { return p == Path::Tfm || p == Path::TfmF32 || p == Path::TfmSplit; }
 inline bool is_f32(Path p) { return p == Path::F32Conv || p == Path::TfmF32; }
 inline bool is_int8_fused(Path p) { return p == Path::Int8Fused256 || p == Path::Int8Fused128; }
 // (an INT8 engine calibrates through the fp16 layer-wise plan: `calibrating` is a run-time state of the engine)

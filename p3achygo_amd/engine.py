@@ -36,7 +36,7 @@ EXPORTS = [
     "p3hip_get_aux",
     "p3hip_load_targets", "p3hip_loss", "p3hip_get_loss", "p3hip_debug_loss_rows",
     "p3hip_debug_plan", "p3hip_debug_act_i8",
-    "p3hip_debug_split", "p3hip_debug_pack_sconv",
+    "p3hip_debug_split", "p3hip_debug_pack_sconv", "p3hip_debug_tfm_split",
 ]
 
 FLAG_RUN_ALL_SLOTS = 2
@@ -74,6 +74,10 @@ OUTPUT_NAMES = tuple(sorted(list(AUX_SEGMENTS) + list(RAW_SEGMENTS) + list(RESUL
 # runs of 1 to about 64 positions: every conv trunk layer by layer through k_sconv, a position split across workgroups
 # (include/p3hip.h)
 FLAG_LOW_LATENCY = 4096
+# the same for the transformer trunks: a block's launches split across more workgroups, the default fp16 plan's bits
+# (include/p3hip.h)
+FLAG_LOW_LATENCY_TFM = 8192
+FLAG_LOW_LATENCY_ANY = FLAG_LOW_LATENCY | FLAG_LOW_LATENCY_TFM   # the low-latency plan whatever the trunk
 FLAG_SYMMETRY_AVG = 32  # every slot averaged over a set of the eight symmetries on the device
 
 
@@ -506,6 +510,18 @@ def debug_plan(path: str, flags: int = 0):
     if name is None:
         raise EngineError("p3hip_create: " + L.p3hip_create_error().decode())
     return name.decode(), n_q.value, dig.value
+
+
+def debug_tfm_split(npos: int, heads: int, n_cu: int = 256):
+    """(query parts per (position, head) of the attention launch, tokens per workgroup of qkv and ffn) of a
+    FLAG_LOW_LATENCY_TFM engine's launches over npos positions, P3HIP_TFM_SPLIT included: p3hip_debug_tfm_split, no device
+    needed.  ValueError for a bad argument or a bad P3HIP_TFM_SPLIT."""
+    L = lib()
+    L.p3hip_debug_tfm_split.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    s, t = C.c_int(0), C.c_int(0)
+    if L.p3hip_debug_tfm_split(npos, heads, n_cu, C.byref(s), C.byref(t)) != 0:
+        raise ValueError("p3hip_debug_tfm_split: bad argument or bad P3HIP_TFM_SPLIT")
+    return s.value, t.value
 
 
 def debug_split(npos: int, kw: int, cout: int, n_cu: int = 256):

@@ -97,8 +97,8 @@ struct EvalPlayerConfig {   // PlayerSearchConfig (player_config.h:20-108), same
   // extension: the player's engine runs its trunk's fp32 plan (P3HIP_FLAG_FP32_ANY: conv and transformer trunks).  0 = the fp16 plan.  A net
   // against itself with one player in fp32 measures what fp16 costs in play.
   int nn_fp32 = 0;
-  // extension: the player's engine runs the low-latency plan (P3HIP_FLAG_LOW_LATENCY: conv trunks, a position split across
-  // workgroups).  For players whose engines see few positions at a time: a timed search turns the forward pass's latency
+  // extension: the player's engine runs its trunk's low-latency plan (P3HIP_FLAG_LOW_LATENCY_ANY: conv trunks, a position
+  // split across workgroups; transformer trunks, a block's launches split across workgroups).  For players whose engines see few positions at a time: a timed search turns the forward pass's latency
   // into visits per move.
   int nn_low_latency = 0;
 };

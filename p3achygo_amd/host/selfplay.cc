@@ -1629,7 +1629,7 @@ int p3host_eval_match(const char* engine_lib, const char* cur_weights, const cha
       ev[e].reset(h);
       const uint32_t sym_mask = pc[e].nn_symmetry_mask;
       const uint32_t flags = P3HIP_FLAG_SHARED_DEVICE | (sym_mask ? P3HIP_FLAG_SYMMETRY_AVG : 0u) |   // the two players' passes run concurrently
-                             (pc[e].nn_fp32 ? P3HIP_FLAG_FP32_ANY : 0u) | (pc[e].nn_low_latency ? P3HIP_FLAG_LOW_LATENCY : 0u);
+                             (pc[e].nn_fp32 ? P3HIP_FLAG_FP32_ANY : 0u) | (pc[e].nn_low_latency ? P3HIP_FLAG_LOW_LATENCY_ANY : 0u);
       if (!h->Open(engine_lib, e == 0 ? cur_weights : cand_weights, slots, device, flags) ||
           (sym_mask && !h->SetSymmetries(sym_mask))) {
         if (err) snprintf(err, 256, "%s", h->err.c_str());
@@ -1799,7 +1799,7 @@ int p3host_eval_match_threads(const char* engine_lib, const char* cur_weights, c
       // leaf and its inverse stay, since the averaged result comes back in the orientation it was loaded in
       const uint32_t sym_mask = pc[e].nn_symmetry_mask;
       const uint32_t flags = P3HIP_FLAG_SHARED_DEVICE | (sym_mask ? P3HIP_FLAG_SYMMETRY_AVG : 0u) |
-                             (pc[e].nn_fp32 ? P3HIP_FLAG_FP32_ANY : 0u) | (pc[e].nn_low_latency ? P3HIP_FLAG_LOW_LATENCY : 0u);
+                             (pc[e].nn_fp32 ? P3HIP_FLAG_FP32_ANY : 0u) | (pc[e].nn_low_latency ? P3HIP_FLAG_LOW_LATENCY_ANY : 0u);
       if (!h->Open(engine_lib, e == 0 ? cur_weights : cand_weights, batch, device, flags) ||
           (sym_mask && !h->SetSymmetries(sym_mask))) {
         if (err) snprintf(err, 256, "%s", h->err.c_str());
