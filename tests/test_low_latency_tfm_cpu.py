@@ -212,6 +212,9 @@ def test_player_key_maps_to_both_bits():
 
 # ---- kernel resources (the manner of tests/test_transformer_kernel_resources_cpu.py) ---------------------------------
 
+TFM_CORE = ["transformer_core.h", "transformer_qkv_body.inc", "transformer_attn_body.inc", "transformer_ffn_body.inc"]
+
+
 def _assembly(stem, sources):
     h = hashlib.sha256()
     for f in sources:
@@ -244,7 +247,7 @@ def _kernels(asm, suffix):
 def split_kernels():
     if shutil.which("hipcc") is None:
         pytest.skip("no hipcc")
-    asm = _assembly("transformer_split", ["transformer_split.hip", "transformer_split.h", "transformer.h"])
+    asm = _assembly("transformer_split", ["transformer_split.hip", "transformer_split.h", "transformer.h"] + TFM_CORE)
     body = asm[:asm.index(".amdhsa_kernel")]
     assert "scratch_" not in body and "v_mfma_f32_16x16x32_f16" in asm
     return _kernels(asm, "_split")
@@ -254,7 +257,7 @@ def split_kernels():
 def default_kernels():
     if shutil.which("hipcc") is None:
         pytest.skip("no hipcc")
-    return _kernels(_assembly("transformer", ["transformer.hip", "transformer.h"]), "")
+    return _kernels(_assembly("transformer", ["transformer.hip", "transformer.h"] + TFM_CORE), "")
 
 
 def test_the_instantiation_set_is_the_expected_one(split_kernels):
@@ -302,7 +305,7 @@ def test_k_tfm_qkv_still_contracts_rope_the_way_the_split_kernels_spell_out():
     chooses otherwise changes the default plan's bits, and this file's kernels have to follow it"""
     if shutil.which("hipcc") is None:
         pytest.skip("no hipcc")
-    asm = _assembly("transformer", ["transformer.hip", "transformer.h"])
+    asm = _assembly("transformer", ["transformer.hip", "transformer.h"] + TFM_CORE)
     seen = 0
     for m in re.finditer(r"^(_ZN2p3\S*k_tfm_qkv\S*):[^\n]*\n(.*?)\n\s*\.section", asm, re.S | re.M):
         blocks = []

@@ -12,7 +12,8 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "p3achygo_amd", "csrc")
-SOURCES = ["transformer.hip", "transformer.h"]
+SOURCES = ["transformer.hip", "transformer.h", "transformer_core.h", "transformer_qkv_body.inc",
+           "transformer_attn_body.inc", "transformer_ffn_body.inc"]
 LDS_PER_CU = 160 * 1024
 WIDTHS = [64, 96, 128, 160, 192, 224, 256, 288, 320, 352, 384]
 # (VGPRs incl. AGPRs, LDS bytes) of the b14d96h3_transformer kernels as first built
