@@ -176,7 +176,9 @@ typedef struct p3hip_engine p3hip_engine;
                                        fp16, layer by layer, through k_sconv (csrc/conv_split.hip), which splits a position
                                        into row strips and output-channel tiles across many workgroups, where every other
                                        plan gives a position to one workgroup and leaves the other CUs idle.  The stem, the
-                                       broadcast dense and the heads are those of the runtime-width plan.  Results are fp16
+                                       broadcast dense and the heads are bit-identical to those of the runtime-width plan
+                                       (split forms of them where a launch's positions leave CUs idle: csrc/edge_split.hip,
+                                       DESIGN.md section 17; P3HIP_EDGE_SPLIT below).  Results are fp16
                                        with the rounding points of the layer-wise plan (DESIGN.md sections 7 and 15), the
                                        same bits at every batch size, in every slot and for every split.  It costs throughput
                                        at large batches.  Measured forward-pass time over the default plan's at batch
@@ -198,7 +200,10 @@ typedef struct p3hip_engine p3hip_engine;
                                        Every query row and token row is computed as the default plan computes it: the
                                        results are the default fp16 plan's, bit for bit, for every split, and where the split
                                        is (1, 64) (on 256 CUs and d96h3: from 43 positions on) the launches are the default
-                                       plan's.  The arena, the stem, the heads and the buffers are the default plan's.
+                                       plan's.  The arena and the buffers are the default plan's; the stem and the heads are
+                                       bit-identical to the default plan's (a stem of 256 or 384 channels and the heads kernel
+                                       k_heads run split where a launch's positions leave CUs idle, csrc/edge_split.hip,
+                                       DESIGN.md section 17; k_headsx stays whole), with one small buffer more.
                                        Measured forward-pass time over the default plan's at batch 1 / 8 / 16 / 32, launch
                                        graph on both: b14d96h3_transformer 0.53 / 0.62 / 0.69 / 0.86
                                        (0.309 ms against 0.587 ms at batch 1), a 14-block d192h6 net 0.50 / 0.56 / 0.79 /
@@ -505,6 +510,15 @@ long p3hip_debug_pack_sconv(const float* w, int taps, int cin, int cout, int cin
  * tokens per workgroup of the qkv and ffn launches over npos positions of a trunk with `heads` heads on a device of n_cu
  * CUs, the P3HIP_TFM_SPLIT override included; 0, or 1 for a bad argument or a bad P3HIP_TFM_SPLIT. */
 int p3hip_debug_tfm_split(int npos, int heads, int n_cu, int* parts, int* tokens);
+/* Test hook, no device (both low-latency flags): the parts per position of the stem, the broadcast dense and the heads
+ * launches over npos positions of a stream of c_pad channels (a multiple of 64 up to 512) on a device of n_cu CUs
+ * (csrc/edge_split.h), the P3HIP_EDGE_SPLIT override included.  stem: 1 or the stem's output passes
+ * (c_pad / 128, or c_pad / 64 where c_pad is no multiple of 128); dense: 1, 3 or 12; heads: 1, 4 or 8 (ignored where
+ * the heads kernel is k_headsx).  A part count of 1 is the unsplit launch.  Returns 0, or 1 (and 1, 1, 1) for a bad argument or a P3HIP_EDGE_SPLIT outside those sets.
+ * P3HIP_EDGE_SPLIT="s,d,h" in the environment at p3hip_create forces the parts of every such launch of an engine with
+ * either low-latency flag (tests, A/B runs); "0" forces 1,1,1, the launches of the engine before the split forms existed;
+ * p3hip_create returns NULL for any other value.  Without a low-latency flag nothing reads it. */
+int p3hip_debug_edge_split(int npos, int c_pad, int n_cu, int* stem, int* dense, int* heads);
 /* P3HIP_FLAG_LAUNCH_GRAPH: 1 once the full-batch forward pass has been captured and is being replayed,
  * 0 before (or without the flag), -1 when the capture failed and the engine fell back to plain launches. */
 int p3hip_graph_state(const p3hip_engine* e);

@@ -25,6 +25,7 @@
 #include "conv_any.h"
 #include "conv_f32.h"
 #include "conv_split.h"
+#include "edge_split.h"
 #include "lconv_i8.h"
 #include "transformer.h"
 #include "transformer_f32.h"
@@ -154,6 +155,9 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
             (e->wf.btype != 1 || path == Path::F32Conv || e->check(hipMalloc((void**)&e->d_s, R * e->wf.Cb * kNLoc * 2), "hipMalloc s")) &&
             (!is_tfm(path) || e->check(hipMalloc((void**)&e->d_qkv, qkv_bytes), "hipMalloc qkv")) &&
             e->check(hipMalloc((void**)&e->d_hp, R * 96 * kNLoc * 4), "hipMalloc hp") &&
+            // (the split heads' pooled values, edge_split.h: the two low-latency paths only)
+            ((path != Path::Split && path != Path::TfmSplit) ||
+             e->check(hipMalloc((void**)&e->d_pool, R * p3::kHeadsPoolFloats * 4), "hipMalloc pooled")) &&
             e->check(hipMalloc((void**)&e->d_out, B * p3::kOutStride * 4), "hipMalloc out") &&
             (!sym || (e->check(hipMalloc((void**)&e->d_sfeats, B * kFeatBytes), "hipMalloc symmetry upload") &&
                       e->check(hipMalloc((void**)&e->d_cout, R * p3::kOutStride * 4), "hipMalloc copy rows"))) &&
@@ -201,7 +205,7 @@ void p3hip_destroy(p3hip_engine* e) {
   if (e->stream || e->d_arena) (void)hipSetDevice(e->device);
   if (e->stream) hipStreamSynchronize(e->stream);
   hipFree(e->d_arena); hipFree(e->d_feats); hipFree(e->d_x); hipFree(e->d_t); hipFree(e->d_u); hipFree(e->d_s);
-  hipFree(e->d_hp); hipFree(e->d_out); hipFree(e->d_res); hipFree(e->d_qkv);
+  hipFree(e->d_hp); hipFree(e->d_pool); hipFree(e->d_out); hipFree(e->d_res); hipFree(e->d_qkv);
   hipFree(e->d_sfeats); hipFree(e->d_cout); hipFree(e->d_aux);
   hipFree(e->d_bw_stamps);
   hipFree(e->d_amax); hipFree(e->d_ascale);
@@ -251,6 +255,21 @@ int p3hip_debug_split(int npos, int kw, int cout, int n_cu, int* strips, int* ti
   if (npos < 1 || (kw != 1 && kw != 3) || cout < 64 || cout % 64 != 0 || n_cu < 1 || !strips || !tile || opt.split_bad) return 1;
   if (opt.split_s) { *strips = opt.split_s; *tile = opt.split_t; }
   else p3::sconv_split(npos, kw, cout, n_cu, strips, tile);
+  return 0;
+}
+
+int p3hip_debug_edge_split(int npos, int c_pad, int n_cu, int* stem, int* dense, int* heads) {
+  if (stem) *stem = 1;
+  if (dense) *dense = 1;
+  if (heads) *heads = 1;
+  const Options opt = Options::from_env();
+  if (npos < 1 || !p3::edge_width_ok(c_pad) || n_cu < 1 || !stem || !dense || !heads || opt.edge_bad) return 1;
+  if (opt.edge_s) {
+    if (!p3::edge_split_valid(c_pad, opt.edge_s, opt.edge_d, opt.edge_h)) return 1;
+    *stem = opt.edge_s; *dense = opt.edge_d; *heads = opt.edge_h;
+  } else {
+    p3::edge_split(npos, c_pad, n_cu, stem, dense, heads);
+  }
   return 0;
 }
 

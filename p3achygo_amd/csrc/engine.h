@@ -93,6 +93,7 @@ struct p3hip_engine {
 #endif
   _Float16* d_s = nullptr;   // nbt trunks: the block kernel's inner-stream scratch (t and u carry the broadcast blocks' tensors)
   float* d_hp = nullptr;
+  float* d_pool = nullptr;   // Split, TfmSplit: what the split heads pool per row, [rows][p3::kHeadsPoolFloats] (edge_split.h)
   // P3HIP_FLAG_AUX: k_heads_aux writes one record per row of the pass into d_aux [rows][kAuxStride],
   // allocated under the flag only; aux_args: its weight pointers, set once at create (a pass fills hp, aux and npos)
   float* d_aux = nullptr;
@@ -192,6 +193,8 @@ enum class LayerKernel { Lconv, LconvAny, LconvI8, LconvI8Any, LconvF32, Sconv }
 LayerKernel layer_kernel(const p3hip_engine* e);
 const char* layer_kernel_name(LayerKernel k, int kw, int cin, int cout);
 void tfm_split_of(const p3hip_engine* e, int npos, int* parts, int* tokens);   // Path::TfmSplit: the split of a launch
+// Path::Split, Path::TfmSplit: the parts per position of the stem, broadcast dense and heads launches (edge_split.h)
+void edge_split_of(const p3hip_engine* e, int npos, int* stem, int* dense, int* heads);
 bool enqueue_forward(p3hip_engine* e, const Pass& p);
 bool expand_sym(p3hip_engine* e, const unsigned char* src, int n);
 bool run_pass(p3hip_engine* e, const Pass& p);

@@ -6,6 +6,7 @@
 #include "conv_any.h"
 #include "conv_f32.h"
 #include "conv_split.h"
+#include "edge_split.h"
 #include "engine.h"
 #include "lconv_i8.h"
 #include "transformer.h"
@@ -251,6 +252,12 @@ bool enqueue_stem(p3hip_engine* e, const Pass& p) {
   a.feats = p.feats; a.x = e->d_x; a.npos = p.npos;
   a.wstream = e->d_arena + pl.init_w_off; a.nms_total = pl.init_nms;
   a.game_w = e->dev<float>(pl.game_w_off); a.game_b = e->dev<float>(pl.game_b_off);
+  // the low-latency plans: a position's output passes on as many workgroups, where the launch's split says so
+  if (e->trunk_path() == Path::Split || e->trunk_path() == Path::TfmSplit) {
+    int stem = 1, dense = 1, heads = 1;
+    edge_split_of(e, p.npos, &stem, &dense, &heads);
+    if (stem > 1) return e->check(p3::launch_init_split(C, a, stem, e->n_cu, e->stream), "launch k_init_split");
+  }
   return e->check(runs_conv_any(e->trunk_path()) ? p3::launch_init_any(C, a, grid_for(e, p.npos, 1), e->stream)
                                              : p3::launch_init(C, a, grid_for(e, p.npos, 1), e->stream), "launch k_init");
 }
@@ -391,8 +398,13 @@ bool enqueue_broadcast_block_layers(p3hip_engine* e, const Pass& p, const BlockP
     const p3::BDenseF32Args d{(float*)e->d_t, (float*)e->d_u, npos, C, e->dev<float>(bp.dense_off), e->dev<float>(bp.dense_bias_off),
                               e->dev<float>(bp.bn[1].scale_off), e->dev<float>(bp.bn[1].shift_off)};
     if (!e->check(p3::launch_bdense_f32(d, e->n_cu, e->stream), "launch k_bdense_f32")) return false;
-  } else if (!e->check(p3::launch_bdense_any(C, bdense_args(e, bp, npos), grid_for(e, npos, 1), e->stream), "launch bdense")) {
-    return false;
+  } else {
+    int stem = 1, dense = 1, heads = 1;
+    edge_split_of(e, npos, &stem, &dense, &heads);
+    const p3::BDenseArgs d = bdense_args(e, bp, npos);
+    if (!(dense > 1 ? e->check(p3::launch_bdense_split(C, d, dense, e->n_cu, e->stream), "launch k_bdense_split")
+                    : e->check(p3::launch_bdense_any(C, d, grid_for(e, npos, 1), e->stream), "launch bdense")))
+      return false;
   }
   return launch_layer(e, p, bp.layers[1], f32 ? "launch conv_last (fp32)" : "launch conv_last (k_sconv)");
 }
@@ -498,7 +510,15 @@ bool enqueue_heads(p3hip_engine* e, const Pass& p) {
   }
   p3::HeadsArgs h = e->heads_args;   // the weight pointers never change after create
   h.x = e->d_x; h.hp = e->d_hp; h.out = p.out; h.res = p.res; h.npos = p.npos;
+  // the low-latency plans: k_heads in three launches over more workgroups, where the launch's split says so (k_headsx
+  // stays whole: edge_split.h)
+  int hparts = 1;
+  if (!e->plan.choice.heads_fused && (e->trunk_path() == Path::Split || e->trunk_path() == Path::TfmSplit)) {
+    int stem = 1, dense = 1;
+    edge_split_of(e, p.npos, &stem, &dense, &hparts);
+  }
   if (!(e->plan.choice.heads_fused ? e->check(p3::launch_headsx(C, h, e->n_cu, e->stream), "launch k_headsx")
+        : hparts > 1               ? e->check(p3::launch_heads_split(h, e->d_pool, hparts, e->stream), "launch k_heads_pool / points / softmax")
                                    : e->check(p3::launch_heads(h, p.npos, e->stream), "launch k_heads"))) return false;
   if (!aux) return true;
   p3::HeadsAuxArgs x = e->aux_args;
@@ -512,6 +532,13 @@ bool enqueue_heads(p3hip_engine* e, const Pass& p) {
 void tfm_split_of(const p3hip_engine* e, int npos, int* parts, int* tokens) {
   if (e->opt.tfm_split_s) { *parts = e->opt.tfm_split_s; *tokens = e->opt.tfm_split_t; }
   else p3::tfm_split(npos, e->plan.choice.tfm_heads, e->n_cu, parts, tokens);
+}
+
+// The parts of a low-latency engine's stem, broadcast dense and heads launches over npos positions: P3HIP_EDGE_SPLIT's, or
+// the chooser's
+void edge_split_of(const p3hip_engine* e, int npos, int* stem, int* dense, int* heads) {
+  if (e->opt.edge_s) { *stem = e->opt.edge_s; *dense = e->opt.edge_d; *heads = e->opt.edge_h; }
+  else p3::edge_split(npos, e->wf.C, e->n_cu, stem, dense, heads);
 }
 
 // The kernel of the layer convs: the path's, and on the INT8 paths while they calibrate the fp16 plan's.  (The fused INT8

@@ -11,6 +11,7 @@
 #include "conv_any.h"
 #include "conv_f32.h"
 #include "conv_split.h"
+#include "edge_split.h"
 #include "lconv_i8.h"
 #include "transformer.h"
 #include "transformer_f32.h"
@@ -48,6 +49,16 @@ Options Options::from_env() {
     if (sscanf(sp, "%d,%d%c", &o.tfm_split_s, &o.tfm_split_t, &tail) != 2 || !p3::tfm_split_valid(o.tfm_split_s, o.tfm_split_t)) {
       o.tfm_split_s = o.tfm_split_t = 0;
       o.tfm_split_bad = true;
+    }
+  }
+  if (const char* sp = getenv("P3HIP_EDGE_SPLIT")) {
+    char tail = 0;
+    if (strcmp(sp, "0") == 0) {
+      o.edge_s = o.edge_d = o.edge_h = 1;
+    } else if (sscanf(sp, "%d,%d,%d%c", &o.edge_s, &o.edge_d, &o.edge_h, &tail) != 3 || o.edge_s < 1 || o.edge_s > 8 ||
+               !p3::edge_split_valid(64, 1, o.edge_d, o.edge_h)) {   // (s against the file's width: choose_plan)
+      o.edge_s = o.edge_d = o.edge_h = 0;
+      o.edge_bad = true;
     }
   }
   return o;
@@ -239,6 +250,11 @@ PlanChoice choose_plan(const WeightFile& wf, uint32_t flags, const Options& opt,
       {(k == Request::LowLatencyTfm || (k == Request::LowLatency && t.tfm_file)) && opt.tfm_split_bad,
        "P3HIP_FLAG_LOW_LATENCY_TFM: P3HIP_TFM_SPLIT must be \"S,T\" with S query parts of 1, 2, 3 or 6 and T = 16, 32 or 64 "
        "tokens per workgroup"},
+      {(k == Request::LowLatency || k == Request::LowLatencyTfm) &&
+           (opt.edge_bad || (opt.edge_s && !p3::edge_split_valid(C, opt.edge_s, opt.edge_d, opt.edge_h))),
+       "P3HIP_FLAG_LOW_LATENCY / P3HIP_FLAG_LOW_LATENCY_TFM: P3HIP_EDGE_SPLIT must be \"0\" or \"s,d,h\" with s = 1 or the "
+       "stem's output passes (the stream's channels / 128, or / 64 where they are no multiple of 128), d = 1, 3 or 12 parts "
+       "of the broadcast dense and h = 1, 4 or 8 parts of the heads"},
       // (INT8_ANY's own path runs the nbt k_block shapes layer by layer, as conv trunks of the set)
       {tr == Trunk::None || (k == Request::Int8Any && tr == Trunk::BlockShape && !t.in_set) || !t.hv_ok,
        "unsupported architecture for the HIP engine (need a conv trunk (" P3HIP_CONV_SET "), or a transformer "

@@ -42,6 +42,12 @@ struct Options {
   // tfm_split).  tfm_split_bad: set to something else than a pair of the kernels' sets, which fails such an engine's creation
   int tfm_split_s = 0, tfm_split_t = 0;
   bool tfm_split_bad = false;
+  // P3HIP_EDGE_SPLIT="s,d,h" (engines of either low-latency flag; tests, A/B runs): the parts per position of every stem,
+  // broadcast dense and heads launch (edge_split.h; s is 1 or the stem's output passes, which depends on the file and is
+  // checked by choose_plan).  "0": all three unsplit, 1,1,1.  0, 0, 0: the launch chooses (edge_split).  edge_bad: the
+  // variable is set to something else, which fails the creation of such an engine
+  int edge_s = 0, edge_d = 0, edge_h = 0;
+  bool edge_bad = false;
   static Options from_env();
 };
 

@@ -36,7 +36,7 @@ EXPORTS = [
     "p3hip_get_aux",
     "p3hip_load_targets", "p3hip_loss", "p3hip_get_loss", "p3hip_debug_loss_rows",
     "p3hip_debug_plan", "p3hip_debug_act_i8",
-    "p3hip_debug_split", "p3hip_debug_pack_sconv", "p3hip_debug_tfm_split",
+    "p3hip_debug_split", "p3hip_debug_pack_sconv", "p3hip_debug_tfm_split", "p3hip_debug_edge_split",
 ]
 
 FLAG_RUN_ALL_SLOTS = 2
@@ -522,6 +522,19 @@ def debug_tfm_split(npos: int, heads: int, n_cu: int = 256):
     if L.p3hip_debug_tfm_split(npos, heads, n_cu, C.byref(s), C.byref(t)) != 0:
         raise ValueError("p3hip_debug_tfm_split: bad argument or bad P3HIP_TFM_SPLIT")
     return s.value, t.value
+
+
+def debug_edge_split(npos: int, c_pad: int, n_cu: int = 256):
+    """(stem, broadcast dense, heads) parts per position of a low-latency engine's launches around the trunk over npos
+    positions of a c_pad-channel stream (csrc/edge_split.h), P3HIP_EDGE_SPLIT included: p3hip_debug_edge_split, no device
+    needed.  ValueError for a bad argument or a bad P3HIP_EDGE_SPLIT (the hook then answers 1, 1, 1)."""
+    L = lib()
+    L.p3hip_debug_edge_split.argtypes = [C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 3
+    s, d, h = C.c_int(0), C.c_int(0), C.c_int(0)
+    if L.p3hip_debug_edge_split(npos, c_pad, n_cu, C.byref(s), C.byref(d), C.byref(h)) != 0:
+        assert (s.value, d.value, h.value) == (1, 1, 1)
+        raise ValueError("p3hip_debug_edge_split: bad argument or bad P3HIP_EDGE_SPLIT")
+    return s.value, d.value, h.value
 
 
 def debug_split(npos: int, kw: int, cout: int, n_cu: int = 256):

@@ -1,6 +1,8 @@
-"""Register, scratch and code-size table of two builds of kernels.hip and conv_any.hip, from the compiler's assembly:
+"""Register, scratch and code-size table of two builds of kernels.hip, conv_any.hip and edge_split.hip, from the
+compiler's assembly:
   tools/kernel_resource_table.py PARENT_DIR NEW_DIR > profiles/layer_kernels_resources.txt
-Each directory holds kernels.s and conv_any.s, made with
+Each directory holds kernels.s and conv_any.s, and edge_split.s where the build has that file (a unit only NEW_DIR has
+is listed with its own figures), made with
   hipcc -O3 -std=c++17 --offload-arch=gfx950 --cuda-device-only -S p3achygo_amd/csrc/X.hip -o DIR/X.s
 One row per kernel: VGPRs (with AGPRs), SGPRs, ScratchSize, spilled VGPRs + SGPRs, code bytes, parent -> new; then the
 scratch instructions of every k_init by loop depth.  Needs no GPU."""
@@ -38,8 +40,11 @@ def kernels(path):
 
 
 def main(parent, new):
-    for unit in ("kernels.s", "conv_any.s"):
-        a, b = kernels(os.path.join(parent, unit)), kernels(os.path.join(new, unit))
+    for unit in ("kernels.s", "conv_any.s", "edge_split.s"):
+        if unit == "edge_split.s" and not os.path.exists(os.path.join(new, unit)):
+            continue
+        b = kernels(os.path.join(new, unit))
+        a = kernels(os.path.join(parent, unit)) if os.path.exists(os.path.join(parent, unit)) else b   # new unit: its own figures
         assert set(a) == set(b), sorted(set(a) ^ set(b))
         names = subprocess.run(["c++filt"] + list(a), capture_output=True, text=True, check=True).stdout.split("\n")
         short = {n: re.sub(r"\(.*", "", d).replace("void ", "").replace("p3::", "") for n, d in zip(a, names)}
