@@ -92,6 +92,17 @@ __device__ __forceinline__ size_t sgpr_offset(size_t v) {
   return v;
 }
 
+// sum / max over the 64 lanes of a wave, the result in every lane (the heads' pooling and softmaxes)
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  return v;
+}
 
 // row (column-padded index) -> validity and plain location
 template <int S>

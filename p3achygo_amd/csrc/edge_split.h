@@ -19,7 +19,9 @@
 //
 // All cut along lines that leave each output value's arithmetic as it is, so the results are those of the unsplit
 // kernels bit for bit (tests/test_edge_split_gpu.py compares bytes).  Where the chooser answers 1 the launch IS the unsplit
-// kernel (launch_init, launch_init_any, launch_bdense_any, launch_heads).
+// kernel (launch_init, launch_init_any, launch_bdense_any, launch_heads).  The passages a split kernel has in common with
+// its unsplit one are one text, included by both (stem_*.inc, bdense_*.inc, heads_score_bin.inc); edge_split.hip's head
+// says which two of the heads are still written twice.
 //
 // Plans whose heads are k_headsx (the transformer plans at stream 128 or 256 with V <= 64, b14d96h3_transformer among
 // them) keep it: its pooling order is not k_heads', and P3HIP_FLAG_LOW_LATENCY_TFM is pinned to the default plan's bytes.

@@ -5,7 +5,11 @@
 // passes taken out of the workgroup: a workgroup keeps ONE pass (the stem's cp, the dense's jp) for all its items, so its
 // weight ring walks that pass's part of the stream circularly and never has to change streams between items, and deals
 // itself the (position [, half [, channel tile]]) items of that pass round.  What a lane computes for an output value is
-// the text of those bodies: the same conv_segment instantiation, the same epilogue expressions.
+// what it computes there, from one text: stem_planes.inc, stem_epilogue.inc, bdense_transpose.inc and bdense_epilogue.inc
+// are included here and in those bodies, around the same conv_segment instantiation.  Of the heads,
+// heads_score_bin.inc is shared with k_heads; the pooling quad and the per-point loop are k_heads' text written a second
+// time, because k_heads' code objects change when it takes its operands through the names a shared text needs
+// (DESIGN.md §17).  The wave reductions are conv_core.h's.
 #include "edge_split.h"
 
 #include <hip/hip_runtime.h>
@@ -55,42 +59,8 @@ __global__ void __launch_bounds__(kWG, 2) k_init_split(InitSplitArgs aa) {
   const int lr = lane & 31, h = lane >> 5;
 
   for (int pos = blockIdx.x / NCP; pos < a.npos; pos += gridDim.x / NCP) {
-    const unsigned char* f = (const unsigned char*)a.feats + (size_t)pos * FeatOff::size;
-    const int color = (signed char)f[FeatOff::color];
-    // ---- planes -> LDS (one thread per board point), as init_body ---------------------
-    for (int loc = threadIdx.x; loc < kNLoc; loc += kWG) {
-      h8 lo = {0, 0, 0, 0, 0, 0, 0, 0}, hi = {0, 0, 0, 0, 0, 0, 0, 0};
-      auto our = [&](int off) {
-        return (_Float16)((signed char)f[off + loc] == color ? 1.0f : 0.0f);
-      };
-      auto opp = [&](int off) {
-        return (_Float16)((signed char)f[off + loc] == -color ? 1.0f : 0.0f);
-      };
-      lo[0] = our(FeatOff::board); lo[1] = opp(FeatOff::board);
-      lo[7] = our(FeatOff::atari); hi[0] = opp(FeatOff::atari);
-      hi[1] = our(FeatOff::two); hi[2] = opp(FeatOff::two);
-      hi[3] = our(FeatOff::three); hi[4] = opp(FeatOff::three);
-      hi[5] = our(FeatOff::ladder); hi[6] = opp(FeatOff::ladder);
-      const int y = (loc * 3450) >> 16, xx = loc - y * kBL;
-#pragma unroll
-      for (int m = 0; m < 5; ++m) {
-        const int* lm = (const int*)(f + FeatOff::last + m * 8);
-        if (lm[0] == y && lm[1] == xx) lo[2 + m] = (_Float16)1.0f;  // pass {19,0}/noop never match
-      }
-      const int s = G::PADTOP + y * G::S + xx;
-      *(h8*)(smem + s * G::SLOTB) = lo;
-      *(h8*)(smem + s * G::SLOTB + 16) = hi;
-    }
-    // ---- game-state scalars (LoadFeatures) ------------------------------------------
-    float gsv[8];
-    gsv[0] = color == 1 ? 1.0f : 0.0f;
-    gsv[1] = color == 1 ? 0.0f : 1.0f;
-#pragma unroll
-    for (int m = 0; m < 5; ++m) {
-      const int* lm = (const int*)(f + FeatOff::last + m * 8);
-      gsv[2 + m] = (lm[0] == 19 && lm[1] == 0) ? 1.0f : 0.0f;
-    }
-    gsv[7] = (color == 1 ? -1.0f : 1.0f) * (*(const float*)(f + FeatOff::komi)) / 15.0f;
+    // ---- feature planes -> LDS, game-state scalars -> gsv[8] ----------------------------
+#include "stem_planes.inc"
 
     // game-state dense of this pass's channels: thread tc computes (gs . Wg + b)[cp CP + tc] into LDS behind the ring
     // (init_body's sum, term by term); the first ring acquire of the K loop below is the barrier that publishes it
@@ -108,25 +78,8 @@ __global__ void __launch_bounds__(kWG, 2) k_init_split(InitSplitArgs aa) {
     acc_zero<G, CP>(acc);
     conv_segment<G, CP, 5, 28>(ring, smem, acc);
     // epilogue: + (gs . Wg + b)[c]  -> x
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) {
-        const int cl = acc_chan<G, CP>(mt, g4), c = cp * CP + cl;
-        const f32x4 bias = *(const f32x4*)(bias_lds + cl);
-#pragma unroll
-        for (int j = 0; j < T::NT; ++j) {
-          const int t = lg + j * T::LG;
-          if (t >= G::NT_TOTAL) continue;
-          const int r = t * 32 + lr;
-          int loc;
-          if (!row_valid<G::S>(r, loc)) continue;
-          h4 o;
-#pragma unroll
-          for (int i = 0; i < 4; ++i) o[i] = (_Float16)(acc[mt][j][g4 * 4 + i] + bias[i]);
-          *(h4*)(a.x + ((size_t)pos * (C / 8) + (c >> 3)) * (kNLoc * 8) + loc * 8 + h * 4) = o;
-        }
-      }
+    constexpr int bias_cp = 0;
+#include "stem_epilogue.inc"
     lds_barrier();   // the next position rewrites the planes and the bias
   }
   ring_drain();
@@ -157,31 +110,7 @@ __device__ __forceinline__ void bdense_one_pass(W wc, Ring<16384>& ring, char* s
   acc_zero<GeoTt, 128>(acc2);
   conv_segment<GeoTt, 128, 1, 1, true>(ring, smem, acc2);
   if (!active) return;
-  const f32x16 acc[2] = {acc2[0][0], acc2[1][0]};
-  // epilogue: rows = channel (regs), cols = j (lanes), as bdense_passes
-#pragma unroll
-  for (int mt = 0; mt < 2; ++mt) {
-    const int j = jp * 128 + jg * 64 + mt * 32 + lr;
-    if (j >= kNLoc) continue;
-    const float bj = p_bias[j];
-#pragma unroll
-    for (int gp = 0; gp < 2; ++gp) {
-      h4 o[2];
-      {
-        const int g4 = 2 * gp;
-        const int c = half * CH + ct * 32 + g4 * 8 + h * 4;
-        const f32x4 sc0 = scale_log2e(*(const f32x4*)(p_scale + c)), sh0 = scale_log2e(*(const f32x4*)(p_shift + c));
-        const f32x4 sc1 = scale_log2e(*(const f32x4*)(p_scale + c + 8)), sh1 = scale_log2e(*(const f32x4*)(p_shift + c + 8));
-        const f32x4 v0 = {acc[mt][g4 * 4] + bj, acc[mt][g4 * 4 + 1] + bj, acc[mt][g4 * 4 + 2] + bj, acc[mt][g4 * 4 + 3] + bj};
-        const f32x4 v1 = {acc[mt][g4 * 4 + 4] + bj, acc[mt][g4 * 4 + 5] + bj, acc[mt][g4 * 4 + 6] + bj, acc[mt][g4 * 4 + 7] + bj};
-        bn_mish8_l2(v0, v1, sc0, sh0, sc1, sh1, o[0], o[1]);
-      }
-      half_swap32(o[0], o[1]);
-      const h8 piece = {o[0][0], o[0][1], o[0][2], o[0][3], o[1][0], o[1][1], o[1][2], o[1][3]};
-      const int cb = (half * CH + ct * 32) / 8 + 2 * gp + h;   // this lane's channel block
-      *(h8*)(u + ((size_t)pos * (C / 8) + cb) * (kNLoc * 8) + j * 8) = piece;
-    }
-  }
+#include "bdense_epilogue.inc"
 }
 
 }  // namespace
@@ -245,16 +174,7 @@ __global__ void __launch_bounds__(kWG, 2) k_bdense_split(BDenseSplitArgs aa) {
     lds_barrier();
     // ---- transpose-stage t[pos][cblk][loc][8] -> Tt[c][i], as bdense_body ---------------
     if (mine(it)) {
-#pragma unroll
-      for (int i = 0; i < 6; ++i) {
-        const int loc = 2 * (l32 + 32 * i);
-        if (loc >= kNLoc) continue;
-        const h8 v0 = xr.v[2 * i];
-        h8 v1 = xr.v[2 * i + 1];
-        if (loc + 1 >= kNLoc) v1 = h8{0, 0, 0, 0, 0, 0, 0, 0};   // board point 361 is padding (K = 384)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) *(h2*)(smem + (combo * 8 + e) * kTtStride + loc * 2) = h2{v0[e], v1[e]};
-      }
+#include "bdense_transpose.inc"
     }
     pair_load(item_of(idx + stride));
     ring_note_xloads(ring);
@@ -284,17 +204,6 @@ namespace {
 struct HeadsSplitArgs { HeadsArgs a; float* pooled; int parts; };
 constexpr int kHeadsH = 32, kHeadsMaxV = 80;
 static_assert(kHeadsPoolFloats == 4 * kHeadsH, "pooled values of a position: mean and max of g, mean and max of v");
-
-__device__ __forceinline__ float edge_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ float edge_wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
 
 }  // namespace
 
@@ -328,8 +237,8 @@ __global__ void __launch_bounds__(256) k_heads_pool(HeadsSplitArgs aa) {
         m = fmaxf(m, x);
       }
     }
-    s = edge_wave_sum(s);
-    m = edge_wave_max(m);
+    s = wave_sum(s);
+    m = wave_max(m);
     if (lane == 0) {
       dst[ch + e] = s * (1.0f / kNLoc);
       dst[H + ch + e] = m;
@@ -445,11 +354,7 @@ __global__ void __launch_bounds__(256) k_heads_points(HeadsSplitArgs aa) {
     const float gam = misc[2], score_out_b = a.score_out_b[0];
     const int per = (800 + nb - 1) / nb, lo = rb * per, hi = lo + per < 800 ? lo + per : 800;
     for (int sidx = lo + t; sidx < hi; sidx += 256) {
-      const float sv = 0.05f * (float)(sidx - 400) + 0.025f;
-      float s = score_out_b;
-      const int z = launder(0);   // keeps the LDS reads inside the bin loop
-#pragma unroll 8
-      for (int k = 0; k < V; ++k) s += mish_f(base[z + k] + sv * w_sp[z + k]) * w_so[z + k];
+#include "heads_score_bin.inc"
       out[kOffScoreLogits + sidx] = gam * s;
     }
   }
@@ -475,7 +380,7 @@ __global__ void __launch_bounds__(256) k_heads_softmax(HeadsSplitArgs aa) {
       m = fmaxf(m, lg[k]);
     }
   }
-  m = edge_wave_max(m);
+  m = wave_max(m);
   if (lane == 0) red[wid] = m;
   __syncthreads();
   m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
@@ -489,7 +394,7 @@ __global__ void __launch_bounds__(256) k_heads_softmax(HeadsSplitArgs aa) {
       s += lg[k];
     }
   }
-  s = edge_wave_sum(s);
+  s = wave_sum(s);
   if (lane == 0) red[wid] = s;
   __syncthreads();
   const float inv = 1.0f / (red[0] + red[1] + red[2] + red[3]);

@@ -16,17 +16,6 @@ namespace {
 constexpr int kH = 32;          // head channels
 constexpr int kAuxWg = 256;
 
-__device__ __forceinline__ float aux_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ float aux_wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-
 // LDS plan (float offsets), every region a multiple of four floats so that the record is 16-byte aligned
 struct AuxLds {
   int gd_w, oq_embed_w, mcts_w, oq_aux_w, pass_aux_w, soft_pass_w, moves_aux_w, soft_moves_w, gbn_scale, gbn_shift, gd_b,
@@ -112,8 +101,8 @@ __global__ void __launch_bounds__(kAuxWg) k_heads_aux(HeadsAuxArgs a) {
             m = fmaxf(m, x);
           }
         }
-        s = aux_wave_sum(s);
-        m = aux_wave_max(m);
+        s = wave_sum(s);
+        m = wave_max(m);
         if (lane == 0) {
           float* dst = al + (is_g ? L.gp : L.vp);
           dst[ch + e] = s * (1.0f / kNLoc);
@@ -183,9 +172,9 @@ __global__ void __launch_bounds__(kAuxWg) k_heads_aux(HeadsAuxArgs a) {
     if (wid == 0) {
       const bool on = lane < kAuxBins;
       const float l = on ? rec[kAuxOffMctsLogits + lane] : -3.0e38f;
-      const float m = aux_wave_max(l);
+      const float m = wave_max(l);
       const float e = on ? __expf(l - m) : 0.0f;
-      const float sum = aux_wave_sum(e);
+      const float sum = wave_sum(e);
       if (on) rec[kAuxOffMctsProbs + lane] = e * (1.0f / sum);
     }
     __syncthreads();

@@ -441,17 +441,6 @@ __global__ void __launch_bounds__(kWG, 2) k_bdense(BDenseArgs a) {
 // core::Softmax in TrtEngineImpl::GetBatch (cc/nn/engine/trt_engine.cc:347-348) moved on
 // device.  fp32 VALU throughout; one 256-thread workgroup per position.
 // =======================================================================================
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-
 // LDS plan of k_heads (float offsets): every small weight matrix of the heads staged once
 // per workgroup, then one scratch area per 256-thread position group.
 template <int H, int V>
@@ -520,6 +509,8 @@ __global__ void __launch_bounds__(1024) k_heads(HeadsArgs a) {
   const float pass_b0 = a.pass_b[0], opt_pass_b = a.opt_pass_b[0], gamma_out_b = a.gamma_out_b[0],
               score_out_b = a.score_out_b[0];
   float* sc = hl + L::n_weights + g * L::n_scratch;
+  // the score bin's operands (heads_score_bin.inc, shared with k_heads_points of edge_split.hip) under their names there
+  const float* base = sc + L::base, * w_sp = hl + L::score_pre_w + (2 * H) * V, * w_so = hl + L::score_out_w;
   __syncthreads();
 
   for (int pos4 = blockIdx.x * L::kGroups; pos4 < a.npos; pos4 += gridDim.x * L::kGroups) {
@@ -568,55 +559,7 @@ __global__ void __launch_bounds__(1024) k_heads(HeadsArgs a) {
     }
     __syncthreads();
     // ---- small dense layers ----------------------------------------------------------
-    if (t < H) {
-      float s = hl[L::gd_b + t];
-#pragma unroll 8
-      for (int k = 0; k < 2 * H; ++k) s += sc[L::gp + k] * hl[L::gd_w + k * H + t];
-      sc[L::gbias + t] = s;
-    } else if (t >= 64 && t < 64 + V) {
-      const int o = t - 64;
-      float s = hl[L::oq_embed_b + o], gm = hl[L::gamma_pre_b + o], b = hl[L::score_pre_b + o];
-#pragma unroll 8
-      for (int k = 0; k < 2 * H; ++k) {
-        const float x = sc[L::vp + k];
-        s += x * hl[L::oq_embed_w + k * V + o];
-        gm += x * hl[L::gamma_pre_w + k * V + o];
-        b += x * hl[L::score_pre_w + k * V + o];
-      }
-      sc[L::emb + o] = mish_f(s);
-      sc[L::gpre + o] = mish_f(gm);
-      sc[L::base + o] = b;
-    } else if (t == 192) {
-      float s0 = pass_b0, so = opt_pass_b;
-#pragma unroll 8
-      for (int k = 0; k < 2 * H; ++k) {
-        s0 += sc[L::gp + k] * hl[L::pass_w + k * 2];
-        so += sc[L::gp + k] * hl[L::opt_pass_w + k];
-      }
-      sc[L::pi + 361] = s0 - 3.0f;
-      sc[L::opt + 361] = so - 3.0f;
-    }
-    __syncthreads();
-    if (t < 14) {
-      float s = hl[L::oq_out_b + t];
-#pragma unroll 8
-      for (int k = 0; k < V; ++k) s += sc[L::emb + k] * hl[L::oq_out_w + k * 14 + t];
-      if (t < 2) sc[L::misc + t] = s;
-      if (live) {
-        if (t < 2) out[kOffOutcomeLogits + t] = s;
-        if (t == 5) {
-          out[kOffErr2] = 4.0f / (1.0f + __expf(-s));
-          if (res) res[kOffErr2] = out[kOffErr2];
-        }
-      }
-    } else if (t == 64) {
-      float s = gamma_out_b;
-#pragma unroll 8
-      for (int k = 0; k < V; ++k) s += sc[L::gpre + k] * hl[L::gamma_out_w + k];
-      if (live) out[kOffGamma] = s;
-      const float sp = s > 20.0f ? s : log1pf(__expf(s));
-      sc[L::misc + 2] = fminf(sp, 10.0f);
-    }
+#include "heads_dense_phase.inc"
     // ---- per-location policy logits and ownership (needs gbias only) ------------------
     for (int i = t; i < kNLoc; i += 256) {
       float pi = 0.0f, po = 0.0f, ow = 0.0f;
@@ -651,94 +594,13 @@ __global__ void __launch_bounds__(1024) k_heads(HeadsArgs a) {
     {
       const float gam = sc[L::misc + 2];
       for (int sidx = t; sidx < 800; sidx += 256) {
-        const float sv = 0.05f * (float)(sidx - 400) + 0.025f;
-        float s = score_out_b;
-        const int z = launder(0);   // keeps the LDS reads inside the bin loop
-#pragma unroll 8
-        for (int k = 0; k < V; ++k)
-          s += mish_f(sc[L::base + z + k] + sv * hl[L::score_pre_w + (2 * H) * V + z + k]) * hl[L::score_out_w + z + k];
+#include "heads_score_bin.inc"
         sc[L::logits + sidx] = gam * s;
       }
     }
     __syncthreads();
-    // ---- raw logits out + the three softmaxes, reductions fused ------------------------
-    float m3[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
-    for (int i = t; i < 362; i += 256) {
-      const float p = sc[L::pi + i], o = sc[L::opt + i];
-      if (live) {
-        out[kOffMoveLogits + i] = p;
-        out[kOffOptLogits + i] = o;
-        if (res) res[kOffMoveLogits + i] = p;
-      }
-      m3[0] = fmaxf(m3[0], p);
-      m3[1] = fmaxf(m3[1], o);
-    }
-    for (int i = t; i < 800; i += 256) {
-      const float l = sc[L::logits + i];
-      if (live) out[kOffScoreLogits + i] = l;
-      m3[2] = fmaxf(m3[2], l);
-    }
-#pragma unroll
-    for (int r = 0; r < 3; ++r) m3[r] = wave_max(m3[r]);
-    if (lane == 0) {
-#pragma unroll
-      for (int r = 0; r < 3; ++r) sc[L::red + r * 4 + wid] = m3[r];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-      m3[r] = fmaxf(fmaxf(sc[L::red + r * 4], sc[L::red + r * 4 + 1]),
-                    fmaxf(sc[L::red + r * 4 + 2], sc[L::red + r * 4 + 3]));
-    __syncthreads();   // red is rewritten below
-    float s3[3] = {0.0f, 0.0f, 0.0f};
-    for (int i = t; i < 362; i += 256) {
-      const float e0 = __expf(sc[L::pi + i] - m3[0]), e1 = __expf(sc[L::opt + i] - m3[1]);
-      sc[L::pi + i] = e0;
-      sc[L::opt + i] = e1;
-      s3[0] += e0;
-      s3[1] += e1;
-    }
-    for (int i = t; i < 800; i += 256) {
-      const float e = __expf(sc[L::logits + i] - m3[2]);
-      sc[L::logits + i] = e;
-      s3[2] += e;
-    }
-#pragma unroll
-    for (int r = 0; r < 3; ++r) s3[r] = wave_sum(s3[r]);
-    if (lane == 0) {
-#pragma unroll
-      for (int r = 0; r < 3; ++r) sc[L::red + r * 4 + wid] = s3[r];
-    }
-    __syncthreads();
-    if (live) {
-      const float i0 = 1.0f / (sc[L::red + 0] + sc[L::red + 1] + sc[L::red + 2] + sc[L::red + 3]);
-      const float i1 = 1.0f / (sc[L::red + 4] + sc[L::red + 5] + sc[L::red + 6] + sc[L::red + 7]);
-      const float i2 = 1.0f / (sc[L::red + 8] + sc[L::red + 9] + sc[L::red + 10] + sc[L::red + 11]);
-      for (int i = t; i < 362; i += 256) {
-        out[kOffMoveProbs + i] = sc[L::pi + i] * i0;
-        out[kOffOptProbs + i] = sc[L::opt + i] * i1;
-        if (res) {
-          res[kOffMoveProbs + i] = sc[L::pi + i] * i0;
-          res[kOffOptProbs + i] = sc[L::opt + i] * i1;
-        }
-      }
-      for (int i = t; i < 800; i += 256) {
-        out[kOffScoreProbs + i] = sc[L::logits + i] * i2;
-        if (res) res[kOffScoreProbs + i] = sc[L::logits + i] * i2;
-      }
-      if (t == 0) {
-        const float v0 = sc[L::misc], v1 = sc[L::misc + 1];
-        const float m = fmaxf(v0, v1);
-        const float e0 = __expf(v0 - m), e1 = __expf(v1 - m);
-        out[kOffValueProbs] = e0 / (e0 + e1);
-        out[kOffValueProbs + 1] = e1 / (e0 + e1);
-        if (res) {
-          res[kOffValueProbs] = e0 / (e0 + e1);
-          res[kOffValueProbs + 1] = e1 / (e0 + e1);
-        }
-      }
-    }
-    __syncthreads();
+    // ---- raw logits out + the three softmaxes, reductions fused; the value softmax -----
+#include "heads_softmax_phase.inc"
   }
 }
 
@@ -899,56 +761,8 @@ __global__ void __launch_bounds__(512, 2) k_headsx(HeadsArgs a) {
       else dst[H + ch] = fmaxf(fmaxf(p0, p1), fmaxf(p2, p3));
     }
     __syncthreads();
-    // ---- small dense layers (k_heads) ------------------------------------------------
-    if (t < H) {
-      float s_ = hl[L::gd_b + t];
-#pragma unroll 8
-      for (int k = 0; k < 2 * H; ++k) s_ += sc[L::gp + k] * hl[L::gd_w + k * H + t];
-      sc[L::gbias + t] = s_;
-    } else if (t >= 64 && t < 64 + V) {
-      const int o = t - 64;
-      float s_ = hl[L::oq_embed_b + o], gmm = hl[L::gamma_pre_b + o], b = hl[L::score_pre_b + o];
-#pragma unroll 8
-      for (int k = 0; k < 2 * H; ++k) {
-        const float x = sc[L::vp + k];
-        s_ += x * hl[L::oq_embed_w + k * V + o];
-        gmm += x * hl[L::gamma_pre_w + k * V + o];
-        b += x * hl[L::score_pre_w + k * V + o];
-      }
-      sc[L::emb + o] = mish_f(s_);
-      sc[L::gpre + o] = mish_f(gmm);
-      sc[L::base + o] = b;
-    } else if (t == 192) {
-      float s0 = pass_b0, so = opt_pass_b;
-#pragma unroll 8
-      for (int k = 0; k < 2 * H; ++k) {
-        s0 += sc[L::gp + k] * hl[L::pass_w + k * 2];
-        so += sc[L::gp + k] * hl[L::opt_pass_w + k];
-      }
-      sc[L::pi + 361] = s0 - 3.0f;
-      sc[L::opt + 361] = so - 3.0f;
-    }
-    __syncthreads();
-    if (t < 14) {
-      float s_ = hl[L::oq_out_b + t];
-#pragma unroll 8
-      for (int k = 0; k < V; ++k) s_ += sc[L::emb + k] * hl[L::oq_out_w + k * 14 + t];
-      if (t < 2) sc[L::misc + t] = s_;
-      if (live) {
-        if (t < 2) out[kOffOutcomeLogits + t] = s_;
-        if (t == 5) {
-          out[kOffErr2] = 4.0f / (1.0f + __expf(-s_));
-          if (res) res[kOffErr2] = out[kOffErr2];
-        }
-      }
-    } else if (t == 64) {
-      float s_ = gamma_out_b;
-#pragma unroll 8
-      for (int k = 0; k < V; ++k) s_ += sc[L::gpre + k] * hl[L::gamma_out_w + k];
-      if (live) out[kOffGamma] = s_;
-      const float sp = s_ > 20.0f ? s_ : log1pf(__expf(s_));
-      sc[L::misc + 2] = fminf(sp, 10.0f);
-    }
+    // ---- small dense layers ----------------------------------------------------------
+#include "heads_dense_phase.inc"
     // ---- policy logits from the p channels kept in registers (needs gbias only) ------------
     {
       float gb[2][4], mw[2][4], omw[2][4];
@@ -1006,84 +820,8 @@ __global__ void __launch_bounds__(512, 2) k_headsx(HeadsArgs a) {
       }
     }
     __syncthreads();
-    // ---- raw logits out + the three softmaxes, reductions fused ------------------------
-    float m3[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
-    for (int i = t; i < 362; i += 256) {
-      const float p = sc[L::pi + i], o = sc[L::opt + i];
-      if (live) {
-        out[kOffMoveLogits + i] = p;
-        out[kOffOptLogits + i] = o;
-        if (res) res[kOffMoveLogits + i] = p;
-      }
-      m3[0] = fmaxf(m3[0], p);
-      m3[1] = fmaxf(m3[1], o);
-    }
-    for (int i = t; i < 800; i += 256) {
-      const float l = sc[L::logits + i];
-      if (live) out[kOffScoreLogits + i] = l;
-      m3[2] = fmaxf(m3[2], l);
-    }
-#pragma unroll
-    for (int r = 0; r < 3; ++r) m3[r] = wave_max(m3[r]);
-    if (lane == 0) {
-#pragma unroll
-      for (int r = 0; r < 3; ++r) sc[L::red + r * 4 + wid] = m3[r];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-      m3[r] = fmaxf(fmaxf(sc[L::red + r * 4], sc[L::red + r * 4 + 1]),
-                    fmaxf(sc[L::red + r * 4 + 2], sc[L::red + r * 4 + 3]));
-    __syncthreads();   // red is rewritten below
-    float s3[3] = {0.0f, 0.0f, 0.0f};
-    for (int i = t; i < 362; i += 256) {
-      const float e0 = __expf(sc[L::pi + i] - m3[0]), e1 = __expf(sc[L::opt + i] - m3[1]);
-      sc[L::pi + i] = e0;
-      sc[L::opt + i] = e1;
-      s3[0] += e0;
-      s3[1] += e1;
-    }
-    for (int i = t; i < 800; i += 256) {
-      const float e = __expf(sc[L::logits + i] - m3[2]);
-      sc[L::logits + i] = e;
-      s3[2] += e;
-    }
-#pragma unroll
-    for (int r = 0; r < 3; ++r) s3[r] = wave_sum(s3[r]);
-    if (lane == 0) {
-#pragma unroll
-      for (int r = 0; r < 3; ++r) sc[L::red + r * 4 + wid] = s3[r];
-    }
-    __syncthreads();
-    if (live) {
-      const float i0 = 1.0f / (sc[L::red + 0] + sc[L::red + 1] + sc[L::red + 2] + sc[L::red + 3]);
-      const float i1 = 1.0f / (sc[L::red + 4] + sc[L::red + 5] + sc[L::red + 6] + sc[L::red + 7]);
-      const float i2 = 1.0f / (sc[L::red + 8] + sc[L::red + 9] + sc[L::red + 10] + sc[L::red + 11]);
-      for (int i = t; i < 362; i += 256) {
-        out[kOffMoveProbs + i] = sc[L::pi + i] * i0;
-        out[kOffOptProbs + i] = sc[L::opt + i] * i1;
-        if (res) {
-          res[kOffMoveProbs + i] = sc[L::pi + i] * i0;
-          res[kOffOptProbs + i] = sc[L::opt + i] * i1;
-        }
-      }
-      for (int i = t; i < 800; i += 256) {
-        out[kOffScoreProbs + i] = sc[L::logits + i] * i2;
-        if (res) res[kOffScoreProbs + i] = sc[L::logits + i] * i2;
-      }
-      if (t == 0) {
-        const float v0 = sc[L::misc], v1 = sc[L::misc + 1];
-        const float m = fmaxf(v0, v1);
-        const float e0 = __expf(v0 - m), e1 = __expf(v1 - m);
-        out[kOffValueProbs] = e0 / (e0 + e1);
-        out[kOffValueProbs + 1] = e1 / (e0 + e1);
-        if (res) {
-          res[kOffValueProbs] = e0 / (e0 + e1);
-          res[kOffValueProbs + 1] = e1 / (e0 + e1);
-        }
-      }
-    }
-    __syncthreads();
+    // ---- raw logits out + the three softmaxes, reductions fused; the value softmax -----
+#include "heads_softmax_phase.inc"
   }
 }
 

@@ -9,6 +9,12 @@
 // same order, so their results are equal bit for bit (tests/test_conv_widths_gpu.py compares).  Where the two forms
 // differ on purpose the body says so under `if constexpr (W::fixed)`.
 //
+// Four passages of init_body, bdense_body and bdense_passes are also the split kernels' (edge_split.hip: one output pass
+// per workgroup) and are written once as text that both include in place: stem_planes.inc, stem_epilogue.inc,
+// bdense_transpose.inc, bdense_epilogue.inc; each names at its head what must be in scope.  Text, not functions, so that
+// the bodies reach the compiler token for token as before; bdense_passes is inlined into k_block's
+// fused tail, whose register allocation tests/test_kernel_resources_cpu.py guards.
+//
 // Layouts, ring and tiling: conv_core.h.  Activation offsets are 64-bit per position (stage_load, residual_addr), the
 // 32-bit lane offsets stay inside one workgroup's positions.
 #pragma once
@@ -70,34 +76,8 @@ __device__ __forceinline__ void bdense_passes(W wc, Ring<16384>& ring, char* sme
     acc_zero<GeoTt, 128>(acc2);
     conv_segment<GeoTt, 128, 1, 1, true>(ring, smem, acc2);
     if (!ct_active) continue;
-    const f32x16 acc[2] = {acc2[0][0], acc2[1][0]};
     // epilogue: rows = channel (regs), cols = j (lanes)
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-      const int j = jp * 128 + jg * 64 + mt * 32 + lr;
-      if (j >= kNLoc) continue;
-      const float bj = p_bias[j];
-      // channel blocks g4 = 2*gp and 2*gp + 1: each lane's quad is one 8-byte half of a
-      // block's piece; after the swap lanes 0-31 hold the whole piece of block 2*gp, lanes
-      // 32-63 that of block 2*gp + 1 (see epilogue_store in conv_core.h)
-#pragma unroll
-      for (int gp = 0; gp < 2; ++gp) {
-        h4 o[2];
-        {
-          const int g4 = 2 * gp;
-          const int c = half * CH + ct * 32 + g4 * 8 + h * 4;
-          const f32x4 sc0 = scale_log2e(*(const f32x4*)(p_scale + c)), sh0 = scale_log2e(*(const f32x4*)(p_shift + c));
-          const f32x4 sc1 = scale_log2e(*(const f32x4*)(p_scale + c + 8)), sh1 = scale_log2e(*(const f32x4*)(p_shift + c + 8));
-          const f32x4 v0 = {acc[mt][g4 * 4] + bj, acc[mt][g4 * 4 + 1] + bj, acc[mt][g4 * 4 + 2] + bj, acc[mt][g4 * 4 + 3] + bj};
-          const f32x4 v1 = {acc[mt][g4 * 4 + 4] + bj, acc[mt][g4 * 4 + 5] + bj, acc[mt][g4 * 4 + 6] + bj, acc[mt][g4 * 4 + 7] + bj};
-          bn_mish8_l2(v0, v1, sc0, sh0, sc1, sh1, o[0], o[1]);
-        }
-        half_swap32(o[0], o[1]);
-        const h8 piece = {o[0][0], o[0][1], o[0][2], o[0][3], o[1][0], o[1][1], o[1][2], o[1][3]};
-        const int cb = (half * CH + ct * 32) / 8 + 2 * gp + h;   // this lane's channel block
-        *(h8*)(u + ((size_t)pos * (C / 8) + cb) * (kNLoc * 8) + j * 8) = piece;
-      }
-    }
+#include "bdense_epilogue.inc"
   }
 }
 
@@ -134,42 +114,8 @@ __device__ __forceinline__ void init_body(InitArgs a, W wc) {
   const int lr = lane & 31, h = lane >> 5;
 
   for (int pos = blockIdx.x; pos < a.npos; pos += gridDim.x) {
-    const unsigned char* f = (const unsigned char*)a.feats + (size_t)pos * FeatOff::size;
-    const int color = (signed char)f[FeatOff::color];
-    // ---- planes -> LDS (one thread per board point) ---------------------------------
-    for (int loc = threadIdx.x; loc < kNLoc; loc += kWG) {
-      h8 lo = {0, 0, 0, 0, 0, 0, 0, 0}, hi = {0, 0, 0, 0, 0, 0, 0, 0};
-      auto our = [&](int off) {
-        return (_Float16)((signed char)f[off + loc] == color ? 1.0f : 0.0f);
-      };
-      auto opp = [&](int off) {
-        return (_Float16)((signed char)f[off + loc] == -color ? 1.0f : 0.0f);
-      };
-      lo[0] = our(FeatOff::board); lo[1] = opp(FeatOff::board);
-      lo[7] = our(FeatOff::atari); hi[0] = opp(FeatOff::atari);
-      hi[1] = our(FeatOff::two); hi[2] = opp(FeatOff::two);
-      hi[3] = our(FeatOff::three); hi[4] = opp(FeatOff::three);
-      hi[5] = our(FeatOff::ladder); hi[6] = opp(FeatOff::ladder);
-      const int y = (loc * 3450) >> 16, xx = loc - y * kBL;
-#pragma unroll
-      for (int m = 0; m < 5; ++m) {
-        const int* lm = (const int*)(f + FeatOff::last + m * 8);
-        if (lm[0] == y && lm[1] == xx) lo[2 + m] = (_Float16)1.0f;  // pass {19,0}/noop never match
-      }
-      const int s = G::PADTOP + y * G::S + xx;
-      *(h8*)(smem + s * G::SLOTB) = lo;
-      *(h8*)(smem + s * G::SLOTB + 16) = hi;
-    }
-    // ---- game-state scalars (LoadFeatures) ------------------------------------------
-    float gsv[8];
-    gsv[0] = color == 1 ? 1.0f : 0.0f;
-    gsv[1] = color == 1 ? 0.0f : 1.0f;
-#pragma unroll
-    for (int m = 0; m < 5; ++m) {
-      const int* lm = (const int*)(f + FeatOff::last + m * 8);
-      gsv[2 + m] = (lm[0] == 19 && lm[1] == 0) ? 1.0f : 0.0f;
-    }
-    gsv[7] = (color == 1 ? -1.0f : 1.0f) * (*(const float*)(f + FeatOff::komi)) / 15.0f;
+    // ---- feature planes -> LDS, game-state scalars -> gsv[8] ----------------------------
+#include "stem_planes.inc"
 
     // game-state dense once per position: thread c computes (gs . Wg + b)[c] into LDS (the
     // area behind the weight ring, one float per channel: C <= kWG); the first ring acquire of
@@ -192,25 +138,8 @@ __device__ __forceinline__ void init_body(InitArgs a, W wc) {
       acc_zero<G, CP>(acc);
       conv_segment<G, CP, 5, 28>(ring, smem, acc);
       // epilogue: + (gs . Wg + b)[c]  -> x
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-          const int c = cp * CP + acc_chan<G, CP>(mt, g4);
-          const f32x4 bias = *(const f32x4*)(bias_lds + c);
-#pragma unroll
-          for (int j = 0; j < T::NT; ++j) {
-            const int t = lg + j * T::LG;
-            if (t >= G::NT_TOTAL) continue;
-            const int r = t * 32 + lr;
-            int loc;
-            if (!row_valid<G::S>(r, loc)) continue;
-            h4 o;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) o[i] = (_Float16)(acc[mt][j][g4 * 4 + i] + bias[i]);
-            *(h4*)(a.x + ((size_t)pos * (C / 8) + (c >> 3)) * (kNLoc * 8) + loc * 8 + h * 4) = o;
-          }
-        }
+      const int bias_cp = cp;
+#include "stem_epilogue.inc"
     }
     lds_barrier();
     // clear the 5 last-move/stone planes for the next position: every valid slot is
@@ -489,16 +418,7 @@ __device__ __forceinline__ void bdense_body(BDenseArgs a, W wc) {
       {
         const int combo = threadIdx.x >> 5, l32 = threadIdx.x & 31;   // combo = channel block of this pass
         if (combo * 8 < nch) {
-#pragma unroll
-          for (int i = 0; i < 6; ++i) {
-            const int loc = 2 * (l32 + 32 * i);
-            if (loc >= kNLoc) continue;
-            const h8 v0 = xr.v[2 * i];
-            h8 v1 = xr.v[2 * i + 1];
-            if (loc + 1 >= kNLoc) v1 = h8{0, 0, 0, 0, 0, 0, 0, 0};   // board point 361 is padding (K = 384)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) *(h2*)(smem + (combo * 8 + e) * kTtStride + loc * 2) = h2{v0[e], v1[e]};
-          }
+#include "bdense_transpose.inc"
         }
       }
       {

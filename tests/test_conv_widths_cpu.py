@@ -278,7 +278,8 @@ def _assembly():
     if shutil.which("hipcc") is None:
         pytest.skip("no hipcc")
     h = hashlib.sha256()
-    for f in ("conv_any.hip", "conv_any.h", "kernels.h", "conv_core.h", "layer_kernels.h", "launch_util.h"):
+    for f in ("conv_any.hip", "conv_any.h", "kernels.h", "conv_core.h", "layer_kernels.h", "launch_util.h",
+              "stem_planes.inc", "stem_epilogue.inc", "bdense_epilogue.inc", "bdense_transpose.inc"):
         h.update(open(os.path.join(CSRC, f), "rb").read())
     out = os.path.join(ROOT, "build", "conv_any_gfx950_%s.s" % h.hexdigest()[:16])
     if not os.path.exists(out):

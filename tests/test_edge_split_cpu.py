@@ -162,7 +162,8 @@ def _assembly():
     if shutil.which("hipcc") is None:
         pytest.skip("no hipcc")
     h = hashlib.sha256()
-    for f in ("edge_split.hip", "edge_split.h", "layer_kernels.h", "conv_core.h", "kernels.h", "launch_util.h"):
+    for f in ("edge_split.hip", "edge_split.h", "layer_kernels.h", "conv_core.h", "kernels.h", "launch_util.h",
+              "stem_planes.inc", "stem_epilogue.inc", "bdense_epilogue.inc", "bdense_transpose.inc", "heads_score_bin.inc"):
         h.update(open(os.path.join(CSRC, f), "rb").read())
     out = os.path.join(ROOT, "build", "edge_split_gfx950_%s.s" % h.hexdigest()[:16])
     if not os.path.exists(out):

@@ -20,7 +20,9 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "p3achygo_amd", "csrc")
-SOURCES = ["kernels.hip", "kernels.h", "conv_core.h", "conv16.h", "layer_kernels.h", "launch_util.h"]
+SOURCES = ["kernels.hip", "kernels.h", "conv_core.h", "conv16.h", "layer_kernels.h", "launch_util.h",
+           "stem_planes.inc", "stem_epilogue.inc", "bdense_epilogue.inc", "bdense_transpose.inc",
+           "heads_dense_phase.inc", "heads_softmax_phase.inc", "heads_score_bin.inc"]
 HEAD_MFMAS = 384          # the fused conv_last: four segments of 4 k32 steps x 24 MFMAs
 
 
