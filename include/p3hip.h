@@ -140,6 +140,23 @@ typedef struct p3hip_engine p3hip_engine;
                                        orientation the slot was loaded in.  Needs 8 x batch_size <= 65536.  See
                                        p3hip_set_symmetries below */
 
+#define P3HIP_FLAG_SYMMETRY_SLOT 16384u /* every slot carries its own symmetry mask (p3hip_set_slot_symmetries below; 0x01
+                                       after every load): a run evaluates the copies of all its slots packed densely, one
+                                       forward row per set bit, and returns every slot's result rotated back into the
+                                       orientation it was loaded in and averaged, by the rule of P3HIP_FLAG_SYMMETRY_AVG.
+                                       A search hands its leaves' one random symmetry to the engine in place of rotating
+                                       features and results on the host, and evaluates a root under all eight in the same
+                                       run: one root at 0xFF and 1023 leaves are 1031 forward rows.  The per-row buffers
+                                       hold the symmetry_rows of p3hip_create_rows.  p3hip_create returns NULL together
+                                       with P3HIP_FLAG_SYMMETRY_AVG, and together with P3HIP_FLAG_AUX for the reason given
+                                       there; every other flag, the NN cache, p3hip_score and p3hip_loss's refusal without
+                                       P3HIP_FLAG_AUX compose as with P3HIP_FLAG_SYMMETRY_AVG.  With
+                                       P3HIP_FLAG_LAUNCH_GRAPH a run over the full static batch whose slots all have one
+                                       symmetry (whichever) replays the graph; a run with an averaged slot goes out kernel by
+                                       kernel.  Not built: the aux record, a graph for runs with averaged slots, and on the
+                                       host side root masks in self-play (the eval hosts have them: player keys
+                                       nn_device_symmetry and nn_root_symmetry_mask) */
+
 #define P3HIP_FLAG_FP32 256u        /* full-precision inference of the conv trunks: every trunk of P3HIP_CONV_SET runs layer by
                                        layer in fp32 from the stem to the heads (csrc/conv_f32.hip).
                                        Weights are packed as fp32, the three head convs included, activations are stored as
@@ -245,6 +262,12 @@ typedef struct p3hip_engine p3hip_engine;
  * Returns NULL on failure; p3hip_create_error() then holds the reason. */
 p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version,
                            int device_ordinal, uint32_t flags);
+/* p3hip_create with the row capacity of a P3HIP_FLAG_SYMMETRY_SLOT engine: symmetry_rows is the number R of forward rows
+ * (copies) one run may evaluate, the size of the per-row device buffers.  0 means 8 x batch_size, which always
+ * suffices; otherwise batch_size <= R <= 8 x batch_size.  NULL for a non-zero R without the flag and for R above 65536.
+ * p3hip_create(...) is p3hip_create_rows(..., 0). */
+p3hip_engine* p3hip_create_rows(const char* weights_path, int batch_size, int version, int device_ordinal,
+                                uint32_t flags, int symmetry_rows);
 const char* p3hip_create_error(void);
 void p3hip_destroy(p3hip_engine* e);
 
@@ -321,6 +344,32 @@ int p3hip_int8_set_scales(p3hip_engine* e, const float* scales, int n);
  *   p3hip_symmetry_maps   the forward and inverse index maps of the 19 x 19 board the kernels use.  Needs no device. */
 int p3hip_set_symmetries(p3hip_engine* e, uint32_t mask);
 void p3hip_symmetry_maps(uint16_t fwd[8][361], uint16_t inv[8][361]);
+
+/* ---- a symmetry set per slot (P3HIP_FLAG_SYMMETRY_SLOT) -------------------------------------------------------
+ * The rule above with a mask per slot.  The copies of the r-th slot of a run (dense, in slot order) occupy the forward
+ * rows first[r] .. first[r] + k_r - 1 in ascending symmetry index, first[r] the sum of the popcounts k of the slots in
+ * front of it.  Copy j is the slot under symmetry s_j as above; after the forward pass its board-indexed outputs are
+ * rotated back, and every float is acc = v_0; acc += v_1; ...; acc / (float)k_r in fp32.  With k_r = 1 the result is
+ * that copy rotated back, bit for bit (x / 1.0f is exact): what FillFeatures under s, a plain engine and
+ * UnapplySymmetry return.
+ *   p3hip_set_slot_symmetries  bit s of mask selects symmetry s.  Sets the mask of the position last loaded into `slot`:
+ *                              call it after the load and before the run, from the thread that loaded the slot (the
+ *                              threading of p3hip_load_slot).  Every p3hip_load_slot / p3hip_load_slot_keyed resets the
+ *                              slot's mask to 0x01, and a slot never loaded has 0x01 (P3HIP_FLAG_RUN_ALL_SLOTS).  The
+ *                              features are loaded in the caller's own orientation; p3hip_get_slot,
+ *                              p3hip_get_slot_keyed, p3hip_get_ownership and p3hip_get_raw answer in that orientation.
+ *                              The NN cache stores that result with the symmetry given to p3hip_load_slot_keyed.
+ *                              Returns 1 (message naming the flag) on an engine created without the flag, 1 for a bad
+ *                              slot and for a mask of 0 or above 255.  p3hip_set_symmetries fails on such an engine.
+ *   p3hip_run                  (p3hip_int8_calibrate, p3hip_upload) returns 1 before anything is launched when the
+ *                              masks of its slots add up to more than symmetry_rows copies; the message states the
+ *                              sum and the capacity.  No slot has a result then (p3hip_get_slot answers 2) and all of
+ *                              them stay pending: lower masks and run again.
+ *   p3hip_debug_symmetry_rows  the table the engine uploads for n dense slots with these masks, by the function the
+ *                              engine itself calls: first[r], and *total = the sum of the popcounts.  Returns 1 for
+ *                              n < 1, any mask of 0, and a total above `rows`.  Needs no device. */
+int p3hip_set_slot_symmetries(p3hip_engine* e, int slot, uint32_t mask);
+int p3hip_debug_symmetry_rows(const uint8_t* masks, int n, int rows, int* first, int* total);
 
 /* ---- the model's other fifteen outputs (P3HIP_FLAG_AUX) -------------------------------------------------------
  * The network has 25 named outputs (python/model.py:1269-1295, exported by python/scripts/convert_to_onnx.py:462-488 as

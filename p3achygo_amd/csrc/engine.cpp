@@ -38,7 +38,7 @@ namespace {
 thread_local std::string g_create_error;
 
 // where p3hip_run / p3hip_upload put the slots' records: the forward pass's input, or the expand's
-unsigned char* upload_buffer(p3hip_engine* e) { return e->sym ? e->d_sfeats : e->d_feats; }
+unsigned char* upload_buffer(p3hip_engine* e) { return e->any_sym() ? e->d_sfeats : e->d_feats; }
 
 // H2D of the `n` records gather_loaded put in the dense upload
 bool upload(p3hip_engine* e, int n) {
@@ -88,10 +88,46 @@ int p3hip_graph_state(const p3hip_engine* e) { return e->graph_failed ? -1 : (e-
 
 p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version,
                            int device_ordinal, uint32_t flags) {
+  return p3hip_create_rows(weights_path, batch_size, version, device_ordinal, flags, 0);
+}
+
+p3hip_engine* p3hip_create_rows(const char* weights_path, int batch_size, int version,
+                                int device_ordinal, uint32_t flags, int symmetry_rows) {
   g_create_error.clear();
   if (version != 1) { g_create_error = "only model version 1 (15 planes + 8 scalars) is supported"; return nullptr; }
   if (batch_size < 1 || batch_size > (1 << 16)) { g_create_error = "bad batch size"; return nullptr; }
   const bool sym = (flags & P3HIP_FLAG_SYMMETRY_AVG) != 0;
+  const bool sym_slot = (flags & P3HIP_FLAG_SYMMETRY_SLOT) != 0;
+  if (sym_slot && sym) {
+    g_create_error = "P3HIP_FLAG_SYMMETRY_SLOT cannot be combined with P3HIP_FLAG_SYMMETRY_AVG: a slot's symmetries come "
+                     "either from the engine's mask or from its own";
+    return nullptr;
+  }
+  if (sym_slot && (flags & P3HIP_FLAG_AUX)) {
+    g_create_error = "P3HIP_FLAG_AUX cannot be combined with P3HIP_FLAG_SYMMETRY_SLOT: the aux record holds tanh, absolute "
+                     "value and softmax outputs, and their average over symmetries is nothing the reference defines";
+    return nullptr;
+  }
+  if (!sym_slot && symmetry_rows != 0) {
+    g_create_error = "symmetry_rows " + std::to_string(symmetry_rows) + " given without P3HIP_FLAG_SYMMETRY_SLOT: only such "
+                     "an engine has a row capacity of its own";
+    return nullptr;
+  }
+  if (sym_slot) {
+    const long full = (long)p3::kNumSyms * batch_size;
+    const long want = symmetry_rows == 0 ? full : (long)symmetry_rows;   // 0: every slot under all eight
+    if (want < batch_size || want > full) {
+      g_create_error = "P3HIP_FLAG_SYMMETRY_SLOT: symmetry_rows " + std::to_string(want) + " is outside batch size " +
+                       std::to_string(batch_size) + " .. 8 x batch size " + std::to_string(full);
+      return nullptr;
+    }
+    if (want > (1 << 16)) {
+      g_create_error = "P3HIP_FLAG_SYMMETRY_SLOT: symmetry_rows " + std::to_string(want) +
+                       " exceeds the engine's row limit of 65536 (symmetry_rows 0 means 8 x batch size)";
+      return nullptr;
+    }
+    symmetry_rows = (int)want;
+  }
   if (sym && (size_t)p3::kNumSyms * batch_size > (1u << 16)) {
     g_create_error = "P3HIP_FLAG_SYMMETRY_AVG evaluates 8 copies of every slot: 8 x batch size " +
                      std::to_string(batch_size) + " exceeds the engine's row limit of 65536 (batch size at most 8192)";
@@ -109,7 +145,8 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
   e->flags = flags;
   e->opt = Options::from_env();
   e->sym = sym;
-  e->rows = sym ? p3::kNumSyms * batch_size : batch_size;
+  e->sym_slot = sym_slot;
+  e->rows = sym ? p3::kNumSyms * batch_size : sym_slot ? symmetry_rows : batch_size;
   auto fail = [&](const std::string& m) {
     g_create_error = m;
     p3hip_destroy(e);
@@ -130,7 +167,9 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
   e->n_cu = prop.multiProcessorCount;
   const int C = e->wf.C;
   const size_t B = batch_size;
-  const size_t R = e->rows;   // the per-row device buffers: 8 x batch copies with P3HIP_FLAG_SYMMETRY_AVG
+  // the per-row device buffers: 8 x batch copies with P3HIP_FLAG_SYMMETRY_AVG, symmetry_rows with P3HIP_FLAG_SYMMETRY_SLOT
+  const size_t R = e->rows;
+  const bool copies = sym || sym_slot;
   // t holds a C-channel tensor (broadcast blocks, classic blocks, the transformer's o) or, in a layer-wise btl / nbt block,
   // two C_b-channel ones side by side (enqueue_forward, regions 1 and 2): 2 C_b > C where C_b > C / 2 (P3HIP_CONV_SET
   // allows C_b up to C, and padding C_b to a multiple of 64 can pass C / 2 as well)
@@ -159,8 +198,11 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
             ((path != Path::Split && path != Path::TfmSplit) ||
              e->check(hipMalloc((void**)&e->d_pool, R * p3::kHeadsPoolFloats * 4), "hipMalloc pooled")) &&
             e->check(hipMalloc((void**)&e->d_out, B * p3::kOutStride * 4), "hipMalloc out") &&
-            (!sym || (e->check(hipMalloc((void**)&e->d_sfeats, B * kFeatBytes), "hipMalloc symmetry upload") &&
-                      e->check(hipMalloc((void**)&e->d_cout, R * p3::kOutStride * 4), "hipMalloc copy rows"))) &&
+            (!copies || (e->check(hipMalloc((void**)&e->d_sfeats, B * kFeatBytes), "hipMalloc symmetry upload") &&
+                         e->check(hipMalloc((void**)&e->d_cout, R * p3::kOutStride * 4), "hipMalloc copy rows"))) &&
+            (!sym_slot || (e->check(hipMalloc((void**)&e->d_symtab, B * 5), "hipMalloc symmetry table") &&
+                           e->check(hipHostMalloc((void**)&e->h_symtab, B * 5, hipHostMallocDefault), "hipHostMalloc") &&
+                           e->check(hipMemsetAsync(e->d_symtab, 0, B * 5, e->stream), "hipMemset symmetry table"))) &&
             (!(flags & P3HIP_FLAG_AUX) || (e->check(hipMalloc((void**)&e->d_aux, R * p3::kAuxStride * 4), "hipMalloc aux") &&
                                            e->check(hipMemsetAsync(e->d_aux, 0, R * p3::kAuxStride * 4, e->stream), "hipMemset aux"))) &&
             (!is_int8(path) || (e->check(hipMalloc((void**)&e->d_amax, (size_t)e->plan.n_q * 4), "hipMalloc amax") &&
@@ -171,8 +213,8 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
   e->h_scale.assign(e->plan.n_q, 0.0f);
   memset(e->h_feats, 0, B * kFeatBytes);
   if (!e->check(hipMemsetAsync(e->d_feats, 0, R * kFeatBytes, e->stream), "hipMemset feats") ||
-      (sym && !e->check(hipMemsetAsync(e->d_sfeats, 0, B * kFeatBytes, e->stream), "hipMemset symmetry upload")) ||
-      (sym && !e->check(hipMemsetAsync(e->d_cout, 0, R * p3::kOutStride * 4, e->stream), "hipMemset copy rows")) ||
+      (copies && !e->check(hipMemsetAsync(e->d_sfeats, 0, B * kFeatBytes, e->stream), "hipMemset symmetry upload")) ||
+      (copies && !e->check(hipMemsetAsync(e->d_cout, 0, R * p3::kOutStride * 4, e->stream), "hipMemset copy rows")) ||
       (is_tfm(path) && !e->check(hipMemsetAsync(e->d_qkv, 0, qkv_bytes, e->stream), "hipMemset qkv")) ||
       !e->check(hipMemsetAsync(e->d_out, 0, B * p3::kOutStride * 4, e->stream), "hipMemset out") ||
       !e->check(hipStreamSynchronize(e->stream), "upload sync")) return fail(e->err);
@@ -193,6 +235,8 @@ p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version
   e->slots = p3::SlotStates((int)B);
   e->slot_sym.assign(B, 0);
   e->row_sym.assign(B, 0);
+  e->slot_mask.assign(B, 1);
+  e->row_mask.assign(B, 1);
   e->has_labels.assign(B, 0);
   e->has_targets.assign(B, 0);
   e->load_seq.assign(B, 0);
@@ -206,7 +250,8 @@ void p3hip_destroy(p3hip_engine* e) {
   if (e->stream) hipStreamSynchronize(e->stream);
   hipFree(e->d_arena); hipFree(e->d_feats); hipFree(e->d_x); hipFree(e->d_t); hipFree(e->d_u); hipFree(e->d_s);
   hipFree(e->d_hp); hipFree(e->d_pool); hipFree(e->d_out); hipFree(e->d_res); hipFree(e->d_qkv);
-  hipFree(e->d_sfeats); hipFree(e->d_cout); hipFree(e->d_aux);
+  hipFree(e->d_sfeats); hipFree(e->d_cout); hipFree(e->d_aux); hipFree(e->d_symtab);
+  if (e->h_symtab) hipHostFree(e->h_symtab);
   hipFree(e->d_bw_stamps);
   hipFree(e->d_amax); hipFree(e->d_ascale);
   if (e->bw_mod) hipModuleUnload(e->bw_mod);
@@ -297,6 +342,7 @@ int p3hip_load_slot(p3hip_engine* e, int slot, const p3hip_features* f) {
   if (slot < 0 || slot >= e->batch) return 1;
   memcpy(e->h_feats + (size_t)slot * kFeatBytes, f, kFeatBytes);
   e->slot_sym[slot] = 0;
+  e->slot_mask[slot] = 1;
   e->has_labels[slot] = 0;   // labels and targets belong to one load (p3hip_load_labels, p3hip_load_targets)
   e->has_targets[slot] = 0;
   ++e->load_seq[slot];
@@ -310,6 +356,7 @@ int p3hip_load_slot_keyed(p3hip_engine* e, int slot, const p3hip_features* f, ui
   if (symmetry < 0 || symmetry > 7) return 1;
   memcpy(e->h_feats + (size_t)slot * kFeatBytes, f, kFeatBytes);
   e->slot_sym[slot] = (unsigned char)symmetry;
+  e->slot_mask[slot] = 1;
   e->has_labels[slot] = 0;
   e->has_targets[slot] = 0;
   ++e->load_seq[slot];
@@ -379,6 +426,7 @@ static int gather_loaded(p3hip_engine* e) {
     if (s != row) identity = false;
     moved.emplace_back(s, row);
     e->row_sym[row] = e->slot_sym[s];
+    e->row_mask[row] = e->slot_mask[s];
     e->run_load_seq[s] = e->load_seq[s];
     if (e->cache.on) {
       e->cache.h_keys[row] = e->cache.h_slot_keys[s];
@@ -393,6 +441,15 @@ static int gather_loaded(p3hip_engine* e) {
       memcpy(e->h_feats_compact + (size_t)m.second * kFeatBytes, e->h_feats + (size_t)m.first * kFeatBytes, kFeatBytes);
   e->last_n = n;
   return n;
+}
+
+// P3HIP_FLAG_SYMMETRY_SLOT: the table of the rows gather_loaded compacted.  When their copies exceed the engine's rows
+// nothing is queued, no slot keeps a row (p3hip_get_slot answers 2) and every slot stays pending for the next run.
+static bool stage_gathered(p3hip_engine* e, int n) {
+  if (!e->sym_slot || stage_sym_table(e, e->row_mask.data(), n)) return true;
+  e->slots.drop_rows();
+  e->last_n = 0;
+  return false;
 }
 
 // An INT8 engine runs only once it has activation scales (the reference refuses --use_int8 without a calibration set);
@@ -457,6 +514,7 @@ int p3hip_upload(p3hip_engine* e) {
   if (!e->bind()) return 1;
   int n = gather_loaded(e);
   if (n == 0) return 0;
+  if (!stage_gathered(e, n)) return 1;
   return upload(e, n) && e->check(hipStreamSynchronize(e->stream), "sync") ? 0 : 1;
 }
 
@@ -492,6 +550,7 @@ static int run_cached(p3hip_engine* e, int n) {
   int nm = 0, nh = 0, ni = 0;
   for (int r = 0; r < n; ++r) nm += c.h_hit[r] < 0;
   int mi = 0, hi = 0;
+  std::vector<unsigned char> miss_mask;   // P3HIP_FLAG_SYMMETRY_SLOT: the masks of the misses, by miss row
   // entries this run reads (hits) or has already given to an insert: one writer per entry, no reader evicted
   std::unordered_set<int> claimed;
   for (int r = 0; r < n; ++r) if (c.h_hit[r] >= 0) claimed.insert(c.h_hit[r]);
@@ -508,6 +567,7 @@ static int run_cached(p3hip_engine* e, int n) {
       c.out_row[r] = mi;
       c.h_sym[mi] = (unsigned)c.h_keys[r].sym;
       miss_rows[mi] = r;
+      if (e->sym_slot) miss_mask.push_back(e->row_mask[r]);
       const int v = c.h_victim[r];
       if (keyed && v >= 0 && claimed.insert(v).second) {
         ins_rows[ni] = r; ins_src[ni] = mi; ins_idx[ni] = v; ++ni;
@@ -519,8 +579,10 @@ static int run_cached(p3hip_engine* e, int n) {
   if (!e->check(hipMemcpyAsync(c.d_lists, c.h_lists, 5 * B * 4, hipMemcpyHostToDevice, s), "H2D lists")) return 1;
   if (nm > 0) {
     a.rows = c.d_lists; a.m = nm; a.feats_in = upload_buffer(e); a.feats_out = c.d_feats2;
-    // the misses are evaluated into their d_out rows 0 .. nm - 1 (symmetry averaging: expanded, evaluated and reduced)
-    if (!e->check(p3::launch_cache_gather(a, s), "launch k_cache_gather") || !run_pass(e, Pass{c.d_feats2, nm, e->d_out}))
+    // the misses are evaluated into their d_out rows 0 .. nm - 1 (symmetry averaging: expanded, evaluated and reduced;
+    // the stream is drained, so the pinned table is free to take the misses' masks: a subset of the run's, within capacity)
+    if ((e->sym_slot && !stage_sym_table(e, miss_mask.data(), nm)) ||
+        !e->check(p3::launch_cache_gather(a, s), "launch k_cache_gather") || !run_pass(e, Pass{c.d_feats2, nm, e->d_out}))
       return 1;
   }
   if (nh > 0) {
@@ -534,13 +596,19 @@ static int run_cached(p3hip_engine* e, int n) {
   }
   if (!download(e, n, nullptr)) return 1;
   if (nh > 0 && !e->check(hipMemcpyAsync(c.h_sym + nm, c.d_sym + nm, (size_t)nh * 4, hipMemcpyDeviceToHost, s), "D2H symmetries")) return 1;
-  return e->check(hipStreamSynchronize(s), "sync") ? 0 : 1;
+  if (!e->check(hipStreamSynchronize(s), "sync")) return 1;
+  // P3HIP_FLAG_SYMMETRY_SLOT: the table on the device is the misses'; d_sfeats holds the run's n slots, so put their
+  // table back for p3hip_forward_resident and p3hip_time_trunk_kernel (drained again: the next stage reuses the pinned block)
+  if (e->sym_slot && nm > 0 && nm < n &&
+      (!stage_sym_table(e, e->row_mask.data(), n) || !e->check(hipStreamSynchronize(s), "sync"))) return 1;
+  return 0;
 }
 
 int p3hip_run(p3hip_engine* e) {
   if (!e->bind() || !int8_ready(e)) return 1;
   int n = gather_loaded(e);
   if (n == 0) return 0;
+  if (!stage_gathered(e, n)) return 1;   // (with the cache on: the capacity check over all rows; the misses get their own table)
   if (e->cache.on && !e->calibrating) return run_cached(e, n);   // calibration evaluates every slot, stores nothing
   if (!upload(e, n)) return 1;
   // The heads kernel writes the result records (the first kResultFloats of an output row) a second time into a dense
@@ -681,10 +749,10 @@ double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
   else if (path == Path::Fused || path == Path::Blockw) per_pass = nfused;
   else if (is_int8_fused(path)) per_pass = nlw;
   if (per_pass == 0) return -1.0;
-  if (e->sym) {
-    // symmetry averaging: the trunk runs over the k copies of the resident slots (p3hip_upload put them in d_sfeats)
+  if (e->any_sym()) {
+    // symmetry averaging: the trunk runs over the copies of the resident slots (p3hip_upload put them in d_sfeats)
     if (!expand_sym(e, e->d_sfeats, n_positions)) return -1.0;
-    n_positions *= e->sym_k;
+    n_positions = e->sym_slot ? sym_rows_of(e, n_positions) : n_positions * e->sym_k;
   }
   while ((int)e->blk_ev.size() < 2 * per_pass) {
     hipEvent_t ev;
@@ -694,7 +762,7 @@ double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
   // Time the kernel where it runs: whole forward passes over the resident batch, with a HIP event pair (on the engine's
   // stream) around each timed launch.  The average over all launches is what rocprofv3 --kernel-trace --stats reports
   // for the same run.
-  Pass p{e->d_feats, n_positions, e->sym ? e->d_cout : e->d_out};
+  Pass p{e->d_feats, n_positions, e->any_sym() ? e->d_cout : e->d_out};
   if (!enqueue_forward(e, p)) return -1.0;   // warm-up
   double total_ms = 0.0;
   long launches = 0;
@@ -775,7 +843,7 @@ double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
 // debugging aid: the residual stream x of the last forward pass, n_positions x C x 361 fp16 in the device layout
 // [pos][C / 8][361][8], as floats
 int p3hip_debug_x(p3hip_engine* e, float* out, int n_positions) {
-  if (e->sym) { e->err = "p3hip_debug_x: not available on a P3HIP_FLAG_SYMMETRY_AVG engine"; return 1; }
+  if (e->any_sym()) { e->err = "p3hip_debug_x: not available on a P3HIP_FLAG_SYMMETRY_AVG / P3HIP_FLAG_SYMMETRY_SLOT engine"; return 1; }
   if (!e->bind() || n_positions < 1 || n_positions > e->batch) return 1;
   return read_acts(e, e->d_x, 0, (size_t)n_positions * e->wf.C * kNLoc, out);
 }
@@ -784,8 +852,8 @@ int p3hip_debug_x(p3hip_engine* e, float* out, int n_positions) {
 // stored for the block behind it (LayerPlan region 3, d_u), [pos][C / 16][361][16]
 int p3hip_debug_act_i8(p3hip_engine* e, int8_t* out, int n_positions) {
   const Path path = e->trunk_path();
-  if ((path != Path::Int8 && path != Path::Int8Any) || e->sym) {
-    e->err = "p3hip_debug_act_i8: only on a P3HIP_FLAG_INT8 / P3HIP_FLAG_INT8_ANY layer-wise engine without P3HIP_FLAG_SYMMETRY_AVG";
+  if ((path != Path::Int8 && path != Path::Int8Any) || e->any_sym()) {
+    e->err = "p3hip_debug_act_i8: only on a P3HIP_FLAG_INT8 / P3HIP_FLAG_INT8_ANY layer-wise engine without P3HIP_FLAG_SYMMETRY_AVG / P3HIP_FLAG_SYMMETRY_SLOT";
     return 1;
   }
   if (!e->bind() || n_positions < 1 || n_positions > e->batch) return 1;
@@ -798,7 +866,10 @@ int p3hip_debug_act_i8(p3hip_engine* e, int8_t* out, int n_positions) {
 // device.  The heads take d_t as scratch, so o is that of the last block only on an engine stopped in front of them
 // (P3HIP_DEBUG_STOP_BLOCK = the block count, or any earlier block).
 int p3hip_debug_tfm(p3hip_engine* e, int which, float* out, int n_positions) {
-  if (!is_tfm(e->trunk_path()) || e->sym) { e->err = "p3hip_debug_tfm: only on a transformer engine without P3HIP_FLAG_SYMMETRY_AVG"; return 1; }
+  if (!is_tfm(e->trunk_path()) || e->any_sym()) {
+    e->err = "p3hip_debug_tfm: only on a transformer engine without P3HIP_FLAG_SYMMETRY_AVG / P3HIP_FLAG_SYMMETRY_SLOT";
+    return 1;
+  }
   if (which < 0 || which > 3) { e->err = "p3hip_debug_tfm: which must be 0 (q), 1 (k), 2 (v) or 3 (o)"; return 1; }
   if (n_positions < 1 || n_positions > e->last_npos) { e->err = "p3hip_debug_tfm: more positions than the last run had"; return 1; }
   if (!e->bind()) return 1;
@@ -817,6 +888,18 @@ int p3hip_rope_table_dim(int head_dim, double* cos_out, double* sin_out) {
 }
 
 void p3hip_symmetry_maps(uint16_t fwd[8][361], uint16_t inv[8][361]) { p3::sym_maps(fwd, inv); }
+
+int p3hip_debug_symmetry_rows(const uint8_t* masks, int n, int rows, int* first, int* total) {
+  return p3::sym_rows(masks, n, rows, first, total);
+}
+
+int p3hip_set_slot_symmetries(p3hip_engine* e, int slot, uint32_t mask) {
+  if (!e->sym_slot) { e->err = "p3hip_set_slot_symmetries: the engine was not created with P3HIP_FLAG_SYMMETRY_SLOT"; return 1; }
+  if (slot < 0 || slot >= e->batch) { e->err = "p3hip_set_slot_symmetries: bad slot"; return 1; }
+  if (mask < 1 || mask > 255) { e->err = "p3hip_set_slot_symmetries: the mask must be 1 .. 255 (bit s = symmetry s)"; return 1; }
+  e->slot_mask[slot] = (unsigned char)mask;
+  return 0;
+}
 
 int p3hip_set_symmetries(p3hip_engine* e, uint32_t mask) {
   if (!e->sym) { e->err = "p3hip_set_symmetries: the engine was not created with P3HIP_FLAG_SYMMETRY_AVG"; return 1; }

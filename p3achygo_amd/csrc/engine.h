@@ -77,6 +77,18 @@ struct p3hip_engine {
   int rows = 0;
   unsigned char* d_sfeats = nullptr;
   float* d_cout = nullptr;
+  // P3HIP_FLAG_SYMMETRY_SLOT: the same buffers, with a mask per slot and `rows` = the
+  // symmetry_rows of p3hip_create_rows.  slot_mask: by slot (set after the load, reset to 0x01 by every load); row_mask:
+  // by dense row of the last gather.  The table of a pass (stage_sym_table: first[] as p3::sym_rows gives it, then the
+  // masks, tab_n rows) goes up in one copy: h_symtab is pinned, [batch] ints then [batch] bytes, d_symtab its device
+  // twin; tab_first / tab_mask point into d_symtab.  tab_total: the copies of those tab_n rows.
+  bool sym_slot = false;
+  std::vector<unsigned char> slot_mask, row_mask;
+  unsigned char *h_symtab = nullptr, *d_symtab = nullptr;
+  int tab_n = 0, tab_total = 0;
+  const int* tab_first() const { return reinterpret_cast<const int*>(d_symtab); }
+  const unsigned char* tab_mask() const { return d_symtab + (size_t)batch * 4; }
+  bool any_sym() const { return sym || sym_slot; }
 
   // buffers
   unsigned char* h_feats = nullptr;       // pinned [batch] slots as loaded
@@ -197,6 +209,11 @@ void tfm_split_of(const p3hip_engine* e, int npos, int* parts, int* tokens);   /
 void edge_split_of(const p3hip_engine* e, int npos, int* stem, int* dense, int* heads);
 bool enqueue_forward(p3hip_engine* e, const Pass& p);
 bool expand_sym(p3hip_engine* e, const unsigned char* src, int n);
+// P3HIP_FLAG_SYMMETRY_SLOT: builds the table of the `n` dense rows with `masks` and queues its upload; false with the
+// sum and the capacity in e->err when the copies exceed e->rows (nothing is queued then)
+bool stage_sym_table(p3hip_engine* e, const unsigned char* masks, int n);
+// the forward rows of the first `n` rows of the staged table (-1: the table holds fewer rows)
+int sym_rows_of(const p3hip_engine* e, int n);
 bool run_pass(p3hip_engine* e, const Pass& p);
 void drop_graph(p3hip_engine* e);
 // scoring.cpp

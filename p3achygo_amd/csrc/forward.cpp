@@ -1,6 +1,9 @@
 // forward.cpp — the forward pass of an engine: the launch arguments of the block kernels, the one launcher of a layer
 // conv, one enqueue function per block family, symmetry expand / reduce, and the captured graph.
+#include <algorithm>
 #include <cstdlib>
+#include <cstring>
+#include <string>
 
 #include "block_i8.h"
 #include "conv_any.h"
@@ -602,8 +605,48 @@ bool enqueue_forward(p3hip_engine* e, const Pass& p) {
   return enqueue_heads(e, p);
 }
 
-// k_sym_expand: the `n` records at `src` -> their k copies in d_feats
+// P3HIP_FLAG_SYMMETRY_SLOT: first[] and the masks of `n` dense rows into the pinned table, and its upload on the stream
+bool stage_sym_table(p3hip_engine* e, const unsigned char* masks, int n) {
+  const size_t B = (size_t)e->batch;
+  int* first = reinterpret_cast<int*>(e->h_symtab);
+  int total = 0;
+  e->tab_n = e->tab_total = 0;
+  if (p3::sym_rows(masks, n, e->rows, first, &total) != 0) {
+    e->err = "P3HIP_FLAG_SYMMETRY_SLOT: the symmetry masks of the " + std::to_string(n) + " slots of this run add up to " +
+             std::to_string(total) + " copies, the engine was created with symmetry_rows " + std::to_string(e->rows) +
+             " (nothing was launched; lower masks with p3hip_set_slot_symmetries and run again)";
+    return false;
+  }
+  memcpy(e->h_symtab + B * 4, masks, (size_t)n);
+  // one copy where the two arrays are adjacent (the full static batch), else one each
+  const bool ok = (size_t)n == B
+      ? e->check(hipMemcpyAsync(e->d_symtab, e->h_symtab, B * 5, hipMemcpyHostToDevice, e->stream), "H2D symmetry table")
+      : e->check(hipMemcpyAsync(e->d_symtab, e->h_symtab, (size_t)n * 4, hipMemcpyHostToDevice, e->stream), "H2D symmetry table") &&
+        e->check(hipMemcpyAsync(e->d_symtab + B * 4, e->h_symtab + B * 4, (size_t)n, hipMemcpyHostToDevice, e->stream), "H2D symmetry masks");
+  if (!ok) return false;
+  e->tab_n = n;
+  e->tab_total = total;
+  return true;
+}
+
+int sym_rows_of(const p3hip_engine* e, int n) {
+  if (n < 1 || n > e->tab_n) return -1;
+  return n == e->tab_n ? e->tab_total : reinterpret_cast<const int*>(e->h_symtab)[n];
+}
+
+// k_sym_expand / k_sym_expand_slots: the `n` records at `src` -> their copies in d_feats
 bool expand_sym(p3hip_engine* e, const unsigned char* src, int n) {
+  if (e->sym_slot) {
+    const int total = sym_rows_of(e, n);
+    if (total < 0) {
+      e->err = "P3HIP_FLAG_SYMMETRY_SLOT: " + std::to_string(n) + " positions asked for, the last p3hip_run / p3hip_upload staged the masks of " +
+               std::to_string(e->tab_n);
+      return false;
+    }
+    p3::SymExpandSlotsArgs x{};
+    x.in = src; x.out = e->d_feats; x.first = e->tab_first(); x.mask = e->tab_mask(); x.n = n; x.cap = e->rows;
+    return e->check(p3::launch_sym_expand_slots(x, total, e->stream), "launch k_sym_expand_slots");
+  }
   p3::SymExpandArgs x{};
   x.in = src; x.out = e->d_feats; x.n = n; x.k = e->sym_k;
   for (int j = 0; j < p3::kNumSyms; ++j) x.syms[j] = e->sym_syms[j];
@@ -614,8 +657,15 @@ namespace {
 
 // P3HIP_FLAG_SYMMETRY_AVG: the `p.npos` slots' records in p.feats -> k copies each in d_feats -> the forward pass over
 // n k rows (the heads write d_cout, never d_res) -> the averaged rows in p.out, and the result records in p.res.
+// P3HIP_FLAG_SYMMETRY_SLOT: the same over the staged table's rows.
 bool enqueue_sym(p3hip_engine* e, const Pass& p) {
-  if (!expand_sym(e, p.feats, p.npos) || !enqueue_forward(e, Pass{e->d_feats, p.npos * e->sym_k, e->d_cout})) return false;
+  const int total = e->sym_slot ? sym_rows_of(e, p.npos) : p.npos * e->sym_k;
+  if (!expand_sym(e, p.feats, p.npos) || !enqueue_forward(e, Pass{e->d_feats, total, e->d_cout})) return false;
+  if (e->sym_slot) {
+    p3::SymReduceSlotsArgs r{};
+    r.rows = e->d_cout; r.out = p.out; r.res = p.res; r.first = e->tab_first(); r.mask = e->tab_mask(); r.n = p.npos; r.cap = e->rows;
+    return e->check(p3::launch_sym_reduce_slots(r, total, e->stream), "launch k_sym_reduce_slots");
+  }
   p3::SymReduceArgs r{};
   r.rows = e->d_cout; r.out = p.out; r.res = p.res; r.n = p.npos; r.k = e->sym_k;
   for (int j = 0; j < p3::kNumSyms; ++j) r.syms[j] = e->sym_syms[j];
@@ -631,9 +681,13 @@ bool enqueue_sym(p3hip_engine* e, const Pass& p) {
 // which a capture must not see), the second is captured, the rest replay.  A capture that fails falls back to the
 // launches for good.  Calibration runs (the fp16 plan + absmax) go kernel by kernel.
 bool run_pass(p3hip_engine* e, const Pass& p) {
-  e->last_npos = p.npos * (e->sym ? e->sym_k : 1);
-  auto enqueue = [&] { return e->sym ? enqueue_sym(e, p) : enqueue_forward(e, p); };
+  e->last_npos = e->sym_slot ? std::max(sym_rows_of(e, p.npos), 0) : p.npos * (e->sym ? e->sym_k : 1);
+  auto enqueue = [&] { return e->any_sym() ? enqueue_sym(e, p) : enqueue_forward(e, p); };
   if (!(e->flags & P3HIP_FLAG_LAUNCH_GRAPH) || p.npos != e->batch || e->graph_failed || e->calibrating) return enqueue();
+  // P3HIP_FLAG_SYMMETRY_SLOT: the graph's grids are those of batch forward rows, every slot under one symmetry (the
+  // kernels read which from the table in device memory, so it may change from replay to replay); a run with an
+  // averaged slot has more rows and goes out kernel by kernel
+  if (e->sym_slot && e->last_npos != e->batch) return enqueue();
   // The capture bakes every kernel argument in: the feature buffer the pass reads (run_cached's passes read the cache's
   // gathered copy) and whether it writes d_res.  The graph serves the pass it was captured for; any other goes out
   // kernel by kernel.

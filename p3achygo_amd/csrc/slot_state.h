@@ -49,6 +49,11 @@ class SlotStates {
     }
     return n;
   }
+  // A run refused after its gather (the copies of a P3HIP_FLAG_SYMMETRY_SLOT run exceed the engine's rows): no slot has
+  // a result; the states stay as they are, so the next run gathers the same slots again.
+  void drop_rows() {
+    for (int& r : row_) r = -1;
+  }
   // Dense row of `slot` in the last run, -1 if it was not evaluated.
   int row(int slot) const { return row_[slot]; }
   // GetBatch: the result has been handed over; the slot stays out of later runs until reloaded.

@@ -10,6 +10,16 @@
 //                 host/symmetry.h ApplyInverse does (out[inv[s][i]] = in[i], i.e. out[p] = in[fwd[s][p]]), then every
 //                 float acc = v_0; acc += v_1; ...; acc / (float)k in fp32 with a correctly rounded division.
 //
+// P3HIP_FLAG_SYMMETRY_SLOT: the same rule with a mask per slot.  The copies of dense slot r lie at
+// rows first[r] .. first[r] + k_r - 1 (k_r the popcount of the slot's mask, ascending symmetry), first[] the running sum
+// of the popcounts (sym_rows), so a run of n slots is `total` = first[n - 1] + k_{n-1} forward rows.
+//
+//   k_sym_expand_slots  n feature records -> total records, slot r's copies from row first[r] on
+//   k_sym_reduce_slots  the total rows -> one row per slot
+//
+// Both read first[] and the masks from device memory (uploaded with the features), so a captured graph whose grids are
+// fixed (every k_r = 1) serves whatever symmetries the slots carry.  The per-copy bodies are written once for both pairs.
+//
 // The maps are built here by a constexpr function, once for the kernels (constant memory) and once for
 // p3hip_symmetry_maps, so a CPU test pins the very tables the kernels read.
 #pragma once
@@ -73,7 +83,31 @@ struct SymReduceArgs {
   int syms[kNumSyms];
 };
 
+struct SymExpandSlotsArgs {
+  const unsigned char* in;     // [n] p3hip_features, dense
+  unsigned char* out;          // [cap] p3hip_features
+  const int* first;            // [n] first row of the slot's copies
+  const unsigned char* mask;   // [n] the slot's symmetries, 1 .. 255
+  int n, cap;                  // cap: the rows `out` holds; a table entry that would pass it writes nothing
+};
+struct SymReduceSlotsArgs {
+  const float* rows;   // [cap][kOutStride]
+  float* out;          // [n][kOutStride]
+  float* res;          // [n][kResultFloats] or null
+  const int* first;
+  const unsigned char* mask;
+  int n, cap;
+};
+
+// first[r] = the popcounts of masks[0 .. r - 1] summed, *total = the sum over all n.  1 for n < 1, a mask of 0, or a
+// total above `rows`; 0 otherwise.  No device.  The engine builds the table it uploads with this function
+// (p3hip_debug_symmetry_rows is this function).
+int sym_rows(const uint8_t* masks, int n, int rows, int* first, int* total);
+
 hipError_t launch_sym_expand(const SymExpandArgs& a, hipStream_t s);
+// total: the table's sum of copies as sym_rows returned it; hipErrorInvalidValue for n < 1 and for total > cap
+hipError_t launch_sym_expand_slots(const SymExpandSlotsArgs& a, int total, hipStream_t s);
+hipError_t launch_sym_reduce_slots(const SymReduceSlotsArgs& a, int total, hipStream_t s);
 hipError_t launch_sym_reduce(const SymReduceArgs& a, hipStream_t s);
 // the tables the kernels read (host copy of the same constexpr build)
 void sym_maps(uint16_t fwd[kNumSyms][kSymLocs], uint16_t inv[kNumSyms][kSymLocs]);

@@ -32,6 +32,7 @@ EXPORTS = [
     "p3hip_blockw_stamps", "p3hip_debug_x", "p3hip_debug_tfm", "p3hip_rope_table", "p3hip_rope_table_dim",
     "p3hip_int8_calibrate", "p3hip_int8_scales", "p3hip_int8_set_scales",
     "p3hip_set_symmetries", "p3hip_symmetry_maps",
+    "p3hip_create_rows", "p3hip_set_slot_symmetries", "p3hip_debug_symmetry_rows",
     "p3hip_load_labels", "p3hip_score", "p3hip_get_score", "p3hip_debug_score_rows",
     "p3hip_get_aux",
     "p3hip_load_targets", "p3hip_loss", "p3hip_get_loss", "p3hip_debug_loss_rows",
@@ -79,6 +80,8 @@ FLAG_LOW_LATENCY = 4096
 FLAG_LOW_LATENCY_TFM = 8192
 FLAG_LOW_LATENCY_ANY = FLAG_LOW_LATENCY | FLAG_LOW_LATENCY_TFM   # the low-latency plan whatever the trunk
 FLAG_SYMMETRY_AVG = 32  # every slot averaged over a set of the eight symmetries on the device
+# the same with a symmetry mask per slot, the copies of all slots packed densely (include/p3hip.h)
+FLAG_SYMMETRY_SLOT = 16384
 
 
 def labels_dtype() -> np.dtype:
@@ -164,6 +167,11 @@ def lib():
         L.p3hip_set_symmetries.argtypes = [C.c_void_p, C.c_uint32]
         L.p3hip_symmetry_maps.argtypes = [C.c_void_p, C.c_void_p]
         L.p3hip_symmetry_maps.restype = None
+        if hasattr(L, "p3hip_create_rows"):   # (P3HIP_LIB may name an earlier build of the library, tools/gpu_ab.py)
+            L.p3hip_create_rows.restype = C.c_void_p
+            L.p3hip_create_rows.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int]
+            L.p3hip_set_slot_symmetries.argtypes = [C.c_void_p, C.c_int, C.c_uint32]
+            L.p3hip_debug_symmetry_rows.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
         L.p3hip_load_labels.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.p3hip_score.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]
         L.p3hip_get_score.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
@@ -218,9 +226,14 @@ class HipEngine:
     """nn::Engine over libp3hip.so (engine.h:22-43)."""
 
     def __init__(self, path: str, batch_size: int, version: int = 1, device: int = 0,
-                 flags: int = 0):
+                 flags: int = 0, symmetry_rows: int = 0):
+        """symmetry_rows: the forward rows a run of a FLAG_SYMMETRY_SLOT engine may evaluate (p3hip_create_rows);
+        0 = 8 x batch_size."""
         self._L = lib()
-        self._h = self._L.p3hip_create(path.encode(), batch_size, version, device, flags)
+        if symmetry_rows:
+            self._h = self._L.p3hip_create_rows(path.encode(), batch_size, version, device, flags, symmetry_rows)
+        else:
+            self._h = self._L.p3hip_create(path.encode(), batch_size, version, device, flags)
         if not self._h:
             raise EngineError("p3hip_create: " + self._L.p3hip_create_error().decode())
         self.batch_size = batch_size
@@ -298,6 +311,14 @@ class HipEngine:
         if not 0 <= int(mask) < 1 << 32:
             raise EngineError(f"set_symmetries: mask {mask} is not a uint32")
         self._ck(self._L.p3hip_set_symmetries(self._h, int(mask)), "set_symmetries")
+
+    # -- a symmetry set per slot (FLAG_SYMMETRY_SLOT) -------------------------------------
+    def set_slot_symmetries(self, batch_id: int, mask: int) -> None:
+        """The symmetries (bit s = symmetry s, 1..255) of the position last loaded into the slot: after LoadBatch, before
+        RunInference.  Every load resets the slot to 0x01.  Fails on an engine created without FLAG_SYMMETRY_SLOT."""
+        if not 0 <= int(mask) < 1 << 32:
+            raise EngineError(f"set_slot_symmetries: mask {mask} is not a uint32")
+        self._ck(self._L.p3hip_set_slot_symmetries(self._h, batch_id, int(mask)), "set_slot_symmetries")
 
     # -- scoring against labels on the device (include/p3hip.h; DefaultStats, benchmark_engine.cc:25-61) ----
     def load_labels(self, batch_id: int, labels) -> None:
@@ -596,9 +617,21 @@ def symmetry_maps():
     return fwd, inv
 
 
+def debug_symmetry_rows(masks, rows: int):
+    """(first, total) of the table a FLAG_SYMMETRY_SLOT engine uploads for dense slots with these masks (no device
+    needed): first[r] = the row at which slot r's copies start, total = the sum of the popcounts.  EngineError where the
+    engine refuses the table: no slot, a mask of 0, more than `rows` copies."""
+    m = np.ascontiguousarray(masks, np.uint8)
+    first = np.zeros(max(len(m), 1), np.int32)
+    total = C.c_int(0)
+    if lib().p3hip_debug_symmetry_rows(m.ctypes.data, len(m), rows, first.ctypes.data, C.byref(total)) != 0:
+        raise EngineError(f"debug_symmetry_rows: refused ({len(m)} slots, {total.value} copies, {rows} rows)")
+    return first[:len(m)], total.value
+
+
 def create_engine(kind: Kind, path: str, batch_size: int, version: int, device: int = 0,
-                  flags: int = 0) -> HipEngine:
+                  flags: int = 0, symmetry_rows: int = 0) -> HipEngine:
     """CreateEngine (engine_factory.cc:56-73); only kHip is served by this package."""
     if kind == Kind.kHip:
-        return HipEngine(path, batch_size, version, device, flags)
+        return HipEngine(path, batch_size, version, device, flags, symmetry_rows)
     raise EngineError(f"Unknown Engine Kind {kind!r} (the reference LOG(FATAL)s here)")

@@ -101,6 +101,14 @@ struct EvalPlayerConfig {   // PlayerSearchConfig (player_config.h:20-108), same
   // split across workgroups; transformer trunks, a block's launches split across workgroups).  For players whose engines see few positions at a time: a timed search turns the forward pass's latency
   // into visits per move.
   int nn_low_latency = 0;
+  // extension: the player's engine takes a symmetry set per slot (P3HIP_FLAG_SYMMETRY_SLOT): every evaluation's random
+  // symmetry goes to the engine as the slot's mask, features are loaded un-rotated and results come back un-rotated.
+  // The games are those of host rotation.
+  int nn_device_symmetry = 0;
+  // extension: evaluations of a search's root position are averaged over these symmetries on the device (bit s =
+  // symmetry s; 0 = off); every other evaluation keeps its one random symmetry.  Implies nn_device_symmetry.
+  uint32_t nn_root_symmetry_mask = 0;
+  bool device_symmetry() const { return nn_device_symmetry != 0 || nn_root_symmetry_mask != 0; }
 };
 
 // nn_symmetry_mask: decimal or 0x hex, 0 .. 255
@@ -244,6 +252,19 @@ inline bool ParsePlayerConfigStream(std::istream& in, EvalPlayerConfig* cfg, std
         }
         cfg->nn_low_latency = val == "1";
       }
+      else if (key == "nn_device_symmetry") {
+        if (val != "0" && val != "1") {
+          if (err) *err = "nn_device_symmetry must be 0 or 1: " + line;
+          return false;
+        }
+        cfg->nn_device_symmetry = val == "1";
+      }
+      else if (key == "nn_root_symmetry_mask") {
+        if (!ParseSymmetryMask(val, &cfg->nn_root_symmetry_mask)) {
+          if (err) *err = "nn_root_symmetry_mask must be 0 .. 255, decimal or 0x hex: " + line;
+          return false;
+        }
+      }
       // unknown keys are ignored (player_config.h:243)
     }
   } catch (const std::exception& e) {   // the reference lets std::stoi / std::stof throw out of main
@@ -296,7 +317,17 @@ class EvalGame {
     }
   }
   void FillEval(int i, p3hip_features* f) {
-    sym_[i] = RandomSymmetry(prob_.prng());
+    const Symmetry drawn = RandomSymmetry(prob_.prng());   // the same draw at the same point, whoever rotates
+    const EvalPlayerConfig& c = cfg_[color_ == kBlack ? 0 : 1];
+    if (c.device_symmetry()) {
+      // the engine rotates: un-rotated features, the symmetry (a root visit: the root mask) as the slot's mask
+      const bool root = parallel_ ? search_.eval_is_root(i) : puct_.eval_is_root();
+      mask_[i] = root && c.nn_root_symmetry_mask ? c.nn_root_symmetry_mask : 1u << (int)drawn;
+      sym_[i] = kIdentity;
+    } else {
+      mask_[i] = 0;
+      sym_[i] = drawn;
+    }
     if (parallel_) FillFeatures(search_.eval_pos(i), search_.eval_color(i), sym_[i], f);
     else FillFeatures(*puct_.eval_game(), puct_.eval_color(), sym_[i], f);
   }
@@ -307,6 +338,8 @@ class EvalGame {
   }
   // the engine's NN cache answered (or evaluated) under symmetry `sym`, which need not be the one FillEval drew
   Symmetry eval_symmetry(int i) const { return sym_[i]; }
+  // the mask to hand to the engine after the load of evaluation i (0: the player's engine has no per-slot symmetries)
+  uint32_t eval_mask(int i) const { return mask_[i]; }
   void DeliverUnder(int i, p3hip_result& r, Symmetry sym) {
     sym_[i] = sym;
     Deliver(i, r);
@@ -412,6 +445,7 @@ class EvalGame {
   GumbelSearch puct_;
   bool parallel_ = true;
   Symmetry sym_[64];
+  uint32_t mask_[64] = {};
   bool done_ = false, resigned_ = false;
   Color winner_ = kEmpty;
   long visits_ = 0, collisions_ = 0;

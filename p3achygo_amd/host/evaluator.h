@@ -33,6 +33,11 @@ struct Evaluator {
     Get(slot, r);
     if (from_cache) *from_cache = false;
   }
+  // A symmetry set per slot (include/p3hip.h P3HIP_FLAG_SYMMETRY_SLOT): the engine rotates the features loaded in the
+  // caller's orientation, and rotates back and averages the results.  Called after the load of `slot`, before the run.
+  // An engine without it says no, and the host keeps rotating itself.
+  virtual bool SlotSymmetries() const { return false; }
+  virtual void SetSlotSymmetries(int /*slot*/, uint32_t /*mask*/) {}
 };
 
 // Uniform policy, even outcome, zero score: the reference's NullEngine
@@ -110,9 +115,13 @@ struct HipEvaluator final : Evaluator {
   decltype(&p3hip_get_slot_keyed) get_keyed = nullptr;
   decltype(&p3hip_cache_stats) cache_stats = nullptr;
   decltype(&p3hip_set_symmetries) set_symmetries = nullptr;
+  decltype(&p3hip_create_rows) create_rows = nullptr;
+  decltype(&p3hip_set_slot_symmetries) set_slot_symmetries = nullptr;
+  bool slot_symmetries = false;   // opened with P3HIP_FLAG_SYMMETRY_SLOT
   std::string err;
 
-  bool Open(const char* lib_path, const char* weights, int batch, int device, uint32_t flags = 0) {
+  // symmetry_rows: the row capacity of a P3HIP_FLAG_SYMMETRY_SLOT engine (p3hip_create_rows; 0 = 8 x batch)
+  bool Open(const char* lib_path, const char* weights, int batch, int device, uint32_t flags = 0, int symmetry_rows = 0) {
     lib = dlopen(lib_path, RTLD_NOW | RTLD_LOCAL);
     if (!lib) { err = dlerror(); return false; }
     create = (decltype(create))dlsym(lib, "p3hip_create");
@@ -128,8 +137,19 @@ struct HipEvaluator final : Evaluator {
     get_keyed = (decltype(get_keyed))dlsym(lib, "p3hip_get_slot_keyed");
     cache_stats = (decltype(cache_stats))dlsym(lib, "p3hip_cache_stats");
     set_symmetries = (decltype(set_symmetries))dlsym(lib, "p3hip_set_symmetries");
+    create_rows = (decltype(create_rows))dlsym(lib, "p3hip_create_rows");
+    set_slot_symmetries = (decltype(set_slot_symmetries))dlsym(lib, "p3hip_set_slot_symmetries");
     if (!create || !destroy || !load || !run || !get) { err = "missing p3hip symbols"; return false; }
-    eng = create(weights, batch, 1, device, flags);
+    if (flags & P3HIP_FLAG_SYMMETRY_SLOT) {
+      if (!create_rows || !set_slot_symmetries) {
+        err = "the engine library has no p3hip_create_rows / p3hip_set_slot_symmetries (a symmetry set per slot, device symmetry)";
+        return false;
+      }
+      eng = create_rows(weights, batch, 1, device, flags, symmetry_rows);
+      slot_symmetries = eng != nullptr;
+    } else {
+      eng = create(weights, batch, 1, device, flags);
+    }
     if (!eng) { err = create_error ? create_error() : "p3hip_create failed"; return false; }
     return true;
   }
@@ -175,6 +195,10 @@ struct HipEvaluator final : Evaluator {
     if (int rc = get_keyed(eng, slot, &r, &sym, &hit)) Fatal("get_slot_keyed", slot, rc);
     if (symmetry) *symmetry = sym;
     if (from_cache) *from_cache = hit != 0;
+  }
+  bool SlotSymmetries() const override { return slot_symmetries; }
+  void SetSlotSymmetries(int slot, uint32_t mask) override {
+    if (int rc = set_slot_symmetries(eng, slot, mask)) Fatal("set_slot_symmetries", slot, rc);
   }
   void GetOwnership(int slot, float out[P3HIP_NUM_LOCS]) override {
     if (!get_own) Fatal("get_ownership (symbol missing)", slot, -1);

@@ -88,8 +88,9 @@ class NNInterface final {
   struct Slot {
     Slot(NNInterface* nn, int task_offset) : nn_(nn), off_(task_offset) {}
     SignalKind signal_kind() const { return nn_->signal_kind(); }
-    void LoadEntry(int thread_id, const Game& game, Color c, Probability& prob) {
-      nn_->LoadEntry(thread_id, off_, game, c, prob);
+    // is_root: the evaluation of a search's root position (it gets the root symmetry mask, if one is set)
+    void LoadEntry(int thread_id, const Game& game, Color c, Probability& prob, bool is_root = false) {
+      nn_->LoadEntry(thread_id, off_, game, c, prob, is_root);
     }
     p3hip_result FetchEntry(int thread_id, const Game& game, Color c) { return nn_->FetchEntry(thread_id, off_, game, c); }
     p3hip_result LoadAndGetInference(int thread_id, const Game& game, Color c, Probability& prob) {
@@ -147,19 +148,38 @@ class NNInterface final {
     return device_cache_;
   }
   bool device_cache() const { return device_cache_; }
+  // Hands every evaluation's random symmetry to the engine (P3HIP_FLAG_SYMMETRY_SLOT): the same draw from the same
+  // PRNG at the same point, the features loaded un-rotated with the mask 1 << sym, and no UnapplySymmetry on the way
+  // back: the engine returns the result in the game's own orientation, bit-identical to the host path.  False when
+  // the engine has no per-slot symmetries.
+  bool SetDeviceSymmetry(bool on) {
+    if (on && !engine_->SlotSymmetries()) return false;
+    device_symmetry_ = on;
+    return true;
+  }
+  bool device_symmetry() const { return device_symmetry_; }
+  // Evaluations of a search's root position (LoadEntry / LoadAndGetInference with is_root) are averaged over the
+  // symmetries of `mask` on the device (bit s = symmetry s, 1 .. 255; 0 = off: one random symmetry like any leaf).  The
+  // random symmetry is drawn all the same, so every other evaluation keeps its draw.  Needs device symmetry.  The
+  // per-thread LRU answers a repeated position with whichever evaluation of it came first, root or leaf.
+  bool SetRootSymmetryMask(uint32_t mask) {
+    if (mask > 255 || (mask && !device_symmetry_)) return false;
+    root_mask_ = mask;
+    return true;
+  }
+  uint32_t root_symmetry_mask() const { return root_mask_; }
   long device_cache_hits() const { return device_hits_.load(std::memory_order_relaxed); }
   long device_cache_lookups() const { return device_lookups_.load(std::memory_order_relaxed); }
 
   // Blocks until the result is ready (nn_interface.cc:108-133).
-  p3hip_result LoadAndGetInference(int thread_id, const Game& game, Color color_to_move, Probability& prob) {
+  p3hip_result LoadAndGetInference(int thread_id, const Game& game, Color color_to_move, Probability& prob,
+                                   bool is_root = false) {
     const Key key = MakeKey(game, color_to_move);
     if (caches_[thread_id].Contains(key)) {
       MarkCached(thread_id, true);
       return *caches_[thread_id].Get(key);
     }
-    const Symmetry sym = RandomSymmetry(prob.prng());
-    if (device_cache_) LoadBatchKeyed(thread_id, game, color_to_move, sym);
-    else LoadBatch(thread_id, game, color_to_move, sym);
+    const Symmetry sym = LoadUnder(thread_id, game, color_to_move, RandomSymmetry(prob.prng()), is_root);
     SignalLoadedAndBlockUntilReady(thread_id);
     p3hip_result r = device_cache_ ? GetBatchKeyed(thread_id, sym) : GetBatch(thread_id, sym);
     caches_[thread_id].Insert(key, r);
@@ -201,17 +221,15 @@ class NNInterface final {
   }
 
   // async API (nn_interface.cc:172-230)
-  void LoadEntry(int thread_id, int offset, const Game& game, Color color_to_move, Probability& prob) {
+  void LoadEntry(int thread_id, int offset, const Game& game, Color color_to_move, Probability& prob,
+                 bool is_root = false) {
     const int tid = thread_id + offset;
     const Key key = MakeKey(game, color_to_move);
     if (caches_[tid].Contains(key)) {
       MarkCached(tid, true);
       return;
     }
-    const Symmetry sym = RandomSymmetry(prob.prng());
-    syms_[tid] = sym;
-    if (device_cache_) LoadBatchKeyed(tid, game, color_to_move, sym);
-    else LoadBatch(tid, game, color_to_move, sym);
+    syms_[tid] = LoadUnder(tid, game, color_to_move, RandomSymmetry(prob.prng()), is_root);
     {
       std::lock_guard<std::mutex> l(mu_);
       ThreadInfo& t = info_[tid];
@@ -300,6 +318,15 @@ class NNInterface final {
     if (v) infer_cv_.notify_all();
   }
 
+  // Loads the position for an evaluation under `sym`; returns the symmetry the host has to undo on the result: `sym`
+  // itself, or the identity when the engine rotates (device symmetry)
+  Symmetry LoadUnder(int tid, const Game& game, Color color_to_move, Symmetry sym, bool is_root) {
+    const Symmetry host_sym = device_symmetry_ ? kIdentity : sym;
+    if (device_cache_) LoadBatchKeyed(tid, game, color_to_move, host_sym);
+    else LoadBatch(tid, game, color_to_move, host_sym);
+    if (device_symmetry_) engine_->SetSlotSymmetries(tid, is_root && root_mask_ ? root_mask_ : 1u << (int)sym);
+    return host_sym;
+  }
   void LoadBatch(int tid, const Game& game, Color color_to_move, Symmetry sym) {   // nn_interface.cc:245-277
     p3hip_features f;
     FillFeatures(game, color_to_move, sym, &f);
@@ -338,7 +365,7 @@ class NNInterface final {
     if (hit) device_hits_.fetch_add(1, std::memory_order_relaxed);
     info_[tid].res_ready.store(false, std::memory_order_release);
     NotifyInfer();
-    UnapplySymmetry((Symmetry)sym, &r);
+    if (sym != (int)kIdentity) UnapplySymmetry((Symmetry)sym, &r);
     return r;
   }
   p3hip_result GetBatch(int tid, Symmetry sym) {   // nn_interface.h:254-292
@@ -347,7 +374,7 @@ class NNInterface final {
     // cleared without the lock: Infer() reads it with acquire before RunInference()
     info_[tid].res_ready.store(false, std::memory_order_release);
     NotifyInfer();
-    UnapplySymmetry(sym, &r);
+    if (sym != kIdentity) UnapplySymmetry(sym, &r);
     return r;
   }
 
@@ -464,7 +491,8 @@ class NNInterface final {
   std::vector<LruCache<Key, p3hip_result, KeyHash>> caches_;
   std::thread infer_thread_;
   int num_cache_last_moves_ = 5;
-  bool device_cache_ = false;
+  bool device_cache_ = false, device_symmetry_ = false;
+  uint32_t root_mask_ = 0;
   std::atomic<long> device_hits_{0}, device_lookups_{0};
   const SignalKind signal_kind_;
   const int num_shared_tasks_;

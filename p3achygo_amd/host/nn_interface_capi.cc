@@ -202,9 +202,170 @@ struct KeyedTableEvaluator final : Evaluator {
   long lookups_ = 0, hits_ = 0, evaluated_ = 0;
 };
 
+// ---- the same evaluator with the HIP engine's per-slot symmetries (include/p3hip.h P3HIP_FLAG_SYMMETRY_SLOT) ---------
+// rotates = true: it takes a mask per slot after the load and applies it itself, on the host, by the engine's rule: the
+// stones of the loaded features under every symmetry of the mask (ascending), "evaluated" into the policy fields,
+// rotated back, averaged.  rotates = false: a plain engine (the interface rotates).  With a table when keys are given.
+struct SlotSymmetryEvaluator final : Evaluator {
+  SlotSymmetryEvaluator(int n, bool rotates)
+      : rotates_(rotates), feats_(n), keys_(n), masks_(n, 1u), out_(n), out_sym_(n), out_hit_(n), loaded_(n, 0) {}
+  bool EnableDeviceCache(int) override { return true; }
+  bool SlotSymmetries() const override { return rotates_; }
+  void SetSlotSymmetries(int t, uint32_t mask) override {
+    masks_[t] = mask;
+    seen_ |= mask;
+    ++mask_calls_;
+    if (mask == 0xFFu) ++full_masks_;
+  }
+  void Load(int t, const p3hip_features& f) override { LoadKeyed(t, f, 0, 0, 0); }
+  void LoadKeyed(int t, const p3hip_features& f, uint64_t lo, uint64_t hi, int sym) override {
+    feats_[t] = f;
+    keys_[t] = {lo, hi, sym};
+    masks_[t] = 1u;   // every load resets the slot's mask
+    loaded_[t] = 1;
+    loaded_syms_ |= 1u << sym;
+  }
+  bool Run() override {
+    for (size_t t = 0; t < feats_.size(); ++t) {
+      if (!loaded_[t]) continue;
+      loaded_[t] = 0;
+      const K& k = keys_[t];
+      const bool keyed = (k.lo | k.hi) != 0;
+      auto it = keyed ? table_.find({k.lo, k.hi}) : table_.end();
+      if (it != table_.end()) {
+        out_[t] = it->second.first;
+        out_sym_[t] = it->second.second;
+        out_hit_[t] = true;
+        ++hits_;
+        continue;
+      }
+      p3hip_result acc;
+      std::memset(&acc, 0, sizeof acc);
+      int copies = 0;
+      for (int s = 0; s < kNumSymmetries; ++s) {
+        if (!(masks_[t] >> s & 1u)) continue;
+        int8_t stones[kNumLocs];
+        ApplySymmetry((Symmetry)s, feats_[t].board, stones, kBoardLen);
+        p3hip_result r;
+        std::memset(&r, 0, sizeof r);
+        for (int i = 0; i < kNumLocs; ++i) r.move_logits[i] = r.move_probs[i] = r.opt_move_probs[i] = (float)stones[i];
+        UnapplySymmetry((Symmetry)s, &r);
+        for (int i = 0; i < kNumLocs; ++i) {
+          acc.move_logits[i] += r.move_logits[i];
+          acc.move_probs[i] += r.move_probs[i];
+          acc.opt_move_probs[i] += r.opt_move_probs[i];
+        }
+        ++copies;
+      }
+      for (int i = 0; i < kNumLocs; ++i) {
+        acc.move_logits[i] /= (float)copies;
+        acc.move_probs[i] /= (float)copies;
+        acc.opt_move_probs[i] /= (float)copies;
+      }
+      acc.value_probs[1] = 1.0f;
+      out_[t] = acc;
+      out_sym_[t] = k.sym;
+      out_hit_[t] = false;
+      ++evaluated_;
+      if (keyed) table_[{k.lo, k.hi}] = {acc, k.sym};
+    }
+    return true;
+  }
+  void Get(int t, p3hip_result& r) override { r = out_[t]; }
+  void GetKeyed(int t, p3hip_result& r, int* sym, bool* hit) override {
+    r = out_[t];
+    if (sym) *sym = out_sym_[t];
+    if (hit) *hit = out_hit_[t];
+  }
+  using K = KeyedTableEvaluator::K;
+  const bool rotates_;
+  std::vector<p3hip_features> feats_;
+  std::vector<K> keys_;
+  std::vector<uint32_t> masks_;
+  std::vector<p3hip_result> out_;
+  std::vector<int> out_sym_;
+  std::vector<char> out_hit_, loaded_;
+  std::unordered_map<std::pair<uint64_t, uint64_t>, std::pair<p3hip_result, int>, KeyedTableEvaluator::PH> table_;
+  uint32_t seen_ = 0, loaded_syms_ = 0;
+  long mask_calls_ = 0, full_masks_ = 0, hits_ = 0, evaluated_ = 0;
+};
+
 }  // namespace
 
 extern "C" {
+// NNInterface with device symmetry (SetDeviceSymmetry) against NNInterface with host rotation, over the evaluator above,
+// on the same positions and the same PRNG seed: `rounds` passes over `positions` random-playout positions, alternately
+// through LoadAndGetInference and the async pair.  keyed != 0: both with the engine-side table (a repeat is a hit).
+// out: {results that differ between the two interfaces (any byte), results that are not the game's own stones, the
+// union of the masks the device interface handed over, the union of the symmetries it loaded features under (1 = only
+// the identity), masks handed over, engine evaluations of the device interface, of the host interface, and after a last
+// pass of root visits under SetRootSymmetryMask(0xFF): root results that are not the game's own stones (the average of
+// eight rotated-back copies of an equivariant evaluation is exact), 0xFF masks handed over}.
+// Returns 1 when the interface refuses device symmetry on an evaluator that has it, or accepts it on one without.
+int p3host_test_nn_device_symmetry(int positions, int rounds, uint64_t seed, int keyed, long out[9]) {
+  auto* dev = new SlotSymmetryEvaluator(4, true);
+  auto* host = new SlotSymmetryEvaluator(4, false);
+  NNInterface nn_dev(1, NNInterface::kTimeoutUs, 0, std::unique_ptr<Evaluator>(dev));
+  NNInterface nn_host(1, NNInterface::kTimeoutUs, 0, std::unique_ptr<Evaluator>(host));
+  if (nn_host.SetDeviceSymmetry(true) || nn_host.device_symmetry()) return 1;
+  if (nn_dev.SetRootSymmetryMask(0xFF)) return 1;   // needs device symmetry
+  if (!nn_dev.SetDeviceSymmetry(true) || !nn_dev.device_symmetry()) return 1;
+  if (nn_dev.SetRootSymmetryMask(256)) return 1;
+  if (keyed && (!nn_dev.EnableDeviceCache(10) || !nn_host.EnableDeviceCache(10))) return 1;
+  Probability setup(seed), pd(seed ^ 0x5bd1e995u), ph(seed ^ 0x5bd1e995u);
+  std::vector<Game> games;
+  std::vector<Color> to_move;
+  for (int g = 0; g < positions; ++g) {
+    Game game(7.5f, true);
+    Color c = kBlack;
+    const int plies = 5 + (int)(RandRange(setup.prng(), 0, 60));
+    for (int m = 0; m < plies && !game.IsGameOver(); ++m) {
+      Loc mv = kPassLoc;
+      for (int tries = 0; tries < 40; ++tries) {
+        const int idx = RandRange(setup.prng(), 0, kNumLocs);
+        if (game.IsValidMove(AsLoc(idx), c)) { mv = AsLoc(idx); break; }
+      }
+      game.PlayMove(mv, c);
+      c = Opp(c);
+    }
+    games.push_back(game);
+    to_move.push_back(c);
+  }
+  long differ = 0, bad = 0;
+  auto eval = [&](NNInterface& nn, Probability& prob, int round, int g) {
+    if (round % 2 == 0) return nn.LoadAndGetInference(0, games[g], to_move[g], prob);
+    nn.LoadEntry(0, 0, games[g], to_move[g], prob);
+    nn.SignalReadyForInference();
+    return nn.FetchEntry(0, 0, games[g], to_move[g]);
+  };
+  for (int round = 0; round < rounds; ++round)
+    for (int g = 0; g < positions; ++g) {
+      const p3hip_result a = eval(nn_dev, pd, round, g), b = eval(nn_host, ph, round, g);
+      if (std::memcmp(&a, &b, sizeof a) != 0) ++differ;
+      for (int i = 0; i < kNumLocs; ++i)
+        if (a.move_logits[i] != (float)games[g].board().at(i) || a.move_probs[i] != a.move_logits[i] ||
+            a.opt_move_probs[i] != a.move_logits[i]) { ++bad; break; }
+    }
+  out[0] = differ; out[1] = bad; out[2] = (long)dev->seen_; out[3] = (long)dev->loaded_syms_; out[4] = dev->mask_calls_;
+  out[5] = dev->evaluated_; out[6] = host->evaluated_;
+  if (!nn_dev.SetRootSymmetryMask(0xFF) || nn_dev.root_symmetry_mask() != 0xFF) return 1;
+  long bad_root = 0;
+  for (int g = 0; g < positions; ++g) {
+    p3hip_result a;
+    if (g % 2 == 0) {
+      a = nn_dev.LoadAndGetInference(0, games[g], to_move[g], pd, /*is_root=*/true);
+    } else {
+      nn_dev.LoadEntry(0, 0, games[g], to_move[g], pd, /*is_root=*/true);
+      nn_dev.SignalReadyForInference();
+      a = nn_dev.FetchEntry(0, 0, games[g], to_move[g]);
+    }
+    for (int i = 0; i < kNumLocs; ++i)
+      if (a.move_logits[i] != (float)games[g].board().at(i)) { ++bad_root; break; }
+  }
+  out[7] = bad_root; out[8] = dev->full_masks_;
+  return 0;
+}
+
 // NNInterface over an engine-side cache (EnableDeviceCache): `rounds` passes over `positions` random-playout
 // positions through LoadAndGetInference (a fresh random symmetry per call) and, every other round, through the
 // async LoadEntry / FetchEntry pair.  Every result, un-rotated by the interface, must show the game's own

@@ -164,6 +164,7 @@ class BatchSearch {
   }
   const Position& eval_pos(int i) const { return *eval_pos_[i]; }
   Color eval_color(int i) const { return eval_color_[i]; }
+  bool eval_is_root(int i) const { return eval_pos_[i] == &root_pos_; }   // evaluation i is the search's root visit
   void Deliver(int i, const p3hip_result& r) { pending_[i] = r; }
   const ParallelSearchResult& result() const { return res_; }
 

@@ -767,6 +767,7 @@ class GumbelSearch {
   void set_bias_cache(BiasCache* cache) { bias_cache_ = cache; }
   const Position* eval_game() const { return eval_game_; }
   Color eval_color() const { return eval_color_; }
+  bool eval_is_root() const { return eval_game_ == &root_pos_; }   // the requested evaluation is the search's root visit
   const GumbelResult& result() const { return res_; }
 
  private:

@@ -127,6 +127,9 @@ struct SelfPlayConfig {       // SPConfig, cc/selfplay/self_play_thread.h:38-61
   int nonroot_var_scale_prior_visits = 10;
   float bias_cache_lambda = 0.0f, bias_cache_alpha = 0.8f;   // --bias_cache_{lambda,alpha} main.cc:58-61 (0 = off)
   bool early_stopping_enabled = false;                       // --early_stopping_enabled main.cc:68
+  // the engine rotates (P3HIP_FLAG_SYMMETRY_SLOT): features go out un-rotated, the request's random symmetry travels as
+  // the slot's mask (GameRunner::BackMask), results come back in the game's orientation
+  bool device_symmetry = false;
   float use_seen_state_prob = 0.5f;       // --use_seen_state_prob     main.cc:48-50
   float sel_mult_base = 0.0f, sel_mult_scale_factor = 1.0f;   // main.cc:51-57
   ForkParams fork_params = ForkParams::ForReuse(0.5f);        // main.cc:191-193
@@ -301,7 +304,7 @@ class GameRunner {
     }
     Request e = std::move(fifo_.front());
     fifo_.pop_front();
-    UnapplySymmetry(e.sym, &r);   // nn_interface.h:263-288
+    if (!cfg_.device_symmetry) UnapplySymmetry(e.sym, &r);   // nn_interface.h:263-288
     cache_.Fill(e.cache_id, r);   // nn_interface.cc:130 (the entry was reserved when the request missed)
     for (Request& w : fifo_)      // requests for the same key made while this one was in flight
       if (w.alias_of == e.cache_id && w.alias_of != 0 && !w.res) w.res.reset(new p3hip_result(r));
@@ -318,6 +321,8 @@ class GameRunner {
   // the request TryAdvance just returned could not be loaded (the batch had gone): it waits, in the scheduler's feature
   // buffer of this game, for the next host phase; nothing else may be requested before it is loaded
   void MarkUnloaded() { unloaded_ = true; }
+  // device symmetry: the mask of the request TryAdvance just returned (still the newest while it waits unloaded)
+  uint32_t BackMask() const { return 1u << (int)fifo_.back().sym; }
   bool unloaded() const { return unloaded_; }
   int FrontSlot(int lane) const {
     return !fifo_.empty() && !fifo_.front().alias_of && fifo_.front().lane == lane ? fifo_.front().slot : -1;
@@ -366,7 +371,7 @@ class GameRunner {
     }
     Request e;
     e.sym = RandomSymmetry(prob_.prng());   // nn_interface.cc:123
-    FillFeatures(pos, c, e.sym, f);
+    FillFeatures(pos, c, cfg_.device_symmetry ? kIdentity : e.sym, f);   // (the draw is the host path's either way)
     ++stats_.evals;
     e.cache_id = cache_.InsertPending(key);
     e.side = side;
@@ -782,6 +787,7 @@ bool g_init_state_sampling = true;
 float g_use_seen_state_prob = 0.5f, g_sel_mult_base = 0.0f, g_sel_mult_scale = 1.0f;
 float g_bias_cache_lambda = 0.0f, g_bias_cache_alpha = 0.8f;
 bool g_early_stopping = false;
+bool g_device_symmetry = false;
 std::string g_calibration_file;
 long g_last_bias_pruned = 0;
 double g_last_bias_adj = 0;
@@ -818,6 +824,10 @@ void p3host_selfplay_set_bias_cache(float lambda, float alpha) {
 void p3host_selfplay_set_calibration_file(const char* path) { g_calibration_file = path ? path : ""; }
 // --early_stopping_enabled of subsequent runs (selfplay/main.cc:68,260; off by default)
 void p3host_selfplay_set_early_stopping(int enabled) { g_early_stopping = enabled != 0; }
+// Subsequent self-play runs over an engine library hand every leaf's random symmetry to the engine (an engine created
+// with P3HIP_FLAG_SYMMETRY_SLOT and as many rows as slots) and neither rotate features nor results on the host; games,
+// records and search results are the host path's.  Off by default; no effect on the null and hash evaluators.
+void p3host_selfplay_set_device_symmetry(int enabled) { g_device_symmetry = enabled != 0; }
 // bias-cache entries pruned / sum of |root adjustment| over the moves of the last run or game
 long p3host_selfplay_last_bias_pruned() { return g_last_bias_pruned; }
 double p3host_selfplay_last_bias_adj() { return g_last_bias_adj; }
@@ -925,6 +935,8 @@ int p3host_selfplay_run(const char* engine_lib, const char* weights, int device,
   cfg.bias_cache_lambda = g_bias_cache_lambda;
   cfg.bias_cache_alpha = g_bias_cache_alpha;
   cfg.early_stopping_enabled = g_early_stopping;
+  const bool dev_sym = g_device_symmetry && engine_lib && engine_lib[0] && std::strcmp(engine_lib, "hash") != 0;
+  cfg.device_symmetry = dev_sym;
   cfg.calibration = ParseCalibrationFile(g_calibration_file);
   cfg.fork_params = ForkParams::ForReuse(g_use_seen_state_prob);
   auto reuse = std::make_unique<ReuseBuffer>(seed ^ 0x676f6578706c6f69ull);
@@ -953,7 +965,9 @@ int p3host_selfplay_run(const char* engine_lib, const char* weights, int device,
       } else {
         auto* e = new HipEvaluator();
         halves[h].lanes[l]->eval.reset(e);
-        if (!e->Open(engine_lib, weights, ng, device, P3HIP_FLAG_SHARED_DEVICE)) {   // one engine per lane, all on this GPU
+        // one engine per lane, all on this GPU (device symmetry: one copy per slot, so as many rows as slots)
+        if (!e->Open(engine_lib, weights, ng, device, P3HIP_FLAG_SHARED_DEVICE | (dev_sym ? P3HIP_FLAG_SYMMETRY_SLOT : 0u),
+                     dev_sym ? ng : 0)) {
           if (err) snprintf(err, 256, "%s", e->err.c_str());
           return 1;
         }
@@ -996,7 +1010,7 @@ int p3host_selfplay_run(const char* engine_lib, const char* weights, int device,
     auto ctl = std::make_shared<PhaseCtl>();
     for (int g = 0; g < cap; ++g) H.settled[g].store(0, std::memory_order_relaxed);
     const long phase_no = H.phase_no++;
-    WorkerPool::JobRef job = pool.Submit(cap, [&H, &L, l, depth, ctl, slow_us, phase_no](int g) {
+    WorkerPool::JobRef job = pool.Submit(cap, [&H, &L, l, depth, ctl, slow_us, phase_no, dev_sym](int g) {
       GameRunner& G = *H.games[g];
       // the request in feats[g] goes into this lane's batch — while the phase is open; after that it waits for the next one
       auto load = [&]() -> bool {
@@ -1005,6 +1019,7 @@ int p3host_selfplay_run(const char* engine_lib, const char* weights, int device,
         if (open) {
           const int slot = L.count.fetch_add(1);
           L.eval->Load(slot, H.feats[g]);
+          if (dev_sym) L.eval->SetSlotSymmetries(slot, G.BackMask());
           G.SetBackSlot(l, slot);
         } else {
           G.MarkUnloaded();
@@ -1051,7 +1066,7 @@ int p3host_selfplay_run(const char* engine_lib, const char* weights, int device,
       // rows left empty (games that wait for a result of the other lane's batch, stragglers handed over) go to games that
       // can start another playout
       std::atomic<int> spare{cap - L.count.load()};
-      pool.ParallelFor(cap, [&H, &L, &spare, l, depth](int g) {
+      pool.ParallelFor(cap, [&H, &L, &spare, l, depth, dev_sym](int g) {
         if (!H.settled[g].load(std::memory_order_acquire)) return;   // a straggler: still at work on the pool
         GameRunner& G = *H.games[g];
         if (G.unloaded()) return;   // a straggler that has just ended with a request: feats[g] holds it for the next phase
@@ -1060,6 +1075,7 @@ int p3host_selfplay_run(const char* engine_lib, const char* weights, int device,
           if (!G.TryAdvance(&H.feats[g], depth)) { spare.fetch_add(1); break; }
           const int slot = L.count.fetch_add(1);
           L.eval->Load(slot, H.feats[g]);
+          if (dev_sym) L.eval->SetSlotSymmetries(slot, G.BackMask());
           G.SetBackSlot(l, slot);
         }
       });
@@ -1502,6 +1518,26 @@ int p3host_test_game_inflight(int default_n, int default_k, int selected_n, int 
 #include "eval_match.h"
 #include "threaded_search.h"
 
+namespace {
+// The engine of an eval player: `flags` (the precision and latency plan of its config, from the caller) plus its
+// symmetry flags, and with nn_device_symmetry / nn_root_symmetry_mask a
+// P3HIP_FLAG_SYMMETRY_SLOT engine of R = slots + 7 x games rows (a game has at most one root in flight; one copy per
+// leaf without a root mask), at most 8 x slots.  False with the message in h->err.
+bool OpenEvalEngine(HipEvaluator* h, const char* engine_lib, const char* weights, int slots, int games, int device,
+                    uint32_t flags, const EvalPlayerConfig& c) {
+  const uint32_t sym_mask = c.nn_symmetry_mask;
+  const bool dev = c.device_symmetry();
+  if (dev && sym_mask) {
+    h->err = "nn_symmetry_mask cannot be combined with nn_device_symmetry / nn_root_symmetry_mask: an engine takes its "
+             "symmetries either from its own mask or slot by slot";
+    return false;
+  }
+  flags |= (sym_mask ? P3HIP_FLAG_SYMMETRY_AVG : 0u) | (dev ? P3HIP_FLAG_SYMMETRY_SLOT : 0u);
+  const int rows = !dev ? 0 : c.nn_root_symmetry_mask ? std::min(8 * slots, slots + 7 * games) : slots;
+  return h->Open(engine_lib, weights, slots, device, flags, rows) && (!sym_mask || h->SetSymmetries(sym_mask));
+}
+}  // namespace
+
 extern "C" {
 
 struct p3host_eval_stats {
@@ -1627,11 +1663,9 @@ int p3host_eval_match(const char* engine_lib, const char* cur_weights, const cha
     } else {
       auto* h = new HipEvaluator();
       ev[e].reset(h);
-      const uint32_t sym_mask = pc[e].nn_symmetry_mask;
-      const uint32_t flags = P3HIP_FLAG_SHARED_DEVICE | (sym_mask ? P3HIP_FLAG_SYMMETRY_AVG : 0u) |   // the two players' passes run concurrently
+      const uint32_t flags = P3HIP_FLAG_SHARED_DEVICE |   // the two players' passes run concurrently
                              (pc[e].nn_fp32 ? P3HIP_FLAG_FP32_ANY : 0u) | (pc[e].nn_low_latency ? P3HIP_FLAG_LOW_LATENCY_ANY : 0u);
-      if (!h->Open(engine_lib, e == 0 ? cur_weights : cand_weights, slots, device, flags) ||
-          (sym_mask && !h->SetSymmetries(sym_mask))) {
+      if (!OpenEvalEngine(h, engine_lib, e == 0 ? cur_weights : cand_weights, slots, num_games, device, flags, pc[e])) {
         if (err) snprintf(err, 256, "%s", h->err.c_str());
         return 1;
       }
@@ -1714,6 +1748,7 @@ int p3host_eval_match(const char* engine_lib, const char* cur_weights, const cha
         } else {
           ev[e]->Load(base[g] + slot_of[g][i], f[slot_of[g][i]]);
         }
+        if (const uint32_t mask = games[g]->eval_mask(i)) ev[e]->SetSlotSymmetries(base[g] + slot_of[g][i], mask);
       }
     });
     bool ok[2] = {true, true};
@@ -1797,17 +1832,21 @@ int p3host_eval_match_threads(const char* engine_lib, const char* cur_weights, c
       ev.reset(h);
       // nn_symmetry_mask: the engine averages every evaluation over those symmetries; the host's random symmetry per
       // leaf and its inverse stay, since the averaged result comes back in the orientation it was loaded in
-      const uint32_t sym_mask = pc[e].nn_symmetry_mask;
-      const uint32_t flags = P3HIP_FLAG_SHARED_DEVICE | (sym_mask ? P3HIP_FLAG_SYMMETRY_AVG : 0u) |
+      // nn_device_symmetry / nn_root_symmetry_mask: the engine rotates, a search's root visit under the root mask
+      const uint32_t flags = P3HIP_FLAG_SHARED_DEVICE |
                              (pc[e].nn_fp32 ? P3HIP_FLAG_FP32_ANY : 0u) | (pc[e].nn_low_latency ? P3HIP_FLAG_LOW_LATENCY_ANY : 0u);
-      if (!h->Open(engine_lib, e == 0 ? cur_weights : cand_weights, batch, device, flags) ||
-          (sym_mask && !h->SetSymmetries(sym_mask))) {
+      if (!OpenEvalEngine(h, engine_lib, e == 0 ? cur_weights : cand_weights, batch, num_games, device, flags, pc[e])) {
         if (err) snprintf(err, 256, "%s", h->err.c_str());
         return 1;
       }
     }
     nn[e].reset(new NNInterface(batch, NNInterface::kTimeoutUs, (size_t)cache_size, std::move(ev),
                                 NNInterface::SignalKind::kExplicit, num_games));
+    if (!use_null && pc[e].device_symmetry() &&
+        (!nn[e]->SetDeviceSymmetry(true) || !nn[e]->SetRootSymmetryMask(pc[e].nn_root_symmetry_mask))) {
+      if (err) snprintf(err, 256, "the engine has no per-slot symmetries (p3hip_set_slot_symmetries)");
+      return 1;
+    }
     const int dc = g_device_nn_cache_log2.load();
     if (dc > 0 && !use_null && !nn[e]->EnableDeviceCache(dc)) {
       if (err) snprintf(err, 256, "the engine has no on-device NN cache (p3hip_cache_enable)");
@@ -1926,6 +1965,17 @@ int p3host_parse_player_symmetry_mask(const char* path, uint32_t* mask, char* er
   std::string e;
   if (!ParsePlayerConfig(path, &c, &e)) { if (err) snprintf(err, 256, "%s", e.c_str()); return 1; }
   *mask = c.nn_symmetry_mask;
+  return 0;
+}
+
+// the nn_device_symmetry and nn_root_symmetry_mask of a player config file (tests): 0 and the values (device_symmetry:
+// what the player gets, the root mask implying it), or 1 with the parser's message
+int p3host_parse_player_device_symmetry(const char* path, int* device_symmetry, uint32_t* root_mask, char* err) {
+  EvalPlayerConfig c;
+  std::string e;
+  if (!ParsePlayerConfig(path, &c, &e)) { if (err) snprintf(err, 256, "%s", e.c_str()); return 1; }
+  *device_symmetry = c.device_symmetry() ? 1 : 0;
+  *root_mask = c.nn_root_symmetry_mask;
   return 0;
 }
 

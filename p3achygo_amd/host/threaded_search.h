@@ -65,7 +65,7 @@ class ThreadedSearch {
     for (auto& x : g_.pending_each_level) x.store(0, std::memory_order_relaxed);
     if (game.IsGameOver()) return Result{};   // not a well-defined search
     if (!root->evaluated) {   // search.cc:781-787
-      slot_.LoadEntry(0, game, color_to_move, probability);
+      slot_.LoadEntry(0, game, color_to_move, probability, /*is_root=*/true);
       slot_.SignalReadyForInference();
       const p3hip_result r = slot_.FetchEntry(0, game, color_to_move);
       EvaluateRoot(r, root, color_to_move);

@@ -238,6 +238,16 @@ def set_calibration_file(path: str = "") -> None:
     L.p3host_selfplay_set_calibration_file(path.encode())
 
 
+def set_device_symmetry(enabled) -> None:
+    """Subsequent self-play runs over an engine library hand every leaf's random symmetry to the engine (an engine
+    created with P3HIP_FLAG_SYMMETRY_SLOT, as many rows as slots) instead of rotating features and results on the
+    host; the games, records and search results are the host path's bit for bit.  Off by default.  An engine library
+    without p3hip_create_rows / p3hip_set_slot_symmetries fails the run with a message."""
+    L = lib()
+    L.p3host_selfplay_set_device_symmetry.argtypes = [C.c_int]
+    L.p3host_selfplay_set_device_symmetry(int(bool(enabled)))
+
+
 def set_early_stopping(enabled: bool) -> None:
     """--early_stopping_enabled of subsequent self-play runs (selfplay/main.cc:68; off by default)."""
     L = lib()
