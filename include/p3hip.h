@@ -135,6 +135,25 @@ typedef struct p3hip_engine p3hip_engine;
                                        the fp16 plan is the fused block kernel, 0.86-0.96x elsewhere (README.md).  p3hip_int8_* as for P3HIP_FLAG_INT8; composes with the flags that does.
                                        p3hip_create returns NULL for a transformer trunk, together with any of the three
                                        other INT8 flags, and together with P3HIP_FLAG_FP32 / P3HIP_FLAG_FP32_TFM */
+#define P3HIP_FLAG_INT8_CONV3 32768u /* calibrated INT8 for the 3x3 convs of the layer-wise blocks only: each layer runs on the
+                                       kernel that wins for it ("INT8 for the 3x3 convs only").  Every
+                                       1x1 conv, the stem, the broadcast blocks, the heads and the raw residual streams are
+                                       the fp16 engine's; a tensor between two layers is int8 when its consumer is a 3x3
+                                       conv and fp16 otherwise.  Served: every conv trunk of P3HIP_CONV_SET whose fp16 plan
+                                       runs layer by layer: (384, 192) btl / nbt and every padded or runtime width (with
+                                       P3HIP_CONV_ANY=1 the templated shapes run on the runtime-width kernels, same bits).
+                                       The quantized tensors are the inputs of the 3x3 convs: the inner layers of a btl
+                                       block, 4 per nbt block.  A classic trunk has only 3x3 convs: its plan is
+                                       P3HIP_FLAG_INT8's (C = 192) or P3HIP_FLAG_INT8_ANY's, bit for bit.  p3hip_int8_* as
+                                       for P3HIP_FLAG_INT8; composes with the flags that does.  p3hip_create returns NULL
+                                       for a transformer trunk, for the (256, 128) and (128, 64) btl / nbt trunks (their
+                                       fp16 plan is the fused block kernel: P3HIP_FLAG_INT8_FUSED, P3HIP_FLAG_INT8_C128 and
+                                       P3HIP_FLAG_INT8_ANY serve them), together with any other INT8 flag, with
+                                       P3HIP_FLAG_FP32 / P3HIP_FLAG_FP32_TFM and with either low-latency flag.
+                                       Measured on one MI355X, engine only, legs interleaved with fp16 (README.md, DESIGN.md
+                                       section 9): 0.84x of fp16's forward time on b14c384btl3 at batch 1024 (12.31 against
+                                       14.64 ms), 0.87-0.90x on b10c384nbt, b14c320btl3 and b10c512nbt, 0.99x on b12c192btl3;
+                                       0.91-1.00x at batch 256 */
 #define P3HIP_FLAG_SYMMETRY_AVG 32u /* every slot a run evaluates is evaluated under each symmetry of the engine's set
                                        (default: all eight) and the results averaged on the device, rotated back into the
                                        orientation the slot was loaded in.  Needs 8 x batch_size <= 65536.  See

@@ -806,6 +806,7 @@ double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
     case Path::ConvAny:
     case Path::Split:
     case Path::Int8Any:
+    case Path::Int8Conv3:
     case Path::Int8:
     case Path::Layerwise: {
       // the runtime-width kernels: the file's own width, not the padded one the kernel runs; the templated: the layer's

@@ -11,6 +11,7 @@
 #include "conv_split.h"
 #include "edge_split.h"
 #include "engine.h"
+#include "lconv_conv3.h"
 #include "lconv_i8.h"
 #include "transformer.h"
 #include "transformer_f32.h"
@@ -239,7 +240,7 @@ bool timed_launch(p3hip_engine* e, int* timed, Launch&& launch) {
 
 // a 1x1 conv of the k_conv1x1 family: 0 conv_first, 1 conv_last of a broadcast block, 2 the head convs
 hipError_t launch_conv1x1(const p3hip_engine* e, int which, const p3::Conv1x1Args& a) {
-  return runs_conv_any(e->trunk_path()) ? p3::launch_conv1x1_any(e->wf.C, which, a, e->n_cu, e->stream)
+  return runs_conv_any(e->plan.choice) ? p3::launch_conv1x1_any(e->wf.C, which, a, e->n_cu, e->stream)
                                     : p3::launch_conv1x1(e->wf.C, which, a, e->n_cu, e->stream);
 }
 
@@ -261,7 +262,7 @@ bool enqueue_stem(p3hip_engine* e, const Pass& p) {
     edge_split_of(e, p.npos, &stem, &dense, &heads);
     if (stem > 1) return e->check(p3::launch_init_split(C, a, stem, e->n_cu, e->stream), "launch k_init_split");
   }
-  return e->check(runs_conv_any(e->trunk_path()) ? p3::launch_init_any(C, a, grid_for(e, p.npos, 1), e->stream)
+  return e->check(runs_conv_any(e->plan.choice) ? p3::launch_init_any(C, a, grid_for(e, p.npos, 1), e->stream)
                                              : p3::launch_init(C, a, grid_for(e, p.npos, 1), e->stream), "launch k_init");
 }
 
@@ -324,7 +325,8 @@ void fill_layer(const p3hip_engine* e, Args& a, const LayerPlan& lp, const Regio
 // The conv of one LayerPlan through the kernel the engine's state selects (layer_kernel).  `what`: the name e->check
 // reports a failed launch under, the kernel's own by default
 bool launch_layer(p3hip_engine* e, const Pass& p, const LayerPlan& lp, const char* what = nullptr) {
-  const LayerKernel k = layer_kernel(e);
+  const LayerKernel k = layer_kernel(e, lp.kw);
+  const bool conv3 = e->trunk_path() == Path::Int8Conv3;
   switch (k) {
     case LayerKernel::LconvF32: {
       p3::LConvF32Args a{};
@@ -348,6 +350,10 @@ bool launch_layer(p3hip_engine* e, const Pass& p, const LayerPlan& lp, const cha
       fill_layer(e, a, lp, Regions<_Float16>(e), p.npos);
       a.w = e->dev<int8_t>(lp.q_off); a.w_scale = e->dev<float>(lp.qs_off);
       a.act_scale = e->d_ascale; a.in_scale = lp.qidx; a.out_scale = lp.qidx + 1;
+      // Int8Conv3: the consumer of the last 3x3's activated output is the fp16 1x1 expand
+      if (conv3 && lp.out_qidx < 0)
+        return e->check(p3::launch_lconv_i8_f16(k == LayerKernel::LconvI8Any, lp.kw, lp.cin, lp.cout, a, e->stream),
+                        what ? what : "launch k_lconv_i8_f16");
       return k == LayerKernel::LconvI8Any
                  ? e->check(p3::launch_lconv_i8_any(lp.kw, lp.cin, lp.cout, a, e->stream), what ? what : "launch k_lconv_i8_any")
                  : e->check(p3::launch_lconv_i8(lp.kw, lp.cin, lp.cout, a, e->stream), what ? what : "launch k_lconv_i8");
@@ -357,6 +363,10 @@ bool launch_layer(p3hip_engine* e, const Pass& p, const LayerPlan& lp, const cha
       p3::LConvArgs a{};
       fill_layer(e, a, lp, Regions<_Float16>(e), p.npos);
       a.wstream = e->d_arena + lp.w_off; a.nms_total = lp.nms;
+      // Int8Conv3: the consumer of the 1x1 reduce's activated output is the first int8 3x3 (calibration: the fp16 plan)
+      if (conv3 && lp.out_qidx >= 0 && !e->calibrating)
+        return e->check(p3::launch_lconv_q8(k == LayerKernel::LconvAny, lp.kw, lp.cin, lp.cout, a, e->d_ascale, lp.out_qidx,
+                                            e->n_cu, e->stream), what ? what : "launch k_lconv_q8");
       return k == LayerKernel::LconvAny
                  ? e->check(p3::launch_lconv_any(lp.kw, lp.cin, lp.cout, a, e->n_cu, e->stream), what ? what : "launch k_lconv_any")
                  : e->check(p3::launch_lconv(lp.kw, lp.cin, lp.cout, a, e->n_cu, e->stream), what ? what : "launch k_lconv");
@@ -369,7 +379,7 @@ bool launch_layer(p3hip_engine* e, const Pass& p, const LayerPlan& lp, const cha
 // paths are the fp16 plan + absmax
 bool enqueue_layerwise_block(p3hip_engine* e, const Pass& p, const BlockPlan& bp) {
   for (const LayerPlan& lp : bp.layers) {
-    if (e->calibrating) {
+    if (e->calibrating && lp.qidx >= 0) {
       // MinMax calibration: the absmax of this conv's quantized input, the activated tensor (pre: mish(bn0(x)),
       // which the fp16 plan never stores) folded into the running maximum
       p3::AbsmaxArgs m{};
@@ -423,7 +433,7 @@ bool enqueue_broadcast_block(p3hip_engine* e, const Pass& p, const BlockPlan& bp
   if (!bp.first_fused && !e->check(launch_conv1x1(e, 0, c0), "launch conv_first")) return false;
   const p3::BDenseArgs d = bdense_args(e, bp, npos);
   if (!(bp.first_fused && bp.dense_fused) &&
-      !e->check(runs_conv_any(e->trunk_path()) ? p3::launch_bdense_any(C, d, grid_for(e, npos, 1), e->stream)
+      !e->check(runs_conv_any(e->plan.choice) ? p3::launch_bdense_any(C, d, grid_for(e, npos, 1), e->stream)
                                            : p3::launch_bdense(C, d, grid_for(e, npos, 1), e->stream), "launch bdense")) return false;
   p3::Conv1x1Args c1{};
   c1.in = e->d_u; c1.out16 = e->d_x; c1.npos = npos;
@@ -547,12 +557,19 @@ void edge_split_of(const p3hip_engine* e, int npos, int* stem, int* dense, int* 
 // The kernel of the layer convs: the path's, and on the INT8 paths while they calibrate the fp16 plan's.  (The fused INT8
 // paths run whole blocks, enqueue_block_i8, once calibrated; Int8Fused128 calibrates through the runtime-width kernel:
 // k_lconv has no C = 128 / C_b = 64 instantiations)
-LayerKernel layer_kernel(const p3hip_engine* e) {
+// Int8Conv3 decides per layer: a 3x3 conv the INT8 kernel, a 1x1 conv (and every conv while calibrating) the fp16 kernel,
+// templated or runtime-width as the trunk's fp16 plan
+LayerKernel layer_kernel(const p3hip_engine* e, int kw) {
   const Path path = e->trunk_path();
+  if (path == Path::Int8Conv3) {
+    const bool any = e->plan.choice.any_width;
+    if (kw == 3 && !e->calibrating) return any ? LayerKernel::LconvI8Any : LayerKernel::LconvI8;
+    return any ? LayerKernel::LconvAny : LayerKernel::Lconv;
+  }
   if (path == Path::F32Conv) return LayerKernel::LconvF32;
   if (path == Path::Split) return LayerKernel::Sconv;
   if (is_int8(path) && !e->calibrating) return path == Path::Int8Any ? LayerKernel::LconvI8Any : LayerKernel::LconvI8;
-  return runs_conv_any(path) || path == Path::Int8Fused128 ? LayerKernel::LconvAny : LayerKernel::Lconv;
+  return runs_conv_any(e->plan.choice) || path == Path::Int8Fused128 ? LayerKernel::LconvAny : LayerKernel::Lconv;
 }
 
 const char* layer_kernel_name(LayerKernel k, int kw, int cin, int cout) {

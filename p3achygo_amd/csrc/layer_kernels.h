@@ -268,9 +268,14 @@ __device__ __forceinline__ void conv1x1_body(Conv1x1Args a, WI wi, WO wo) {
 // 256-thread workgroup per position — 1x1: 52 KB of activations + 24 KB of ring, 3x3: 60.6 KB + 12 KB (K = 32 ring
 // steps) — so that TWO workgroups share a CU and one's loads, stores and BN + mish run under the other's K loop;
 // they take turns at the higher wave priority, one position group each (see BlockArgs::pair_turns).
-template <int KW, bool PRE, bool ACT, bool RES, bool DUAL, int NW, class WI, class WO>
-__device__ __forceinline__ void lconv_body(LConvArgs a, WI wi, WO wo) {
+//   Q   : how the activated tensor (act, or dual's second output) is stored.  FpOut: as fp16, the fp16 plans.  A policy
+//         with `on` set (lconv_conv3.hip Q8Out, P3HIP_FLAG_INT8_CONV3) stores it quantized, from the fp32 values, in
+//         the int8 layout the INT8 3x3 conv reads; dual's raw output stays fp16
+struct FpOut { static constexpr bool on = false; };
+template <int KW, bool PRE, bool ACT, bool RES, bool DUAL, int NW, class Q = FpOut, class WI, class WO>
+__device__ __forceinline__ void lconv_body(LConvArgs a, WI wi, WO wo, Q q = Q{}) {
   static_assert(!(ACT && DUAL), "act stores the activated tensor only, dual stores both");
+  static_assert(!Q::on || (NW == 4 && (ACT || DUAL) && !(ACT && RES)), "a quantized output is an activated one");
   constexpr int CB = 64, NPOS = NW == 8 ? 2 : 1, CP = 64;
   // 3x3 layers in the 4-wave form: K = 32 ring steps (60.6 KB of activations + 12 KB of ring), as in k_block
   using G = Geo<NPOS, CB, KW, NW, (NW == 4 && KW == 3) ? 2 : kKMS>;
@@ -337,7 +342,16 @@ __device__ __forceinline__ void lconv_body(LConvArgs a, WI wi, WO wo) {
       }
       epilogue_store<G, CP, false, T::NT>(acc, rr, a.out);    // raw y
       activate();
-      epilogue_store<G, CP, false, T::NT>(acc, rr, a.out2);   // the consumer's input, activated once here
+      if constexpr (Q::on) {
+        q.template store<G, CP, T::NT>(acc, a.out2, COUT, pos0, cp * CP);   // 24 four-byte stores
+        pending_stores = 36;
+      } else {
+        epilogue_store<G, CP, false, T::NT>(acc, rr, a.out2);   // the consumer's input, activated once here
+        pending_stores = 24;
+      }
+    } else if constexpr (Q::on) {
+      activate();
+      q.template store<G, CP, T::NT>(acc, a.out, COUT, pos0, cp * CP);
       pending_stores = 24;
     } else {
       pending_stores = 12;

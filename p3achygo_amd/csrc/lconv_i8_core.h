@@ -67,7 +67,9 @@ __device__ __forceinline__ i32x4 stage_pre(const h8& lo, const h8& hi, const flo
 // FixedW all three fold to the constants the templated kernel always had, with RuntimeW they are registers.  The LDS
 // image (two slices) depends on neither.  One slice (CIN = 64): nothing is prefetched and image 0 alone is read; image
 // s & 1 is never read before stage_store(s) and the barrier behind it.
-template <int KW, class WI, class WO, bool PRE, bool ACT, bool RES, bool DUAL>
+// OUT16 (lconv_conv3.hip, P3HIP_FLAG_INT8_CONV3: the consumer is an fp16 1x1 conv): the activated tensor goes out as fp16
+// in the fp16 layout, (_Float16) mish(bn_out(y)), the fp16 plan's own rounding point, and no output scale is read.
+template <int KW, class WI, class WO, bool PRE, bool ACT, bool RES, bool DUAL, bool OUT16 = false>
 __device__ __forceinline__ void lconv_i8_body(LConvI8Args a, WI wi, WO wo) {
   static_assert(!(ACT && (RES || DUAL)), "act stores the activated tensor only");
   if constexpr (WI::fixed && WO::fixed)
@@ -161,7 +163,7 @@ __device__ __forceinline__ void lconv_i8_body(LConvI8Args a, WI wi, WO wo) {
   }
 
   // epilogue: lane holds output channels c0 + r (r = 0..3) of board point loc, for every (tile, cout tile)
-  const float s_out = (ACT || DUAL) ? a.act_scale[a.out_scale] : 0.0f;
+  const float s_out = (!OUT16 && (ACT || DUAL)) ? a.act_scale[a.out_scale] : 0.0f;
 #pragma unroll
   for (int ct = 0; ct < 4; ++ct) {
     const int c0 = cp * 64 + ct * 16 + 4 * g;
@@ -187,7 +189,12 @@ __device__ __forceinline__ void lconv_i8_body(LConvI8Args a, WI wi, WO wo) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] += (float)old[r];
       }
-      if (ACT || DUAL) {
+      if constexpr (OUT16 && (ACT || DUAL)) {
+        h4 o;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[r] = (_Float16)mish_f(v[r] * sc[r] + sh[r]);
+        *(h4*)((_Float16*)(ACT ? a.out : (void*)a.out2) + o16) = o;
+      } else if (ACT || DUAL) {
         unsigned u = 0;
 #pragma unroll
         for (int r = 0; r < 4; ++r) u |= q8(mish_f(v[r] * sc[r] + sh[r]), s_out) << (8 * r);

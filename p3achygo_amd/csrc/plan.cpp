@@ -75,6 +75,7 @@ const char* path_name(Path p) {
     case Path::Int8Fused256: return "Int8Fused256";
     case Path::Int8Fused128: return "Int8Fused128";
     case Path::Int8Any: return "Int8Any";
+    case Path::Int8Conv3: return "Int8Conv3";
     case Path::F32Conv: return "F32Conv";
     case Path::Split: return "Split";
     case Path::Tfm: return "Tfm";
@@ -103,6 +104,7 @@ struct TrunkClass {
   bool in_set = false;     // a conv trunk of P3HIP_CONV_SET (a k_block or k_lconv shape with a broadcast block at every
                            // position is none, and runs all the same)
   bool hv_ok = false;      // H = 32 and V in {32, 48, 64, 80}
+  bool classic = false;    // classic blocks: 3x3 convs only
 };
 
 TrunkClass classify(const WeightFile& wf) {
@@ -110,6 +112,7 @@ TrunkClass classify(const WeightFile& wf) {
   TrunkClass t;
   t.tfm_file = wf.btype == 3;
   t.btl123 = wf.btype == 0 && wf.inner >= 1 && wf.inner <= 3;
+  t.classic = wf.btype == 2;
   t.in_set = WeightFile::conv_set(wf.model_C, wf.model_Cb, wf.btype, wf.inner, wf.bint) && C % 64 == 0 &&
              (wf.btype == 2 || Cb % 64 == 0);
   t.hv_ok = wf.H == 32 && (wf.V == 32 || wf.V == 48 || wf.V == 64 || wf.V == 80);
@@ -129,8 +132,9 @@ TrunkClass classify(const WeightFile& wf) {
 
 // What the precision flags ask for: one plan
 struct Request {
-  enum Kind { Fp16, Int8, Int8Fused, Int8C128, Int8Any, Fp32, LowLatency, LowLatencyTfm } kind = Fp16;
+  enum Kind { Fp16, Int8, Int8Fused, Int8C128, Int8Any, Int8Conv3, Fp32, LowLatency, LowLatencyTfm } kind = Fp16;
   bool int8_any = false;   // P3HIP_FLAG_INT8_ANY was given (kind is the plan it chose)
+  bool int8_conv3 = false;   // P3HIP_FLAG_INT8_CONV3 was given (a classic trunk: kind is Int8 or Int8Any, its whole plan)
   bool alone = true;       // Int8Fused, Int8C128: no other of the three INT8 flags beside it
   bool f32_conv = false, f32_tfm = false;   // Fp32: P3HIP_FLAG_FP32 serves the conv trunks, P3HIP_FLAG_FP32_TFM the
                                             // transformers; both together: whatever the trunk
@@ -155,7 +159,21 @@ Request read_request(uint32_t flags, const TrunkClass& t, int C, const Options& 
   Request r;
   r.f32_conv = (flags & P3HIP_FLAG_FP32) != 0;
   r.f32_tfm = (flags & P3HIP_FLAG_FP32_TFM) != 0;
-  if (flags & P3HIP_FLAG_LOW_LATENCY) {
+  if (flags & P3HIP_FLAG_INT8_CONV3) {
+    // (a flag set with this flag in it is this flag's to answer: it was added last, and the answers of every set without
+    // it stay what they were)
+    r.int8_conv3 = true;
+    r.kind = !t.classic ? Request::Int8Conv3 : (t.trunk == Trunk::LconvShape && !opt.conv_any) ? Request::Int8 : Request::Int8Any;
+    if (i8_three || (flags & P3HIP_FLAG_INT8_ANY))
+      r.clash = "P3HIP_FLAG_INT8_CONV3 cannot be combined with P3HIP_FLAG_INT8, P3HIP_FLAG_INT8_FUSED, P3HIP_FLAG_INT8_C128 or "
+                "P3HIP_FLAG_INT8_ANY: an engine runs one INT8 plan";
+    else if (fp32_flag)
+      r.clash = "P3HIP_FLAG_INT8_CONV3 cannot be combined with P3HIP_FLAG_FP32 or P3HIP_FLAG_FP32_TFM: an engine runs one "
+                "precision plan";
+    else if (flags & (P3HIP_FLAG_LOW_LATENCY | P3HIP_FLAG_LOW_LATENCY_TFM))
+      r.clash = "P3HIP_FLAG_INT8_CONV3 cannot be combined with P3HIP_FLAG_LOW_LATENCY or P3HIP_FLAG_LOW_LATENCY_TFM: their "
+                "kernels run in fp16";
+  } else if (flags & P3HIP_FLAG_LOW_LATENCY) {
     r.kind = Request::LowLatency;
     r.ll_tfm = (flags & P3HIP_FLAG_LOW_LATENCY_TFM) != 0;
     if (i8_three || (flags & P3HIP_FLAG_INT8_ANY))
@@ -203,6 +221,7 @@ Path path_of(const Request& r, const TrunkClass& t, const WeightFile& wf, const 
     case Request::Fp32: return Path::F32Conv;
     case Request::LowLatency: return Path::Split;
     case Request::Int8Any: return Path::Int8Any;
+    case Request::Int8Conv3: return Path::Int8Conv3;
     case Request::Int8Fused: return Path::Int8Fused256;
     case Request::Int8C128: return Path::Int8Fused128;
     case Request::Int8: return Path::Int8;
@@ -234,6 +253,9 @@ PlanChoice choose_plan(const WeightFile& wf, uint32_t flags, const Options& opt,
       {k == Request::LowLatencyTfm && !t.tfm_file,
        "P3HIP_FLAG_LOW_LATENCY_TFM serves the transformer trunks only (" P3HIP_TRANSFORMER_SET "); the conv trunks have "
        "P3HIP_FLAG_LOW_LATENCY"},
+      {r.int8_conv3 && t.tfm_file,
+       "P3HIP_FLAG_INT8_CONV3 serves the conv trunks (" P3HIP_CONV_SET ") whose fp16 plan runs layer by layer; the "
+       "transformer trunks (" P3HIP_TRANSFORMER_SET ") have no INT8 plan"},
       {r.int8_any && t.tfm_file,
        "P3HIP_FLAG_INT8_ANY serves the conv trunks (" P3HIP_CONV_SET "); the transformer trunks (" P3HIP_TRANSFORMER_SET
        ") have no INT8 plan"},
@@ -260,6 +282,10 @@ PlanChoice choose_plan(const WeightFile& wf, uint32_t flags, const Options& opt,
        "unsupported architecture for the HIP engine (need a conv trunk (" P3HIP_CONV_SET "), or a transformer "
        "trunk (" P3HIP_TRANSFORMER_SET "); H=32, V in {32,48,64,80} (transformer: V in {32,48,64}, and 80 at "
        "d > 256))"},
+      {r.int8_conv3 && tr == Trunk::BlockShape,
+       "P3HIP_FLAG_INT8_CONV3 serves the trunks whose fp16 plan runs layer by layer; the C = 256 / C_b = 128 and C = 128 / "
+       "C_b = 64 btl and nbt trunks run the fused block kernel, which no layer-wise plan approaches: P3HIP_FLAG_INT8_FUSED, "
+       "P3HIP_FLAG_INT8_C128 and P3HIP_FLAG_INT8_ANY serve them"},
       // (INT8_C128 answers every trunk it does not serve with its own message, the runtime-width conv trunks included)
       {k == Request::Int8C128 && !(r.alone && tr == Trunk::BlockShape && C == 128 && t.btl123),
        "INT8_C128 is available only for C = 128 / C_b = 64 trunks of btl blocks with 1, 2 or 3 inner layers "
@@ -285,12 +311,13 @@ PlanChoice choose_plan(const WeightFile& wf, uint32_t flags, const Options& opt,
       return c;
     }
   c.path = path_of(r, t, wf, opt);
+  c.any_width = c.path == Path::Int8Conv3 && (tr == Trunk::OtherConv || opt.conv_any);
   // (layer-wise: p3::conv_any_slice(C) = 64 at classic C = 192 and at INT8_C128's C = 128, 128 at C = 384 and at
   // INT8_FUSED's C = 256)
   c.CB = is_layerwise(c.path) ? p3::conv_any_slice(C) : (is_tfm(c.path) ? 128 : Cb);
   c.CPI = is_layerwise(c.path) ? p3::conv_any_init_pass(C) : 128;
   c.heads_image = !is_f32(c.path) && p3::heads_fusable(C, wf.V);
-  c.heads_fused = c.heads_image && opt.heads_fuse && !runs_conv_any(c.path);
+  c.heads_fused = c.heads_image && opt.heads_fuse && !runs_conv_any(c);
   if (is_tfm(c.path)) {
     c.tfm_heads = Cb;
     c.tfm_D = wf.model_C / Cb;
@@ -642,7 +669,7 @@ void pack_layerwise_block(Builder& b, int i) {
     LayerPlan lp{kw, cin, cout, pre, act ? 1 : 0, res, dual, pre_bn, out_bn, in_buf, out_buf, out2_buf};
     const float* W = conv_w(wf, i, j, kw, cin, cout);
     lp.w_off = add_conv_image(b, W, kw, cin, cout, cin, cout, true, 64, 64, &lp.nms);
-    if (is_int8(path)) {
+    if (is_int8(path) && (path != Path::Int8Conv3 || kw == 3)) {
       std::vector<int8_t> q;
       std::vector<float> sw;
       p3::pack_lconv_i8(q, sw, W, kw * kw, cin, cout);
@@ -673,6 +700,11 @@ void pack_layerwise_block(Builder& b, int i) {
     add_layer(4, 3, Cb, Cb, false, none, false, true, true, bp.bn[5], 3, 1, 2);             // t'', act5(t'')
     add_layer(5, 1, Cb, C, false, none, false, true, next_layerwise, next_bn0, 2, 0, 3);
   }
+  // Int8Conv3: the activated output of layer j (act, or dual's second tensor) is the input of layer j + 1 of the block,
+  // stored as int8 when that is a 3x3 conv; the last layer's goes to the next block's 1x1 reduce, in fp16
+  if (path == Path::Int8Conv3)
+    for (size_t j = 0; j + 1 < bp.layers.size(); ++j)
+      if (bp.layers[j].act == 1 || bp.layers[j].dual) bp.layers[j].out_qidx = bp.layers[j + 1].qidx;
   b.have_xa = next_layerwise;
   b.plan.blocks.push_back(bp);
 }

@@ -64,6 +64,9 @@ enum class Path {
   Int8Fused128,   // P3HIP_FLAG_INT8_C128: the same at C = 128 / C_b = 64 (block_i8_c128.hip)
   Int8Any,        // P3HIP_FLAG_INT8_ANY on every trunk the three above do not serve: k_lconv_i8_any, widths as launch
                   // arguments; stem, broadcast blocks and heads as ConvAny's
+  Int8Conv3,      // P3HIP_FLAG_INT8_CONV3 on the btl / nbt trunks whose fp16 plan is Layerwise or ConvAny: that plan's layers,
+                  // the 3x3 convs through k_lconv_i8 / k_lconv_i8_any, everything else in fp16 (PlanChoice::any_width: the
+                  // runtime-width kernels).  A classic trunk has only 3x3 convs and takes Int8 / Int8Any itself
   F32Conv,        // P3HIP_FLAG_FP32: every conv trunk layer by layer through conv_f32.hip
   Split,          // P3HIP_FLAG_LOW_LATENCY: every conv trunk layer by layer through k_sconv (conv_split.hip), a position
                   // split across workgroups; stem, broadcast dense and heads as ConvAny's
@@ -76,10 +79,7 @@ inline bool is_tfm(Path p) { return p == Path::Tfm || p == Path::TfmF32 || p == 
 inline bool is_f32(Path p) { return p == Path::F32Conv || p == Path::TfmF32; }
 inline bool is_int8_fused(Path p) { return p == Path::Int8Fused256 || p == Path::Int8Fused128; }
 // (an INT8 engine calibrates through the fp16 layer-wise plan: `calibrating` is a run-time state of the engine)
-inline bool is_int8(Path p) { return p == Path::Int8 || p == Path::Int8Any || is_int8_fused(p); }
-// the stem, the broadcast blocks, the head convs and the fp16 layer convs (calibration) through conv_any.hip
-// (Split: all of these but the layer convs and the broadcast blocks' two 1x1 convs, which run through k_sconv)
-inline bool runs_conv_any(Path p) { return p == Path::ConvAny || p == Path::Int8Any || p == Path::Split; }
+inline bool is_int8(Path p) { return p == Path::Int8 || p == Path::Int8Any || p == Path::Int8Conv3 || is_int8_fused(p); }
 // conv blocks planned conv by conv (BlockPlan kind 4)
 inline bool is_layerwise(Path p) {
   return p == Path::Layerwise || p == Path::ConvAny || is_int8(p) || p == Path::F32Conv || p == Path::Split;
@@ -93,7 +93,13 @@ struct PlanChoice {
   bool heads_image = false;   // the arena holds k_headsx's weight fragments and tensor image (C <= 256, fp16)
   bool heads_fused = false;   // k_headsx runs: the head convs inside the heads kernel (P3HIP_NO_HFUSE, conv_any clear it)
   int tfm_heads = 0, tfm_D = 0;   // transformer: head count and head width (model width wf.model_C = heads x D)
+  bool any_width = false;   // Int8Conv3: the fp16 plan of this trunk is ConvAny's (a padded or runtime width, P3HIP_CONV_ANY=1)
 };
+// the stem, the broadcast blocks, the head convs and the fp16 layer convs (calibration) through conv_any.hip
+// (Split: all of these but the layer convs and the broadcast blocks' two 1x1 convs, which run through k_sconv)
+inline bool runs_conv_any(const PlanChoice& c) {
+  return c.path == Path::ConvAny || c.path == Path::Int8Any || c.path == Path::Split || (c.path == Path::Int8Conv3 && c.any_width);
+}
 
 const char* path_name(Path p);   // "Fused", "Int8Any", ..: the enumerator's name (p3hip_debug_plan)
 
@@ -131,9 +137,11 @@ struct LayerPlan {
   size_t w_off = 0;
   int nms = 0;
   // INT8 paths: the quantized weights (lconv_i8.h pack_lconv_i8), their per-output-channel scales, and the index of
-  // this layer's input among the engine's quantized tensors (its output, when quantized, is the next one: its consumer)
+  // this layer's input among the engine's quantized tensors (its output, when quantized, is the next one: its consumer).
+  // Int8Conv3: on the 3x3 layers only; a 1x1 layer in front of one quantizes its output for it
   size_t q_off = 0, qs_off = 0;
   int qidx = -1;
+  int out_qidx = -1;   // Int8Conv3: the consumer's qidx where this layer stores its activated output as int8, else -1 (fp16)
 };
 
 // One transformer block (kind 5): arena offsets of its tensors, the GEMM weights as MFMA A fragments (transformer.h)

@@ -155,7 +155,7 @@ def score_chunks(engine, paths: Iterable[str], max_batches: int | None = 1001) -
 
 
 def calibrate_from_chunks(engine, paths: Iterable[str], max_batches: int | None = None) -> int:
-    """MinMax calibration of an INT8 engine (any of FLAG_INT8, FLAG_INT8_FUSED, FLAG_INT8_C128, FLAG_INT8_ANY) on the
+    """MinMax calibration of an INT8 engine (any of FLAG_INT8, FLAG_INT8_FUSED, FLAG_INT8_C128, FLAG_INT8_ANY, FLAG_INT8_CONV3) on the
     positions of recorded chunks: one p3hip_int8_calibrate per batch of engine.batch_size rows.  Returns the number of
     calibration batches."""
     nb = prev = 0

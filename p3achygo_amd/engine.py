@@ -48,6 +48,8 @@ FLAG_INT8_FUSED = 64   # calibrated INT8 of the C = 256 btl trunks, one fused in
 FLAG_INT8_C128 = 128   # the same for the C = 128 / C_b = 64 btl trunks (b12c128btl3): k_block_i8<128,64>, two workgroups per CU
 FLAG_INT8_ANY = 2048   # calibrated INT8 whatever the conv trunk: the plan of one of the three flags above where one serves it,
 # else layer by layer on k_lconv_i8_any at the padded widths (include/p3hip.h, DESIGN.md section 9 "INT8 at any width")
+FLAG_INT8_CONV3 = 32768   # calibrated INT8 for the 3x3 convs of the layer-wise blocks only, every 1x1 conv in fp16 (include/p3hip.h,
+# DESIGN.md section 9 "INT8 for the 3x3 convs only"); a classic trunk takes FLAG_INT8's / FLAG_INT8_ANY's plan
 FLAG_FP32 = 256   # the conv trunks layer by layer in fp32, weights and activations included
 FLAG_FP32_TFM = 512   # the transformer trunks in fp32, weights and activations included
 FLAG_FP32_ANY = FLAG_FP32 | FLAG_FP32_TFM   # full precision whatever the trunk

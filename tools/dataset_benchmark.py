@@ -8,7 +8,7 @@ plan to profiles/dataset_benchmark.jsonl.
 
 WEIGHTS is a .p3w file, or the name of a net of p3achygo_amd.netspec.CONFIGS (random-init weights: the timing is real, the
 accuracy figures mean nothing; this tool is for trained nets).  Plans: fp16, fp32, int8 (the INT8 plan that serves the
-trunk: the shape's own flag, else P3HIP_FLAG_INT8_ANY), or int8_lw / int8_fused / int8_c128 / int8_any by name.  INT8
+trunk: the shape's own flag, else P3HIP_FLAG_INT8_ANY), or int8_lw / int8_fused / int8_c128 / int8_any / int8_conv3 by name.  INT8
 plans are calibrated from the --calibrate chunks through
 dataset.calibrate_from_chunks (default: the scored chunks themselves, which flatters them).  --host-scoring scores through
 p3hip_get_slot and the numpy restatement (dataset.host_score) instead of p3hip_score.  --ab REPS runs both ways REPS
@@ -36,7 +36,7 @@ from p3achygo_amd import dataset, engine, netspec  # noqa: E402
 PLAN_FLAGS = {"fp16": (0,), "fp32": (engine.FLAG_FP32_ANY,),
               "int8": (engine.FLAG_INT8_FUSED, engine.FLAG_INT8_C128, engine.FLAG_INT8, engine.FLAG_INT8_ANY),
               "int8_lw": (engine.FLAG_INT8,), "int8_fused": (engine.FLAG_INT8_FUSED,), "int8_c128": (engine.FLAG_INT8_C128,),
-              "int8_any": (engine.FLAG_INT8_ANY,)}
+              "int8_any": (engine.FLAG_INT8_ANY,), "int8_conv3": (engine.FLAG_INT8_CONV3,)}
 
 
 def create(path, batch, plan, extra=0):

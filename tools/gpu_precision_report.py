@@ -4,7 +4,8 @@ reference's cc/nn/engine/scripts/compare_engines.cc.
 For one net and N positions of features.random_positions, runs the fp32 engine (P3HIP_FLAG_FP32_ANY: the fp32 plan of
 the net's trunk, conv or transformer; a transformer's only other plan is fp16), the fp16 engine and
 every INT8 plan that serves the net (P3HIP_FLAG_INT8, _INT8_FUSED, _INT8_C128: the ones p3hip_create accepts, calibrated
-on the same positions; where none of the three does, P3HIP_FLAG_INT8_ANY's own layer-wise plan, row "int8_any"), and prints one JSON line per plan: its largest and mean deviation from the fp32 engine in the raw
+on the same positions; where none of the three does, P3HIP_FLAG_INT8_ANY's own layer-wise plan, row "int8_any"; P3HIP_FLAG_INT8_CONV3 where it
+has a plan of its own, row "int8_conv3"), and prints one JSON line per plan: its largest and mean deviation from the fp32 engine in the raw
 outputs and in the move, value and score probabilities, and the largest and mean KL(fp32 || plan) of the move, value and
 score distributions.  --out writes the lines (default profiles/precision_report.jsonl); --append adds them to the file.
 
@@ -65,11 +66,18 @@ def main():
         ref = evaluate(eng, pos, args.batch)
         eng.close()
         plans = [("fp16", 0), ("int8", engine.FLAG_INT8), ("int8_fused", engine.FLAG_INT8_FUSED), ("int8_c128", engine.FLAG_INT8_C128),
-                 ("int8_any", engine.FLAG_INT8_ANY)]
+                 ("int8_any", engine.FLAG_INT8_ANY), ("int8_conv3", engine.FLAG_INT8_CONV3)]
         for label, flag in plans:
             # (on a trunk one of the three other INT8 flags serves, INT8_ANY is that flag's plan bit for bit: no second row)
             if label == "int8_any" and any(x["plan"].startswith("int8") for x in lines):
                 continue
+            # (P3HIP_FLAG_INT8_CONV3: a row where the flag has a plan of its own; a classic trunk's is the int8 row's)
+            if label == "int8_conv3":
+                try:
+                    if engine.debug_plan(path, flag)[0] != "Int8Conv3":
+                        continue
+                except engine.EngineError:
+                    continue
             try:
                 eng = engine.HipEngine(path, args.batch, flags=flag)
             except engine.EngineError:
