@@ -613,6 +613,23 @@ int p3hip_debug_act_i8(p3hip_engine* e, int8_t* out, int n_positions);
  * an engine without a transformer trunk, for n_positions < 1 or beyond the last run's, and for any other `which`.
  * A P3HIP_FLAG_FP32_TFM engine returns its stored fp32 values, exactly, in the same orders. */
 int p3hip_debug_tfm(p3hip_engine* e, int which, float* out, int n_positions);
+/* Test hook: fills with `byte` (0 .. 255), on the engine's stream, every value buffer on the device that a forward pass
+ * has to write before it reads it, then waits for the fill: the residual stream and the blocks' scratch, token rows
+ * 0 .. 360 of the transformer's q, k and v, the heads' scratch, the output rows, the dense result records and the aux
+ * records, and the term and sum buffers of p3hip_score and p3hip_loss where they exist.  An engine that reads no byte it
+ * did not write computes the same bits after it as without it (0xFF: NaN as fp16 and fp32, -1 as int8; 0x7B: about
+ * 6.1e4 as fp16, 1.3e36 as fp32, 123 as int8).  Left alone: what is state (weights, INT8 maxima and scales, the NN
+ * cache's table, labels and targets), every record an address is computed from (features, symmetry tables, the cache's
+ * keys and lists, the rows of scoring and loss), and what p3hip_create zeroes once for good (q, k, v rows 361 .. 383).
+ * The results of earlier runs are gone: p3hip_get_slot, p3hip_get_ownership, p3hip_get_raw, p3hip_get_aux,
+ * p3hip_get_score and p3hip_get_loss answer 2 and p3hip_score / p3hip_loss find no row until the next run; a slot whose
+ * result had not been fetched is evaluated again by that run.  A captured launch graph stays valid.  Returns 0, 1 on a
+ * bad byte or a HIP error. */
+int p3hip_debug_poison(p3hip_engine* e, int byte);
+/* Test hook, no device needed: the table p3hip_debug_poison goes by, one line per device buffer of an engine,
+ * "member<TAB>class<TAB>range": class is poisoned, state, index or zeroed-once, range the part of a zeroed-once buffer
+ * that stays zero ("What a forward pass may read"). */
+const char* p3hip_debug_poison_table(void);
 /* Algorithmic FLOPs (2*MAC) of one position: total, and 3x3 trunk convs only. */
 void p3hip_flops_per_position(const p3hip_engine* e, double* total, double* conv3x3);
 /* The spiral RoPE tables the transformer trunk uses (python/model_transformer.py, head_dim 32, 4 rotations, theta

@@ -27,6 +27,7 @@
 #include "conv_split.h"
 #include "edge_split.h"
 #include "lconv_i8.h"
+#include "loss.h"
 #include "transformer.h"
 #include "transformer_f32.h"
 #include "transformer_split.h"
@@ -78,6 +79,135 @@ int read_acts(p3hip_engine* e, const _Float16* buf, size_t first, size_t n, floa
   for (size_t i = 0; i < n; ++i) out[i] = (float)h[i];
   return 0;
 }
+
+// ---- the device buffers of an engine: their sizes, and what a forward pass may read of them ----------------------
+//
+// The sizes of the buffers p3hip_create allocates, from what it fixed before (batch, rows, the weight file, the plan):
+// p3hip_create allocates by these and p3hip_debug_poison fills by them, so the two cannot drift apart.
+size_t act_elems(const p3hip_engine* e, size_t channels) { return (size_t)e->rows * channels * kNLoc; }
+size_t x_bytes(const p3hip_engine* e) { return act_elems(e, e->wf.C) * act_bytes(e->trunk_path()); }
+// t holds a C-channel tensor (broadcast blocks, classic blocks, the transformer's o) or, in a layer-wise btl / nbt block,
+// two C_b-channel ones side by side (enqueue_forward, regions 1 and 2): 2 C_b > C where C_b > C / 2 (P3HIP_CONV_SET
+// allows C_b up to C, and padding C_b to a multiple of 64 can pass C / 2 as well)
+size_t t_bytes(const p3hip_engine* e) {
+  const size_t C = e->wf.C;
+  const size_t Ct = (e->wf.btype == 0 || e->wf.btype == 1) ? std::max<size_t>(C, 2 * (size_t)e->wf.Cb) : C;
+  return act_elems(e, Ct) * act_bytes(e->trunk_path());
+}
+size_t s_bytes(const p3hip_engine* e) { return act_elems(e, e->wf.Cb) * 2; }
+size_t qkv_bytes(const p3hip_engine* e) {   // heads x head width = model width
+  return 3 * (size_t)e->rows * p3::kTfmLPad * (size_t)e->wf.model_C * act_bytes(e->trunk_path());
+}
+size_t hp_bytes(const p3hip_engine* e) { return (size_t)e->rows * 96 * kNLoc * 4; }
+size_t pool_bytes(const p3hip_engine* e) { return (size_t)e->rows * p3::kHeadsPoolFloats * 4; }
+size_t out_bytes(const p3hip_engine* e) { return (size_t)e->batch * p3::kOutStride * 4; }
+size_t cout_bytes(const p3hip_engine* e) { return (size_t)e->rows * p3::kOutStride * 4; }
+size_t res_bytes(const p3hip_engine* e) { return (size_t)e->batch * p3::kResultFloats * 4; }
+size_t aux_bytes(const p3hip_engine* e) { return (size_t)e->rows * p3::kAuxStride * 4; }
+size_t feats_bytes(const p3hip_engine* e) { return (size_t)e->rows * kFeatBytes; }
+size_t slot_feats_bytes(const p3hip_engine* e) { return (size_t)e->batch * kFeatBytes; }
+size_t symtab_bytes(const p3hip_engine* e) { return (size_t)e->batch * 5; }
+size_t quant_bytes(const p3hip_engine* e) { return (size_t)e->plan.n_q * 4; }
+size_t arena_bytes(const p3hip_engine* e) { return e->arena_bytes; }
+// (the buffers other entry points make: p3hip_cache_enable, scoring.cpp ensure_scoring, loss_abi.cpp ensure_loss, and the
+// diagnostics of forward.cpp)
+size_t cache_entries(const p3hip_engine* e) { return (size_t)e->cache.mask + 1; }
+size_t batch_words(const p3hip_engine* e) { return (size_t)e->batch * 4; }
+
+// q, k, v are [3][rows][head][384][D]: token rows 0 .. 360 of every head are what a block writes and reads; rows
+// 361 .. 383 are zeroed by p3hip_create and never written (transformer.h kTfmLPad), and the attention kernels read them
+// as keys and values.  Fills the 361 written rows of every head and leaves the 23 others alone.
+bool poison_qkv_tokens(p3hip_engine* e, int byte) {
+  const size_t eb = act_bytes(e->trunk_path()), D = (size_t)e->plan.choice.tfm_D;
+  const size_t heads = (size_t)e->plan.choice.tfm_heads;
+  return e->check(hipMemset2DAsync(e->d_qkv, p3::kTfmLPad * D * eb, byte, (size_t)kNLoc * D * eb, 3 * (size_t)e->rows * heads, e->stream),
+                  "poison q, k, v");
+}
+
+// What a forward pass may read of a device buffer ("What a forward pass may read"):
+//   Poisoned    values that a pass, or the entry point that reads them, must write before it reads them: whatever they
+//               held before must not reach an output.  p3hip_debug_poison fills them.
+//   State       what outlives a pass by design: weights, calibration, the cache's table, labels and targets, diagnostics.
+//   Index       records the kernels or the host compute addresses from (features, symmetry tables, the cache's keys and
+//               lists, the rows of scoring and loss).  Never filled: no run may address through poison.
+//   ZeroedOnce  zeroed by p3hip_create and never written in part (zero_range); the rest is filled as Poisoned.
+enum class BufClass { Poisoned, State, Index, ZeroedOnce };
+
+const char* class_name(BufClass c) {
+  switch (c) {
+    case BufClass::Poisoned: return "poisoned";
+    case BufClass::State: return "state";
+    case BufClass::Index: return "index";
+    case BufClass::ZeroedOnce: return "zeroed-once";
+  }
+  return "";
+}
+
+struct DeviceBuffer {
+  const char* name;                         // the member of p3hip_engine, as engine.h spells it (nested: struct.member)
+  void* (*ptr)(const p3hip_engine*);        // null: this engine has no such buffer
+  size_t (*bytes)(const p3hip_engine*);
+  BufClass cls;
+  const char* zero_range = "";                            // ZeroedOnce: the part that stays zero, in words
+  bool (*poison_rest)(p3hip_engine*, int) = nullptr;      // ZeroedOnce: fills everything outside zero_range
+};
+
+#define P3_BUF(member) #member, [](const p3hip_engine* e) -> void* { return (void*)e->member; }
+#define P3_BYTES(expr) [](const p3hip_engine* e) -> size_t { return expr; }
+
+// Every device pointer member of p3hip_engine, once (tests/test_scratch_poison_cpu.py holds engine.h against this table).
+const DeviceBuffer kDeviceBuffers[] = {
+    // the forward pass's activations and head scratch: every pass writes what it reads of them
+    {P3_BUF(d_x), x_bytes, BufClass::Poisoned},
+    {P3_BUF(d_t), t_bytes, BufClass::Poisoned},
+    {P3_BUF(d_u), x_bytes, BufClass::Poisoned},
+    {P3_BUF(d_s), s_bytes, BufClass::Poisoned},
+    {P3_BUF(d_qkv), qkv_bytes, BufClass::ZeroedOnce, "token rows 361..383 of every head of q, k and v", poison_qkv_tokens},
+    {P3_BUF(d_hp), hp_bytes, BufClass::Poisoned},
+    {P3_BUF(d_pool), pool_bytes, BufClass::Poisoned},
+    // the output rows: a run writes the rows it hands out
+    {P3_BUF(d_cout), cout_bytes, BufClass::Poisoned},
+    {P3_BUF(d_out), out_bytes, BufClass::Poisoned},
+    {P3_BUF(d_res), res_bytes, BufClass::Poisoned},
+    {P3_BUF(d_aux), aux_bytes, BufClass::Poisoned},
+    // p3hip_score and p3hip_loss write the terms and sums they copy back
+    {P3_BUF(scoring.d_terms), P3_BYTES(batch_words(e) * P3HIP_NUM_SCORE_TERMS), BufClass::Poisoned},
+    {P3_BUF(scoring.d_sums), P3_BYTES(P3HIP_NUM_SCORE_TERMS * sizeof(double)), BufClass::Poisoned},
+    {P3_BUF(loss.d_terms), P3_BYTES(batch_words(e) * P3HIP_NUM_LOSS_TERMS), BufClass::Poisoned},
+    {P3_BUF(loss.d_sums), P3_BYTES(P3HIP_NUM_LOSS_TERMS * sizeof(double)), BufClass::Poisoned},
+    // state
+    {P3_BUF(d_arena), arena_bytes, BufClass::State},
+    {P3_BUF(d_amax), quant_bytes, BufClass::State},
+    {P3_BUF(d_ascale), quant_bytes, BufClass::State},
+    {P3_BUF(cache.d_tkeys), P3_BYTES(cache_entries(e) * 16), BufClass::State},
+    {P3_BUF(cache.d_tmeta), P3_BYTES(cache_entries(e) * 4), BufClass::State},
+    {P3_BUF(cache.d_tvals), P3_BYTES(cache_entries(e) * p3::kOutStride * 4), BufClass::State},
+    {P3_BUF(scoring.d_labels), P3_BYTES((size_t)e->batch * sizeof(p3hip_labels)), BufClass::State},
+    {P3_BUF(loss.d_targets), P3_BYTES(batch_words(e) * p3::kTgtStride), BufClass::State},
+    {P3_BUF(d_bw_stamps), P3_BYTES((size_t)8 * 16 * 4 * 24 * 8), BufClass::State},
+#ifdef P3_DIAG
+    {P3_BUF(d_stamps), P3_BYTES((size_t)p3::kStampWgs * 8 * p3::kStampSections * p3::kStampSlots * 8), BufClass::State},
+    {P3_BUF(d_spans), P3_BYTES((size_t)p3::kSpanWgs * p3::kSpanSlots * 8), BufClass::State},
+#else
+    {"d_stamps", [](const p3hip_engine*) -> void* { return nullptr; }, P3_BYTES(0), BufClass::State},
+    {"d_spans", [](const p3hip_engine*) -> void* { return nullptr; }, P3_BYTES(0), BufClass::State},
+#endif
+    // index
+    {P3_BUF(d_feats), feats_bytes, BufClass::Index},
+    {P3_BUF(d_sfeats), slot_feats_bytes, BufClass::Index},
+    {P3_BUF(d_symtab), symtab_bytes, BufClass::Index},
+    {P3_BUF(cache.d_keys), P3_BYTES((size_t)e->batch * sizeof(p3::CacheKey)), BufClass::Index},
+    {P3_BUF(cache.d_hit), batch_words, BufClass::Index},
+    {P3_BUF(cache.d_victim), batch_words, BufClass::Index},
+    {P3_BUF(cache.d_lists), P3_BYTES(5 * batch_words(e)), BufClass::Index},
+    {P3_BUF(cache.d_sym), batch_words, BufClass::Index},
+    {P3_BUF(cache.d_feats2), slot_feats_bytes, BufClass::Index},
+    {P3_BUF(scoring.d_rows), batch_words, BufClass::Index},
+    {P3_BUF(loss.d_rows), batch_words, BufClass::Index},
+};
+
+#undef P3_BUF
+#undef P3_BYTES
 
 }  // namespace
 
@@ -165,58 +295,52 @@ p3hip_engine* p3hip_create_rows(const char* weights_path, int batch_size, int ve
   if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
     return fail(std::string("device is ") + prop.gcnArchName + ", this engine is built for gfx950 only");
   e->n_cu = prop.multiProcessorCount;
-  const int C = e->wf.C;
   const size_t B = batch_size;
-  // the per-row device buffers: 8 x batch copies with P3HIP_FLAG_SYMMETRY_AVG, symmetry_rows with P3HIP_FLAG_SYMMETRY_SLOT
-  const size_t R = e->rows;
+  // the per-row device buffers have e->rows rows: 8 x batch copies with P3HIP_FLAG_SYMMETRY_AVG, symmetry_rows with
+  // P3HIP_FLAG_SYMMETRY_SLOT.  Their sizes: the functions in front of kDeviceBuffers
   const bool copies = sym || sym_slot;
-  // t holds a C-channel tensor (broadcast blocks, classic blocks, the transformer's o) or, in a layer-wise btl / nbt block,
-  // two C_b-channel ones side by side (enqueue_forward, regions 1 and 2): 2 C_b > C where C_b > C / 2 (P3HIP_CONV_SET
-  // allows C_b up to C, and padding C_b to a multiple of 64 can pass C / 2 as well)
-  const size_t Ct = (e->wf.btype == 0 || e->wf.btype == 1) ? std::max<size_t>(C, 2 * (size_t)e->wf.Cb) : (size_t)C;
   const Path path = e->trunk_path();
-  const size_t eb = act_bytes(path);
-  const size_t qkv_bytes = 3 * R * p3::kTfmLPad * (size_t)e->wf.model_C * eb;   // heads x head width = model width
+  e->arena_bytes = ar.host.size();
   bool ok = e->check(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking), "hipStreamCreate") &&
-            e->check(hipMalloc((void**)&e->d_arena, ar.host.size()), "hipMalloc arena") &&
+            e->check(hipMalloc((void**)&e->d_arena, arena_bytes(e)), "hipMalloc arena") &&
             // on the engine's own stream: it is non-blocking (no implicit ordering with the null stream a plain
             // hipMemcpy / hipMemset runs on), and the first run must find the weights there
             e->check(hipMemcpyAsync(e->d_arena, ar.host.data(), ar.host.size(), hipMemcpyHostToDevice, e->stream), "upload weights") &&
             e->check(hipHostMalloc((void**)&e->h_feats, B * kFeatBytes, hipHostMallocDefault), "hipHostMalloc") &&
             e->check(hipHostMalloc((void**)&e->h_feats_compact, B * kFeatBytes, hipHostMallocDefault), "hipHostMalloc") &&
             e->check(hipHostMalloc((void**)&e->h_out, B * p3::kResultFloats * 4, hipHostMallocDefault), "hipHostMalloc") &&
-            e->check(hipMalloc((void**)&e->d_res, B * p3::kResultFloats * 4), "hipMalloc results") &&
-            e->check(hipMalloc((void**)&e->d_feats, R * kFeatBytes), "hipMalloc feats") &&
-            e->check(hipMalloc((void**)&e->d_x, R * C * kNLoc * eb), "hipMalloc x") &&
-            e->check(hipMalloc((void**)&e->d_t, R * Ct * kNLoc * eb), "hipMalloc t") &&
-            e->check(hipMalloc((void**)&e->d_u, R * C * kNLoc * eb), "hipMalloc u") &&
+            e->check(hipMalloc((void**)&e->d_res, res_bytes(e)), "hipMalloc results") &&
+            e->check(hipMalloc((void**)&e->d_feats, feats_bytes(e)), "hipMalloc feats") &&
+            e->check(hipMalloc((void**)&e->d_x, x_bytes(e)), "hipMalloc x") &&
+            e->check(hipMalloc((void**)&e->d_t, t_bytes(e)), "hipMalloc t") &&
+            e->check(hipMalloc((void**)&e->d_u, x_bytes(e)), "hipMalloc u") &&
             // (d_s is the fused nbt kernel's scratch; the fp32 plan runs layer by layer and has none)
-            (e->wf.btype != 1 || path == Path::F32Conv || e->check(hipMalloc((void**)&e->d_s, R * e->wf.Cb * kNLoc * 2), "hipMalloc s")) &&
-            (!is_tfm(path) || e->check(hipMalloc((void**)&e->d_qkv, qkv_bytes), "hipMalloc qkv")) &&
-            e->check(hipMalloc((void**)&e->d_hp, R * 96 * kNLoc * 4), "hipMalloc hp") &&
+            (e->wf.btype != 1 || path == Path::F32Conv || e->check(hipMalloc((void**)&e->d_s, s_bytes(e)), "hipMalloc s")) &&
+            (!is_tfm(path) || e->check(hipMalloc((void**)&e->d_qkv, qkv_bytes(e)), "hipMalloc qkv")) &&
+            e->check(hipMalloc((void**)&e->d_hp, hp_bytes(e)), "hipMalloc hp") &&
             // (the split heads' pooled values, edge_split.h: the two low-latency paths only)
             ((path != Path::Split && path != Path::TfmSplit) ||
-             e->check(hipMalloc((void**)&e->d_pool, R * p3::kHeadsPoolFloats * 4), "hipMalloc pooled")) &&
-            e->check(hipMalloc((void**)&e->d_out, B * p3::kOutStride * 4), "hipMalloc out") &&
-            (!copies || (e->check(hipMalloc((void**)&e->d_sfeats, B * kFeatBytes), "hipMalloc symmetry upload") &&
-                         e->check(hipMalloc((void**)&e->d_cout, R * p3::kOutStride * 4), "hipMalloc copy rows"))) &&
-            (!sym_slot || (e->check(hipMalloc((void**)&e->d_symtab, B * 5), "hipMalloc symmetry table") &&
+             e->check(hipMalloc((void**)&e->d_pool, pool_bytes(e)), "hipMalloc pooled")) &&
+            e->check(hipMalloc((void**)&e->d_out, out_bytes(e)), "hipMalloc out") &&
+            (!copies || (e->check(hipMalloc((void**)&e->d_sfeats, slot_feats_bytes(e)), "hipMalloc symmetry upload") &&
+                         e->check(hipMalloc((void**)&e->d_cout, cout_bytes(e)), "hipMalloc copy rows"))) &&
+            (!sym_slot || (e->check(hipMalloc((void**)&e->d_symtab, symtab_bytes(e)), "hipMalloc symmetry table") &&
                            e->check(hipHostMalloc((void**)&e->h_symtab, B * 5, hipHostMallocDefault), "hipHostMalloc") &&
-                           e->check(hipMemsetAsync(e->d_symtab, 0, B * 5, e->stream), "hipMemset symmetry table"))) &&
-            (!(flags & P3HIP_FLAG_AUX) || (e->check(hipMalloc((void**)&e->d_aux, R * p3::kAuxStride * 4), "hipMalloc aux") &&
-                                           e->check(hipMemsetAsync(e->d_aux, 0, R * p3::kAuxStride * 4, e->stream), "hipMemset aux"))) &&
-            (!is_int8(path) || (e->check(hipMalloc((void**)&e->d_amax, (size_t)e->plan.n_q * 4), "hipMalloc amax") &&
-                          e->check(hipMalloc((void**)&e->d_ascale, (size_t)e->plan.n_q * 4), "hipMalloc scales") &&
-                          e->check(hipMemsetAsync(e->d_amax, 0, (size_t)e->plan.n_q * 4, e->stream), "hipMemset amax") &&
-                          e->check(hipMemsetAsync(e->d_ascale, 0, (size_t)e->plan.n_q * 4, e->stream), "hipMemset scales")));
+                           e->check(hipMemsetAsync(e->d_symtab, 0, symtab_bytes(e), e->stream), "hipMemset symmetry table"))) &&
+            (!(flags & P3HIP_FLAG_AUX) || (e->check(hipMalloc((void**)&e->d_aux, aux_bytes(e)), "hipMalloc aux") &&
+                                           e->check(hipMemsetAsync(e->d_aux, 0, aux_bytes(e), e->stream), "hipMemset aux"))) &&
+            (!is_int8(path) || (e->check(hipMalloc((void**)&e->d_amax, quant_bytes(e)), "hipMalloc amax") &&
+                          e->check(hipMalloc((void**)&e->d_ascale, quant_bytes(e)), "hipMalloc scales") &&
+                          e->check(hipMemsetAsync(e->d_amax, 0, quant_bytes(e), e->stream), "hipMemset amax") &&
+                          e->check(hipMemsetAsync(e->d_ascale, 0, quant_bytes(e), e->stream), "hipMemset scales")));
   if (!ok) return fail(e->err);
   e->h_scale.assign(e->plan.n_q, 0.0f);
   memset(e->h_feats, 0, B * kFeatBytes);
-  if (!e->check(hipMemsetAsync(e->d_feats, 0, R * kFeatBytes, e->stream), "hipMemset feats") ||
-      (copies && !e->check(hipMemsetAsync(e->d_sfeats, 0, B * kFeatBytes, e->stream), "hipMemset symmetry upload")) ||
-      (copies && !e->check(hipMemsetAsync(e->d_cout, 0, R * p3::kOutStride * 4, e->stream), "hipMemset copy rows")) ||
-      (is_tfm(path) && !e->check(hipMemsetAsync(e->d_qkv, 0, qkv_bytes, e->stream), "hipMemset qkv")) ||
-      !e->check(hipMemsetAsync(e->d_out, 0, B * p3::kOutStride * 4, e->stream), "hipMemset out") ||
+  if (!e->check(hipMemsetAsync(e->d_feats, 0, feats_bytes(e), e->stream), "hipMemset feats") ||
+      (copies && !e->check(hipMemsetAsync(e->d_sfeats, 0, slot_feats_bytes(e), e->stream), "hipMemset symmetry upload")) ||
+      (copies && !e->check(hipMemsetAsync(e->d_cout, 0, cout_bytes(e), e->stream), "hipMemset copy rows")) ||
+      (is_tfm(path) && !e->check(hipMemsetAsync(e->d_qkv, 0, qkv_bytes(e), e->stream), "hipMemset qkv")) ||
+      !e->check(hipMemsetAsync(e->d_out, 0, out_bytes(e), e->stream), "hipMemset out") ||
       !e->check(hipStreamSynchronize(e->stream), "upload sync")) return fail(e->err);
   // the heads' arguments that never change: the weight pointers, by the table that packed them
   e->heads_args.conv_a = e->d_arena + e->plan.heads_conv_a_off;
@@ -878,6 +1002,37 @@ int p3hip_debug_tfm(p3hip_engine* e, int which, float* out, int n_positions) {
   const size_t per = (size_t)e->rows * p3::kTfmLPad * d;
   const size_t n = (size_t)n_positions * (which < 3 ? p3::kTfmLPad : kNLoc) * d;
   return which < 3 ? read_acts(e, e->d_qkv, which * per, n, out) : read_acts(e, e->d_t, 0, n, out);
+}
+
+// test hook: every value buffer a forward pass (or p3hip_score / p3hip_loss) must define before it reads it, filled with
+// `byte` on the engine's stream: the rows of kDeviceBuffers of class Poisoned, and of a ZeroedOnce buffer what lies outside
+// its zero range.  State and Index buffers are left alone, so no later run can compute an address from the fill.  The
+// results of earlier runs are gone: no slot keeps a row and the rows count as overwritten (run_seq), as after the hooks
+// that write d_out without a gather.  No pointer changes, so a captured graph stays valid.
+int p3hip_debug_poison(p3hip_engine* e, int byte) {
+  if (byte < 0 || byte > 255) { e->err = "p3hip_debug_poison: the fill is one byte, 0 .. 255"; return 1; }
+  if (!e->bind()) return 1;
+  for (const DeviceBuffer& b : kDeviceBuffers) {
+    void* p = b.ptr(e);
+    if (!p) continue;
+    if (b.cls == BufClass::Poisoned && !e->check(hipMemsetAsync(p, byte, b.bytes(e), e->stream), b.name)) return 1;
+    if (b.cls == BufClass::ZeroedOnce && !b.poison_rest(e, byte)) return 1;
+  }
+  if (!e->check(hipStreamSynchronize(e->stream), "sync")) return 1;
+  ++e->run_seq;   // p3hip_score, p3hip_loss and their getters stop answering for the last run
+  e->slots.drop_rows();   // p3hip_get_*: 2, not evaluated (a slot not yet fetched stays pending for the next run)
+  return 0;
+}
+
+// test hook, no device needed: the table p3hip_debug_poison goes by, one line per device pointer member of p3hip_engine,
+// "name<TAB>class<TAB>the range that stays zero (zeroed-once only)"
+const char* p3hip_debug_poison_table(void) {
+  static const std::string text = [] {
+    std::string t;
+    for (const DeviceBuffer& b : kDeviceBuffers) t += std::string(b.name) + "\t" + class_name(b.cls) + "\t" + b.zero_range + "\n";
+    return t;
+  }();
+  return text.c_str();
 }
 
 void p3hip_rope_table(double* cos_out, double* sin_out) { spiral_rope_table(32, cos_out, sin_out); }

@@ -55,7 +55,11 @@ struct p3hip_engine {
   // p3hip_time_trunk_kernel: event pairs around the timed launches of a forward pass
   std::vector<hipEvent_t> blk_ev;
 
+  // Every device pointer below (d_*, those of the nested structs included) has one row in kDeviceBuffers (engine.cpp): its
+  // size and whether a forward pass may read what an earlier one left there.  A new buffer needs a row, or
+  // tests/test_scratch_poison_cpu.py fails.
   unsigned char* d_arena = nullptr;
+  size_t arena_bytes = 0;
   p3::HeadsArgs heads_args{};   // the heads' weight pointers, set once at create; a pass fills x, hp, out, res and npos
   // The INT8 paths: the layer-wise blocks' convs run on int8 inputs with per-tensor activation
   // scales.  amax: running per-tensor maxima of the calibration runs (float bits, atomicMax); scale: the s_a = max / 127

@@ -38,6 +38,7 @@ EXPORTS = [
     "p3hip_load_targets", "p3hip_loss", "p3hip_get_loss", "p3hip_debug_loss_rows",
     "p3hip_debug_plan", "p3hip_debug_act_i8",
     "p3hip_debug_split", "p3hip_debug_pack_sconv", "p3hip_debug_tfm_split", "p3hip_debug_edge_split",
+    "p3hip_debug_poison", "p3hip_debug_poison_table",
 ]
 
 FLAG_RUN_ALL_SLOTS = 2
@@ -489,6 +490,12 @@ class HipEngine:
         self._ck(self._L.p3hip_debug_act_i8(self._h, out.ctypes.data, n), "debug_act_i8")
         return out.reshape(n, channels // 16, 361, 16).transpose(0, 1, 3, 2).reshape(n, channels, 361)
 
+    def debug_poison(self, byte: int) -> None:
+        """Test hook (p3hip.h p3hip_debug_poison): fills every value buffer a forward pass must write before it reads it
+        with `byte` (0..255); state, index records and the regions zeroed once stay.  The last run's results are gone."""
+        self._L.p3hip_debug_poison.argtypes = [C.c_void_p, C.c_int]
+        self._ck(self._L.p3hip_debug_poison(self._h, int(byte)), "debug_poison")
+
     def graph_state(self) -> int:
         """P3HIP_FLAG_LAUNCH_GRAPH: 1 replaying the captured forward pass, 0 not (yet), -1 capture failed."""
         self._L.p3hip_graph_state.argtypes = [C.c_void_p]
@@ -533,6 +540,21 @@ def debug_plan(path: str, flags: int = 0):
     if name is None:
         raise EngineError("p3hip_create: " + L.p3hip_create_error().decode())
     return name.decode(), n_q.value, dig.value
+
+
+def debug_poison_table() -> dict:
+    """{device pointer member of p3hip_engine: (class, range that stays zero)} of the table p3hip_debug_poison goes by
+    (csrc/engine.cpp kDeviceBuffers; no device needed).  ValueError where a member has two rows."""
+    L = lib()
+    L.p3hip_debug_poison_table.restype = C.c_char_p
+    L.p3hip_debug_poison_table.argtypes = []
+    out = {}
+    for line in L.p3hip_debug_poison_table().decode().splitlines():
+        name, cls, zero_range = line.split("\t")
+        if name in out:
+            raise ValueError(f"p3hip_debug_poison_table: {name} has two rows")
+        out[name] = (cls, zero_range)
+    return out
 
 
 def debug_tfm_split(npos: int, heads: int, n_cu: int = 256):
