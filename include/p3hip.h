@@ -154,6 +154,24 @@ typedef struct p3hip_engine p3hip_engine;
                                        section 9): 0.84x of fp16's forward time on b14c384btl3 at batch 1024 (12.31 against
                                        14.64 ms), 0.87-0.90x on b10c384nbt, b14c320btl3 and b10c512nbt, 0.99x on b12c192btl3;
                                        0.91-1.00x at batch 256 */
+#define P3HIP_FLAG_WINOGRAD 65536u   /* every 3x3 conv of the layer-wise blocks as F(2x2, 3x3) Winograd on fp16 MFMAs (k_wconv,
+                                       csrc/conv_wino.hip): 2.25 x fewer multiplications per output, no
+                                       calibration, fp16 inputs and outputs everywhere.  The weights are transformed from the
+                                       file's fp32 values and rounded once to fp16, the input transform runs in two fp16
+                                       stages, accumulation and the output transform are fp32.  Every 1x1 conv, the stem, the
+                                       broadcast blocks, the heads, the buffers and the layouts are the fp16 plan's own.  The
+                                       plan has its own parity bound (tests/winograd_restatement.py): it is a little less
+                                       accurate than the default plan and far more than the INT8 plans.  Served: every conv
+                                       trunk of P3HIP_CONV_SET whose fp16 plan runs layer by layer: (384, 192) btl / nbt,
+                                       classic at every C, every padded or runtime width (with P3HIP_CONV_ANY=1 the templated
+                                       shapes take the runtime-width 1x1 kernels, same bits).  Composes with the flags that
+                                       do not touch the trunk.  p3hip_create returns NULL for a transformer trunk, for the
+                                       (256, 128) and (128, 64) btl / nbt trunks (their fp16 plan is the fused block
+                                       kernel), together with any INT8 flag, with P3HIP_FLAG_FP32 / P3HIP_FLAG_FP32_TFM and
+                                       with either low-latency flag.  Measured on one MI355X, legs interleaved with fp16
+                                       (README.md): as accurate as fp16 (raw outputs 0.0036 against
+                                       0.0033 from the fp32 engine on b14c384btl3) and slower, 1.79x of fp16's forward time
+                                       on b14c384btl3 at batch 1024, 1.70-2.31x over five nets and two batches */
 #define P3HIP_FLAG_SYMMETRY_AVG 32u /* every slot a run evaluates is evaluated under each symmetry of the engine's set
                                        (default: all eight) and the results averaged on the device, rotated back into the
                                        orientation the slot was loaded in.  Needs 8 x batch_size <= 65536.  See
@@ -557,13 +575,14 @@ int p3hip_get_raw(p3hip_engine* e, int slot, float* out);
  * INT8 engine k_lconv_i8<3,..> (P3HIP_FLAG_INT8_ANY on a trunk of its own path: k_lconv_i8_any<3>, and the FLOPs at the file's own
  * widths), and writes the FLOPs of one 3x3 conv.  A P3HIP_FLAG_FP32 engine is layer-wise whatever its
  * trunk: it times k_lconv_f32<3> and writes the FLOPs of one 3x3 conv at the file's own widths; so is a
- * P3HIP_FLAG_LOW_LATENCY engine, with k_sconv<3>.  A P3HIP_FLAG_LOW_LATENCY_TFM engine times the attention launch of the
+ * P3HIP_FLAG_LOW_LATENCY engine, with k_sconv<3>; a P3HIP_FLAG_WINOGRAD engine times k_wconv and writes the FLOPs of one
+ * direct 3x3 conv at the file's own widths.  A P3HIP_FLAG_LOW_LATENCY_TFM engine times the attention launch of the
  * split in force for n_positions: k_tfm_attn_split, or k_tfm_attn where that is one part, with the same FLOPs. */
 double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
                                double* flops_per_launch, const char** kernel_name);
 /* Test hook, no device: loads the file and builds the host-side plan of (file, flags, the P3HIP_* environment) as
  * p3hip_create would.  Returns the name of the trunk path chosen ("Fused", "Layerwise", "ConvAny", "Int8", "Int8Fused256",
- * "Int8Fused128", "Int8Any", "F32Conv", "Tfm", ..), or NULL with the reason in p3hip_create_error().  n_q: the quantized
+ * "Int8Fused128", "Int8Any", "F32Conv", "Winograd3", "Tfm", ..), or NULL with the reason in p3hip_create_error().  n_q: the quantized
  * tensors of an INT8 plan (0 otherwise); digest: a 64-bit FNV-1a hash over the int8 weight bytes and the weight scales
  * of every quantized conv, in the plan's order (0 without any).  Either pointer may be NULL. */
 const char* p3hip_debug_plan(const char* weights_path, uint32_t flags, int* n_q, uint64_t* digest);
@@ -574,6 +593,16 @@ const char* p3hip_debug_plan(const char* weights_path, uint32_t flags, int* n_q,
  * raw fp16 bits; returns the number of elements, writes at most n of them. */
 int p3hip_debug_split(int npos, int kw, int cout, int n_cu, int* strips, int* tile);
 long p3hip_debug_pack_sconv(const float* w, int taps, int cin, int cout, int cin_pad, int cout_pad, uint16_t* out, long n);
+/* Test hooks, no device (P3HIP_FLAG_WINOGRAD).  p3hip_debug_pack_wconv: k_wconv's weight image (csrc/conv_wino.h
+ * pack_wconv) of the 3x3 conv W[9][cin][cout] padded to cin_pad x cout_pad (multiples of 64), as raw fp16 bits; returns
+ * the number of elements, writes at most n of them.  p3hip_debug_wconv_grid: how the launcher cuts a k_wconv launch over
+ * npos positions and cout output channels on a device of n_cu CUs (csrc/conv_wino.h wconv_grid, wconv_unit, the
+ * functions the launcher and the kernel call): *grid workgroups, *units units of work, dealt round (workgroup b takes
+ * the units b, b + grid, ..); with 0 <= unit < units also that unit's first flat tile (tile f = 100 position + 10 tile
+ * row + tile column), its tile count and its first output channel (any of the three pointers may be NULL).  Returns 0,
+ * or 1 for a bad argument. */
+long p3hip_debug_pack_wconv(const float* w, int cin, int cout, int cin_pad, int cout_pad, uint16_t* out, long n);
+int p3hip_debug_wconv_grid(int npos, int cout, int n_cu, int* grid, long* units, long unit, long* tile0, int* ntiles, int* cout0);
 /* Test hook, no device (P3HIP_FLAG_LOW_LATENCY_TFM): the query parts per (position, head) of the attention launch and the
  * tokens per workgroup of the qkv and ffn launches over npos positions of a trunk with `heads` heads on a device of n_cu
  * CUs, the P3HIP_TFM_SPLIT override included; 0, or 1 for a bad argument or a bad P3HIP_TFM_SPLIT. */

@@ -25,6 +25,7 @@
 #include "conv_any.h"
 #include "conv_f32.h"
 #include "conv_split.h"
+#include "conv_wino.h"
 #include "edge_split.h"
 #include "lconv_i8.h"
 #include "loss.h"
@@ -455,6 +456,27 @@ long p3hip_debug_pack_sconv(const float* w, int taps, int cin, int cout, int cin
   p3::pack_sconv(img, w, taps, cin, cout, cin_pad, cout_pad);
   for (long i = 0; i < n && i < (long)img.size(); ++i) memcpy(out + i, &img[i], 2);
   return (long)img.size();
+}
+
+long p3hip_debug_pack_wconv(const float* w, int cin, int cout, int cin_pad, int cout_pad, uint16_t* out, long n) {
+  std::vector<_Float16> img;
+  p3::pack_wconv(img, w, cin, cout, cin_pad, cout_pad);
+  for (long i = 0; i < n && i < (long)img.size(); ++i) memcpy(out + i, &img[i], 2);
+  return (long)img.size();
+}
+
+int p3hip_debug_wconv_grid(int npos, int cout, int n_cu, int* grid, long* units, long unit, long* tile0, int* ntiles, int* cout0) {
+  if (npos < 1 || cout < 64 || cout > p3::kWinoMaxC || cout % 64 != 0 || n_cu < 1 || !grid || !units) return 1;
+  *grid = p3::wconv_grid(npos, cout, n_cu);
+  *units = p3::wconv_units(npos, cout);
+  if (unit < 0 || unit >= *units) return (tile0 || ntiles || cout0) ? 1 : 0;
+  long t0 = 0;
+  int nt = 0, c0 = 0;
+  p3::wconv_unit(npos, cout, unit, &t0, &nt, &c0);
+  if (tile0) *tile0 = t0;
+  if (ntiles) *ntiles = nt;
+  if (cout0) *cout0 = c0;
+  return 0;
 }
 
 int p3hip_kind(const p3hip_engine*) { return P3HIP_KIND_HIP; }
@@ -931,6 +953,7 @@ double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
     case Path::Split:
     case Path::Int8Any:
     case Path::Int8Conv3:
+    case Path::Winograd3:
     case Path::Int8:
     case Path::Layerwise: {
       // the runtime-width kernels: the file's own width, not the padded one the kernel runs; the templated: the layer's

@@ -205,7 +205,7 @@ namespace eng {
 
 // forward.cpp
 // The kernel that runs the convs of the layer-wise blocks in the engine's present state, and its name in a profile
-enum class LayerKernel { Lconv, LconvAny, LconvI8, LconvI8Any, LconvF32, Sconv };
+enum class LayerKernel { Lconv, LconvAny, LconvI8, LconvI8Any, LconvF32, Sconv, Wconv };
 LayerKernel layer_kernel(const p3hip_engine* e, int kw = 3);   // (kw: of the layer; the timed convs are the 3x3)
 const char* layer_kernel_name(LayerKernel k, int kw, int cin, int cout);
 void tfm_split_of(const p3hip_engine* e, int npos, int* parts, int* tokens);   // Path::TfmSplit: the split of a launch

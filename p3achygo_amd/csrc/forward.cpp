@@ -9,6 +9,7 @@
 #include "conv_any.h"
 #include "conv_f32.h"
 #include "conv_split.h"
+#include "conv_wino.h"
 #include "edge_split.h"
 #include "engine.h"
 #include "lconv_conv3.h"
@@ -343,6 +344,12 @@ bool launch_layer(p3hip_engine* e, const Pass& p, const LayerPlan& lp, const cha
       else p3::sconv_split(a.npos, lp.kw, a.cout, e->n_cu, &a.strips, &a.tile);
       return e->check(p3::launch_sconv(lp.kw, a, e->n_cu, e->stream), what ? what : "launch k_sconv");
     }
+    case LayerKernel::Wconv: {
+      p3::WConvArgs a{};
+      fill_layer(e, a, lp, Regions<_Float16>(e), p.npos);
+      a.cin = lp.cin; a.cout = lp.cout; a.w = e->d_arena + lp.wino_off;
+      return e->check(p3::launch_wconv(a, e->n_cu, e->stream), what ? what : "launch k_wconv");
+    }
     case LayerKernel::LconvI8:
     case LayerKernel::LconvI8Any: {
       // (the callers check int8_ready) the fp16 plan's regions, an int8 tensor where that stores an activated one
@@ -566,6 +573,8 @@ LayerKernel layer_kernel(const p3hip_engine* e, int kw) {
     if (kw == 3 && !e->calibrating) return any ? LayerKernel::LconvI8Any : LayerKernel::LconvI8;
     return any ? LayerKernel::LconvAny : LayerKernel::Lconv;
   }
+  // Winograd3: a 3x3 conv k_wconv, a 1x1 conv the kernel of the trunk's fp16 plan
+  if (path == Path::Winograd3) return kw == 3 ? LayerKernel::Wconv : e->plan.choice.any_width ? LayerKernel::LconvAny : LayerKernel::Lconv;
   if (path == Path::F32Conv) return LayerKernel::LconvF32;
   if (path == Path::Split) return LayerKernel::Sconv;
   if (is_int8(path) && !e->calibrating) return path == Path::Int8Any ? LayerKernel::LconvI8Any : LayerKernel::LconvI8;
@@ -580,6 +589,7 @@ const char* layer_kernel_name(LayerKernel k, int kw, int cin, int cout) {
     case LayerKernel::LconvI8Any: return p3::lconv_i8_any_kernel_name(kw);
     case LayerKernel::LconvF32: return p3::lconv_f32_kernel_name(kw);
     case LayerKernel::Sconv: return p3::sconv_kernel_name(kw);
+    case LayerKernel::Wconv: return p3::wconv_kernel_name();
   }
   return nullptr;
 }

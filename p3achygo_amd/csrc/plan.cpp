@@ -11,6 +11,7 @@
 #include "conv_any.h"
 #include "conv_f32.h"
 #include "conv_split.h"
+#include "conv_wino.h"
 #include "edge_split.h"
 #include "lconv_i8.h"
 #include "transformer.h"
@@ -76,6 +77,7 @@ const char* path_name(Path p) {
     case Path::Int8Fused128: return "Int8Fused128";
     case Path::Int8Any: return "Int8Any";
     case Path::Int8Conv3: return "Int8Conv3";
+    case Path::Winograd3: return "Winograd3";
     case Path::F32Conv: return "F32Conv";
     case Path::Split: return "Split";
     case Path::Tfm: return "Tfm";
@@ -132,7 +134,7 @@ TrunkClass classify(const WeightFile& wf) {
 
 // What the precision flags ask for: one plan
 struct Request {
-  enum Kind { Fp16, Int8, Int8Fused, Int8C128, Int8Any, Int8Conv3, Fp32, LowLatency, LowLatencyTfm } kind = Fp16;
+  enum Kind { Fp16, Int8, Int8Fused, Int8C128, Int8Any, Int8Conv3, Winograd, Fp32, LowLatency, LowLatencyTfm } kind = Fp16;
   bool int8_any = false;   // P3HIP_FLAG_INT8_ANY was given (kind is the plan it chose)
   bool int8_conv3 = false;   // P3HIP_FLAG_INT8_CONV3 was given (a classic trunk: kind is Int8 or Int8Any, its whole plan)
   bool alone = true;       // Int8Fused, Int8C128: no other of the three INT8 flags beside it
@@ -159,7 +161,19 @@ Request read_request(uint32_t flags, const TrunkClass& t, int C, const Options& 
   Request r;
   r.f32_conv = (flags & P3HIP_FLAG_FP32) != 0;
   r.f32_tfm = (flags & P3HIP_FLAG_FP32_TFM) != 0;
-  if (flags & P3HIP_FLAG_INT8_CONV3) {
+  if (flags & P3HIP_FLAG_WINOGRAD) {
+    // (as P3HIP_FLAG_INT8_CONV3 below: the flag added last answers every set it stands in)
+    r.kind = Request::Winograd;
+    if (i8_three || (flags & (P3HIP_FLAG_INT8_ANY | P3HIP_FLAG_INT8_CONV3)))
+      r.clash = "P3HIP_FLAG_WINOGRAD cannot be combined with P3HIP_FLAG_INT8, P3HIP_FLAG_INT8_FUSED, P3HIP_FLAG_INT8_C128, "
+                "P3HIP_FLAG_INT8_ANY or P3HIP_FLAG_INT8_CONV3: its kernel runs in fp16";
+    else if (fp32_flag)
+      r.clash = "P3HIP_FLAG_WINOGRAD cannot be combined with P3HIP_FLAG_FP32 or P3HIP_FLAG_FP32_TFM: an engine runs one "
+                "precision plan";
+    else if (flags & (P3HIP_FLAG_LOW_LATENCY | P3HIP_FLAG_LOW_LATENCY_TFM))
+      r.clash = "P3HIP_FLAG_WINOGRAD cannot be combined with P3HIP_FLAG_LOW_LATENCY or P3HIP_FLAG_LOW_LATENCY_TFM: it has no "
+                "low-latency form";
+  } else if (flags & P3HIP_FLAG_INT8_CONV3) {
     // (a flag set with this flag in it is this flag's to answer: it was added last, and the answers of every set without
     // it stay what they were)
     r.int8_conv3 = true;
@@ -222,6 +236,7 @@ Path path_of(const Request& r, const TrunkClass& t, const WeightFile& wf, const 
     case Request::LowLatency: return Path::Split;
     case Request::Int8Any: return Path::Int8Any;
     case Request::Int8Conv3: return Path::Int8Conv3;
+    case Request::Winograd: return Path::Winograd3;
     case Request::Int8Fused: return Path::Int8Fused256;
     case Request::Int8C128: return Path::Int8Fused128;
     case Request::Int8: return Path::Int8;
@@ -253,6 +268,9 @@ PlanChoice choose_plan(const WeightFile& wf, uint32_t flags, const Options& opt,
       {k == Request::LowLatencyTfm && !t.tfm_file,
        "P3HIP_FLAG_LOW_LATENCY_TFM serves the transformer trunks only (" P3HIP_TRANSFORMER_SET "); the conv trunks have "
        "P3HIP_FLAG_LOW_LATENCY"},
+      {k == Request::Winograd && t.tfm_file,
+       "P3HIP_FLAG_WINOGRAD serves the conv trunks (" P3HIP_CONV_SET ") whose fp16 plan runs layer by layer; the "
+       "transformer trunks (" P3HIP_TRANSFORMER_SET ") have no 3x3 convs"},
       {r.int8_conv3 && t.tfm_file,
        "P3HIP_FLAG_INT8_CONV3 serves the conv trunks (" P3HIP_CONV_SET ") whose fp16 plan runs layer by layer; the "
        "transformer trunks (" P3HIP_TRANSFORMER_SET ") have no INT8 plan"},
@@ -282,6 +300,9 @@ PlanChoice choose_plan(const WeightFile& wf, uint32_t flags, const Options& opt,
        "unsupported architecture for the HIP engine (need a conv trunk (" P3HIP_CONV_SET "), or a transformer "
        "trunk (" P3HIP_TRANSFORMER_SET "); H=32, V in {32,48,64,80} (transformer: V in {32,48,64}, and 80 at "
        "d > 256))"},
+      {k == Request::Winograd && tr == Trunk::BlockShape,
+       "P3HIP_FLAG_WINOGRAD serves the trunks whose fp16 plan runs layer by layer; the C = 256 / C_b = 128 and C = 128 / "
+       "C_b = 64 btl and nbt trunks run the fused block kernel, and a layer-wise Winograd plan for them is not built"},
       {r.int8_conv3 && tr == Trunk::BlockShape,
        "P3HIP_FLAG_INT8_CONV3 serves the trunks whose fp16 plan runs layer by layer; the C = 256 / C_b = 128 and C = 128 / "
        "C_b = 64 btl and nbt trunks run the fused block kernel, which no layer-wise plan approaches: P3HIP_FLAG_INT8_FUSED, "
@@ -311,7 +332,7 @@ PlanChoice choose_plan(const WeightFile& wf, uint32_t flags, const Options& opt,
       return c;
     }
   c.path = path_of(r, t, wf, opt);
-  c.any_width = c.path == Path::Int8Conv3 && (tr == Trunk::OtherConv || opt.conv_any);
+  c.any_width = (c.path == Path::Int8Conv3 || c.path == Path::Winograd3) && (tr == Trunk::OtherConv || opt.conv_any);
   // (layer-wise: p3::conv_any_slice(C) = 64 at classic C = 192 and at INT8_C128's C = 128, 128 at C = 384 and at
   // INT8_FUSED's C = 256)
   c.CB = is_layerwise(c.path) ? p3::conv_any_slice(C) : (is_tfm(c.path) ? 128 : Cb);
@@ -898,6 +919,22 @@ void pack_aux(Builder& b) {
   }
 }
 
+// P3HIP_FLAG_WINOGRAD: k_wconv's image of every 3x3 layer conv, behind everything else in the arena (what lies in front
+// is the fp16 plan's image of the same flags, offset for offset), from the file's fp32 weights
+void pack_wino(Builder& b) {
+  for (size_t i = 0; i < b.plan.blocks.size(); ++i) {   // (plan index = block index in the file)
+    BlockPlan& bp = b.plan.blocks[i];
+    if (bp.kind != 4) continue;
+    for (size_t j = 0; j < bp.layers.size(); ++j) {
+      LayerPlan& lp = bp.layers[j];
+      if (lp.kw != 3) continue;
+      std::vector<_Float16> img;
+      p3::pack_wconv(img, conv_w(b.wf, (int)i, (int)j, 3, lp.cin, lp.cout), lp.cin, lp.cout, lp.cin, lp.cout);
+      lp.wino_off = b.ar.add(img.data(), img.size() * 2);
+    }
+  }
+}
+
 }  // namespace
 
 // The spiral RoPE tables of python/model_transformer.py spiral_rope_cos_sin_table(num_rotations = 4, embed_dim = D,
@@ -947,6 +984,7 @@ bool build_plan(const WeightFile& wf, uint32_t flags, const Options& opt, Plan& 
   if (path == Path::Blockw) pack_blockw_runs(b);
   if (!pack_heads(b, err)) return false;
   if (flags & P3HIP_FLAG_AUX) pack_aux(b);
+  if (path == Path::Winograd3) pack_wino(b);
   if (!wf.missing.empty()) {
     err = "weight file lacks tensors of the architecture its header names: " + wf.missing;
     return false;

@@ -67,6 +67,9 @@ enum class Path {
   Int8Conv3,      // P3HIP_FLAG_INT8_CONV3 on the btl / nbt trunks whose fp16 plan is Layerwise or ConvAny: that plan's layers,
                   // the 3x3 convs through k_lconv_i8 / k_lconv_i8_any, everything else in fp16 (PlanChoice::any_width: the
                   // runtime-width kernels).  A classic trunk has only 3x3 convs and takes Int8 / Int8Any itself
+  Winograd3,      // P3HIP_FLAG_WINOGRAD on the trunks whose fp16 plan is Layerwise or ConvAny, classic included: that plan's
+                  // layers, arena and buffers, the 3x3 convs through k_wconv (conv_wino.hip) from one more weight image
+                  // per 3x3 layer (LayerPlan::wino_off), everything else the fp16 plan's kernels (PlanChoice::any_width)
   F32Conv,        // P3HIP_FLAG_FP32: every conv trunk layer by layer through conv_f32.hip
   Split,          // P3HIP_FLAG_LOW_LATENCY: every conv trunk layer by layer through k_sconv (conv_split.hip), a position
                   // split across workgroups; stem, broadcast dense and heads as ConvAny's
@@ -82,7 +85,7 @@ inline bool is_int8_fused(Path p) { return p == Path::Int8Fused256 || p == Path:
 inline bool is_int8(Path p) { return p == Path::Int8 || p == Path::Int8Any || p == Path::Int8Conv3 || is_int8_fused(p); }
 // conv blocks planned conv by conv (BlockPlan kind 4)
 inline bool is_layerwise(Path p) {
-  return p == Path::Layerwise || p == Path::ConvAny || is_int8(p) || p == Path::F32Conv || p == Path::Split;
+  return p == Path::Layerwise || p == Path::ConvAny || is_int8(p) || p == Path::Winograd3 || p == Path::F32Conv || p == Path::Split;
 }
 inline size_t act_bytes(Path p) { return is_f32(p) ? 4 : 2; }   // bytes per activation element of d_x, d_t, d_u, d_qkv
 
@@ -93,12 +96,13 @@ struct PlanChoice {
   bool heads_image = false;   // the arena holds k_headsx's weight fragments and tensor image (C <= 256, fp16)
   bool heads_fused = false;   // k_headsx runs: the head convs inside the heads kernel (P3HIP_NO_HFUSE, conv_any clear it)
   int tfm_heads = 0, tfm_D = 0;   // transformer: head count and head width (model width wf.model_C = heads x D)
-  bool any_width = false;   // Int8Conv3: the fp16 plan of this trunk is ConvAny's (a padded or runtime width, P3HIP_CONV_ANY=1)
+  bool any_width = false;   // Int8Conv3, Winograd3: the fp16 plan of this trunk is ConvAny's (a padded or runtime width, P3HIP_CONV_ANY=1)
 };
 // the stem, the broadcast blocks, the head convs and the fp16 layer convs (calibration) through conv_any.hip
 // (Split: all of these but the layer convs and the broadcast blocks' two 1x1 convs, which run through k_sconv)
 inline bool runs_conv_any(const PlanChoice& c) {
-  return c.path == Path::ConvAny || c.path == Path::Int8Any || c.path == Path::Split || (c.path == Path::Int8Conv3 && c.any_width);
+  return c.path == Path::ConvAny || c.path == Path::Int8Any || c.path == Path::Split ||
+         ((c.path == Path::Int8Conv3 || c.path == Path::Winograd3) && c.any_width);
 }
 
 const char* path_name(Path p);   // "Fused", "Int8Any", ..: the enumerator's name (p3hip_debug_plan)
@@ -141,6 +145,7 @@ struct LayerPlan {
   // Int8Conv3: on the 3x3 layers only; a 1x1 layer in front of one quantizes its output for it
   size_t q_off = 0, qs_off = 0;
   int qidx = -1;
+  size_t wino_off = 0;   // Winograd3, 3x3 layers: k_wconv's image (conv_wino.h pack_wconv), behind everything else in the arena
   int out_qidx = -1;   // Int8Conv3: the consumer's qidx where this layer stores its activated output as int8, else -1 (fp16)
 };
 

@@ -39,6 +39,7 @@ EXPORTS = [
     "p3hip_debug_plan", "p3hip_debug_act_i8",
     "p3hip_debug_split", "p3hip_debug_pack_sconv", "p3hip_debug_tfm_split", "p3hip_debug_edge_split",
     "p3hip_debug_poison", "p3hip_debug_poison_table",
+    "p3hip_debug_pack_wconv", "p3hip_debug_wconv_grid",
 ]
 
 FLAG_RUN_ALL_SLOTS = 2
@@ -51,6 +52,8 @@ FLAG_INT8_ANY = 2048   # calibrated INT8 whatever the conv trunk: the plan of on
 # else layer by layer on k_lconv_i8_any at the padded widths (include/p3hip.h, DESIGN.md section 9 "INT8 at any width")
 FLAG_INT8_CONV3 = 32768   # calibrated INT8 for the 3x3 convs of the layer-wise blocks only, every 1x1 conv in fp16 (include/p3hip.h,
 # DESIGN.md section 9 "INT8 for the 3x3 convs only"); a classic trunk takes FLAG_INT8's / FLAG_INT8_ANY's plan
+FLAG_WINOGRAD = 65536   # the 3x3 convs of the layer-wise blocks as F(2x2, 3x3) Winograd on fp16 MFMAs, everything else the fp16
+# plan's own (include/p3hip.h); no calibration, its own parity bound
 FLAG_FP32 = 256   # the conv trunks layer by layer in fp32, weights and activations included
 FLAG_FP32_TFM = 512   # the transformer trunks in fp32, weights and activations included
 FLAG_FP32_ANY = FLAG_FP32 | FLAG_FP32_TFM   # full precision whatever the trunk
@@ -606,6 +609,40 @@ def pack_sconv(w: np.ndarray, cin_pad: int, cout_pad: int) -> np.ndarray:
     if n != out.size:
         raise ValueError(f"pack_sconv: the image has {n} elements, expected {out.size}")
     return out.reshape(cout_pad // 16, cin_pad // 32, taps, 64, 8)
+
+
+def pack_wconv(w: np.ndarray, cin_pad: int, cout_pad: int) -> np.ndarray:
+    """k_wconv's weight image of the 3x3 conv w [9][cin][cout] (csrc/conv_wino.h pack_wconv) as float16
+    [cout_pad / 16][cin_pad / 32][16 planes][64][8]; no device needed."""
+    w = np.ascontiguousarray(w, np.float32)
+    taps, cin, cout = w.shape
+    if taps != 9:
+        raise ValueError("pack_wconv: a 3x3 conv has 9 taps")
+    L = lib()
+    L.p3hip_debug_pack_wconv.restype = C.c_long
+    L.p3hip_debug_pack_wconv.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_long]
+    out = np.zeros(16 * cin_pad * cout_pad, np.float16)
+    n = L.p3hip_debug_pack_wconv(w.ctypes.data, cin, cout, cin_pad, cout_pad, out.ctypes.data, out.size)
+    if n != out.size:
+        raise ValueError(f"pack_wconv: the image has {n} elements, expected {out.size}")
+    return out.reshape(cout_pad // 16, cin_pad // 32, 16, 64, 8)
+
+
+def debug_wconv_grid(npos: int, cout: int, n_cu: int = 256, unit: int = -1):
+    """How a k_wconv launch of a FLAG_WINOGRAD engine over npos positions and cout output channels is cut on a device of
+    n_cu CUs (p3hip_debug_wconv_grid, no device needed): (grid, units), and with 0 <= unit < units
+    (grid, units, first flat tile, tiles, first output channel) of that unit.  ValueError for a bad argument."""
+    L = lib()
+    L.p3hip_debug_wconv_grid.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_long), C.c_long,
+                                         C.POINTER(C.c_long), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    grid, units, t0, nt, c0 = C.c_int(0), C.c_long(0), C.c_long(0), C.c_int(0), C.c_int(0)
+    if unit < 0:
+        if L.p3hip_debug_wconv_grid(npos, cout, n_cu, C.byref(grid), C.byref(units), -1, None, None, None) != 0:
+            raise ValueError("p3hip_debug_wconv_grid: bad argument")
+        return grid.value, units.value
+    if L.p3hip_debug_wconv_grid(npos, cout, n_cu, C.byref(grid), C.byref(units), unit, C.byref(t0), C.byref(nt), C.byref(c0)) != 0:
+        raise ValueError("p3hip_debug_wconv_grid: bad argument")
+    return grid.value, units.value, t0.value, nt.value, c0.value
 
 
 def rope_table():

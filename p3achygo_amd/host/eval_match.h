@@ -101,6 +101,9 @@ struct EvalPlayerConfig {   // PlayerSearchConfig (player_config.h:20-108), same
   // split across workgroups; transformer trunks, a block's launches split across workgroups).  For players whose engines see few positions at a time: a timed search turns the forward pass's latency
   // into visits per move.
   int nn_low_latency = 0;
+  // extension: the player's engine runs the 3x3 convs of a layer-wise conv trunk as F(2x2, 3x3) Winograd
+  // (P3HIP_FLAG_WINOGRAD).  A trunk the plan does not serve ends the match with the engine's message.
+  int nn_winograd = 0;
   // extension: the player's engine takes a symmetry set per slot (P3HIP_FLAG_SYMMETRY_SLOT): every evaluation's random
   // symmetry goes to the engine as the slot's mask, features are loaded un-rotated and results come back un-rotated.
   // The games are those of host rotation.
@@ -251,6 +254,13 @@ inline bool ParsePlayerConfigStream(std::istream& in, EvalPlayerConfig* cfg, std
           return false;
         }
         cfg->nn_low_latency = val == "1";
+      }
+      else if (key == "nn_winograd") {
+        if (val != "0" && val != "1") {
+          if (err) *err = "nn_winograd must be 0 or 1: " + line;
+          return false;
+        }
+        cfg->nn_winograd = val == "1";
       }
       else if (key == "nn_device_symmetry") {
         if (val != "0" && val != "1") {

@@ -1664,7 +1664,8 @@ int p3host_eval_match(const char* engine_lib, const char* cur_weights, const cha
       auto* h = new HipEvaluator();
       ev[e].reset(h);
       const uint32_t flags = P3HIP_FLAG_SHARED_DEVICE |   // the two players' passes run concurrently
-                             (pc[e].nn_fp32 ? P3HIP_FLAG_FP32_ANY : 0u) | (pc[e].nn_low_latency ? P3HIP_FLAG_LOW_LATENCY_ANY : 0u);
+                             (pc[e].nn_fp32 ? P3HIP_FLAG_FP32_ANY : 0u) | (pc[e].nn_low_latency ? P3HIP_FLAG_LOW_LATENCY_ANY : 0u) |
+                             (pc[e].nn_winograd ? P3HIP_FLAG_WINOGRAD : 0u);
       if (!OpenEvalEngine(h, engine_lib, e == 0 ? cur_weights : cand_weights, slots, num_games, device, flags, pc[e])) {
         if (err) snprintf(err, 256, "%s", h->err.c_str());
         return 1;
@@ -1834,7 +1835,8 @@ int p3host_eval_match_threads(const char* engine_lib, const char* cur_weights, c
       // leaf and its inverse stay, since the averaged result comes back in the orientation it was loaded in
       // nn_device_symmetry / nn_root_symmetry_mask: the engine rotates, a search's root visit under the root mask
       const uint32_t flags = P3HIP_FLAG_SHARED_DEVICE |
-                             (pc[e].nn_fp32 ? P3HIP_FLAG_FP32_ANY : 0u) | (pc[e].nn_low_latency ? P3HIP_FLAG_LOW_LATENCY_ANY : 0u);
+                             (pc[e].nn_fp32 ? P3HIP_FLAG_FP32_ANY : 0u) | (pc[e].nn_low_latency ? P3HIP_FLAG_LOW_LATENCY_ANY : 0u) |
+                             (pc[e].nn_winograd ? P3HIP_FLAG_WINOGRAD : 0u);
       if (!OpenEvalEngine(h, engine_lib, e == 0 ? cur_weights : cand_weights, batch, num_games, device, flags, pc[e])) {
         if (err) snprintf(err, 256, "%s", h->err.c_str());
         return 1;
@@ -1994,6 +1996,15 @@ int p3host_parse_player_low_latency(const char* path, int* low_latency, char* er
   std::string e;
   if (!ParsePlayerConfig(path, &c, &e)) { if (err) snprintf(err, 256, "%s", e.c_str()); return 1; }
   *low_latency = c.nn_low_latency;
+  return 0;
+}
+
+// the nn_winograd of a player config file (tests): 0 and the value, or 1 with the parser's message
+int p3host_parse_player_winograd(const char* path, int* winograd, char* err) {
+  EvalPlayerConfig c;
+  std::string e;
+  if (!ParsePlayerConfig(path, &c, &e)) { if (err) snprintf(err, 256, "%s", e.c_str()); return 1; }
+  *winograd = c.nn_winograd;
   return 0;
 }
 

@@ -5,7 +5,7 @@ For one net and N positions of features.random_positions, runs the fp32 engine (
 the net's trunk, conv or transformer; a transformer's only other plan is fp16), the fp16 engine and
 every INT8 plan that serves the net (P3HIP_FLAG_INT8, _INT8_FUSED, _INT8_C128: the ones p3hip_create accepts, calibrated
 on the same positions; where none of the three does, P3HIP_FLAG_INT8_ANY's own layer-wise plan, row "int8_any"; P3HIP_FLAG_INT8_CONV3 where it
-has a plan of its own, row "int8_conv3"), and prints one JSON line per plan: its largest and mean deviation from the fp32 engine in the raw
+has a plan of its own, row "int8_conv3"; P3HIP_FLAG_WINOGRAD where it serves the net, row "winograd", uncalibrated), and prints one JSON line per plan: its largest and mean deviation from the fp32 engine in the raw
 outputs and in the move, value and score probabilities, and the largest and mean KL(fp32 || plan) of the move, value and
 score distributions.  --out writes the lines (default profiles/precision_report.jsonl); --append adds them to the file.
 
@@ -66,7 +66,8 @@ def main():
         ref = evaluate(eng, pos, args.batch)
         eng.close()
         plans = [("fp16", 0), ("int8", engine.FLAG_INT8), ("int8_fused", engine.FLAG_INT8_FUSED), ("int8_c128", engine.FLAG_INT8_C128),
-                 ("int8_any", engine.FLAG_INT8_ANY), ("int8_conv3", engine.FLAG_INT8_CONV3)]
+                 ("int8_any", engine.FLAG_INT8_ANY), ("int8_conv3", engine.FLAG_INT8_CONV3),
+                 ("winograd", engine.FLAG_WINOGRAD)]
         for label, flag in plans:
             # (on a trunk one of the three other INT8 flags serves, INT8_ANY is that flag's plan bit for bit: no second row)
             if label == "int8_any" and any(x["plan"].startswith("int8") for x in lines):
@@ -82,7 +83,7 @@ def main():
                 eng = engine.HipEngine(path, args.batch, flags=flag)
             except engine.EngineError:
                 continue   # the plan does not serve this net
-            if flag:
+            if flag and label != "winograd":   # (P3HIP_FLAG_WINOGRAD needs no calibration)
                 for i in range(0, len(pos), args.batch):
                     part = pos[i:i + args.batch]
                     eng.load_all(part)
