@@ -1,5 +1,6 @@
-// block_i8.h — arguments and launchers of the fused INT8 block kernels: C = 256 / C_b = 128 btl trunks (block_i8.hip,
-// P3HIP_FLAG_INT8_FUSED) and C = 128 / C_b = 64 btl trunks (block_i8_c128.hip, P3HIP_FLAG_INT8_C128).
+// block_i8.h — arguments and launcher of the fused INT8 block kernel (block_i8.hip, k_block_i8): C = 256 / C_b = 128 btl
+// trunks (geometry <256,128>, P3HIP_FLAG_INT8_FUSED) and C = 128 / C_b = 64 btl trunks (geometry <128,64>,
+// P3HIP_FLAG_INT8_C128).
 // Numerics: DESIGN.md section 9 "Fused INT8 blocks".
 #pragma once
 #include <hip/hip_runtime.h>
@@ -27,11 +28,9 @@ struct BlockI8Args {
   int q0;
 };
 
-hipError_t launch_block_i8(const BlockI8Args& a, int n_cu, hipStream_t s);
-const char* block_i8_kernel_name();
-
-// the same block at C = 128 / C_b = 64: 256-thread workgroups, two per CU
-hipError_t launch_block_i8_c128(const BlockI8Args& a, int n_cu, hipStream_t s);
-const char* block_i8_c128_kernel_name();
+// C = 256: 512-thread workgroups, one per CU; C = 128: 256-thread workgroups, two per CU; any other C is
+// hipErrorInvalidValue (and has no name)
+hipError_t launch_block_i8(int C, const BlockI8Args& a, int n_cu, hipStream_t s);
+const char* block_i8_kernel_name(int C);   // "k_block_i8<256,128>", "k_block_i8<128,64>"
 
 }  // namespace p3

@@ -946,7 +946,7 @@ double p3hip_time_trunk_kernel(p3hip_engine* e, int n_positions, int iters,
     case Path::Int8Fused256:
     case Path::Int8Fused128:
       flops = 2.0 * n_positions * kNLoc * block_macs;
-      name = path == Path::Int8Fused128 ? p3::block_i8_c128_kernel_name() : p3::block_i8_kernel_name();
+      name = p3::block_i8_kernel_name(wf.C);
       break;
     case Path::F32Conv:
     case Path::ConvAny:

@@ -65,7 +65,7 @@ struct p3hip_engine {
   // scales.  amax: running per-tensor maxima of the calibration runs (float bits, atomicMax); scale: the s_a = max / 127
   // the int8 kernels read at launch time, so that a replayed graph sees new scales.  Int8Fused256 / Int8Fused128
   // ("Fused INT8 blocks"): the btl blocks are planned layer by layer (the fp16 plan the calibration runs, at C = 128
-  // through k_lconv_any) and run as one k_block_i8 launch each.
+  // through k_lconv_any) and run as one k_block_i8 launch each (block_i8.hip, one kernel at two geometries).
   bool calibrating = false, have_scales = false;
   unsigned* d_amax = nullptr;
   float* d_ascale = nullptr;

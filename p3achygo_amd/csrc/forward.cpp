@@ -460,10 +460,7 @@ bool enqueue_block_i8(p3hip_engine* e, const Pass& p, const BlockPlan& bp) {
     const FoldedBN& bn = j == 0 ? lp.pre_bn : bp.layers[j - 1].out_bn;
     a.scale[j] = e->dev<float>(bn.scale_off); a.shift[j] = e->dev<float>(bn.shift_off);
   }
-  auto launch = [&] {
-    return e->check(e->trunk_path() == Path::Int8Fused128 ? p3::launch_block_i8_c128(a, e->n_cu, e->stream)
-                                                    : p3::launch_block_i8(a, e->n_cu, e->stream), "launch k_block_i8");
-  };
+  auto launch = [&] { return e->check(p3::launch_block_i8(e->wf.C, a, e->n_cu, e->stream), "launch k_block_i8"); };
   return timed_launch(e, p.timed, launch);
 }
 

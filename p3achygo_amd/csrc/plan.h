@@ -61,7 +61,7 @@ enum class Path {
   ConvAny,        // conv_any.hip, widths as launch arguments: every other trunk of P3HIP_CONV_SET (and P3HIP_CONV_ANY=1)
   Int8,           // P3HIP_FLAG_INT8: k_lconv_i8 on the templated layer-wise shapes
   Int8Fused256,   // P3HIP_FLAG_INT8_FUSED: k_block_i8 per btl block at C = 256 / C_b = 128
-  Int8Fused128,   // P3HIP_FLAG_INT8_C128: the same at C = 128 / C_b = 64 (block_i8_c128.hip)
+  Int8Fused128,   // P3HIP_FLAG_INT8_C128: the same at C = 128 / C_b = 64 (block_i8.hip, geometry <128,64>)
   Int8Any,        // P3HIP_FLAG_INT8_ANY on every trunk the three above do not serve: k_lconv_i8_any, widths as launch
                   // arguments; stem, broadcast blocks and heads as ConvAny's
   Int8Conv3,      // P3HIP_FLAG_INT8_CONV3 on the btl / nbt trunks whose fp16 plan is Layerwise or ConvAny: that plan's layers,

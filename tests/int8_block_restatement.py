@@ -1,9 +1,16 @@
-"""CPU emulation of the fused INT8 blocks (P3HIP_FLAG_INT8_FUSED, DESIGN.md section 9 "Fused INT8 blocks").
+"""CPU emulation of the fused INT8 blocks (P3HIP_FLAG_INT8_FUSED and P3HIP_FLAG_INT8_C128, DESIGN.md section 9 "Fused
+INT8 blocks").
 
-TEST INFRASTRUCTURE ONLY: used by tests/test_int8_block_cpu.py and tests/test_int8_block_gpu.py.  The quantizer, the
-conv of one quantized layer (`_Q`), the error measures and the calibration set come from tests/int8_restatement.py.
+TEST INFRASTRUCTURE ONLY: used by tests/test_int8_block_cpu.py and tests/test_int8_block_gpu.py, and at C = 128 through
+tests/int8_block_c128.py.  The quantizer, the conv of one quantized layer (`_Q`), the error measures and the calibration
+set come from tests/int8_restatement.py.
 
-The scheme of section 9 on the C = 256 / C_b = 128 btl trunks, where a block depends on the stored fp16 x alone:
+The emulation takes the width from `cfg`; the served set is a parameter, `widths`: a (C, C_b) pair.  This module's own
+is that of P3HIP_FLAG_INT8_FUSED, with its fixtures (SERVED) and bounds (BOUNDS); tests/int8_block_c128.py holds those of
+P3HIP_FLAG_INT8_C128.
+
+The scheme of section 9 on the C = 256 / C_b = 128 and C = 128 / C_b = 64 btl trunks, where a block depends on the
+stored fp16 x alone:
   a0 = q(mish(bn0(x16)));  conv j: exact integer accumulation, y = (float) acc * float32(s_a * s_w[c]);
   reduce and inner convs hand q(mish(bn_{j+1}(y))) on;  the expand conv gives x <- fp16((float) x16 + y).
 The init conv, the broadcast blocks (t and u stored in fp16), the heads and x are the fp16 engine's.  Calibration
@@ -27,6 +34,8 @@ import tfm_restatement  # noqa: E402
 
 DT = torch.float64
 
+WIDTHS = (256, 128)   # (C, C_b) of the trunks P3HIP_FLAG_INT8_FUSED serves
+
 # the trunks P3HIP_FLAG_INT8_FUSED serves among the fixtures
 SERVED = ("test_b3c256btl1", "test_b5c256btl2_i2", "test_b10c256btl1_i2", "b12c256btl3")
 
@@ -44,14 +53,13 @@ BOUNDS = {
 }
 
 
-def is_served(cfg) -> bool:
-    return cfg.channels == 256 and cfg.bottleneck_channels == 128 and cfg.block_type == "btl" and \
-        1 <= cfg.inner_layers <= 3
+def is_served(cfg, widths=WIDTHS) -> bool:
+    return (cfg.channels, cfg.bottleneck_channels) == widths and cfg.block_type == "btl" and 1 <= cfg.inner_layers <= 3
 
 
-def quantized_tensors(cfg) -> List[str]:
+def quantized_tensors(cfg, widths=WIDTHS) -> List[str]:
     """Names of the quantized tensors in the engine's order: block by block, conv by conv (the input of conv j)."""
-    if not is_served(cfg):
+    if not is_served(cfg, widths):
         return []
     return [f"blocks.{i}.conv{j}.in" for i in range(cfg.blocks) if cfg.block_kind(i) != "broadcast"
             for j in range(cfg.inner_layers + 2)]
@@ -80,20 +88,21 @@ def btl_block(cfg, k, x, Q):
 
 
 def block(cfg, W, k, x_in, scales_k=None):
-    """Teacher-forced: btl block k alone from x_in ([n, 256, 361] or [n, 256, 19, 19]); scales_k: its
+    """Teacher-forced: btl block k alone from x_in ([n, C, 361] or [n, C, 19, 19]); scales_k: its
     (inner layers + 2) activation scales, or None for the unquantized fp16 block (activated tensors stored in fp16,
-    fp16 weights).  Returns [n, 256, 19, 19] float64."""
+    fp16 weights).  Returns [n, C, 19, 19] float64."""
     x = torch.from_numpy(np.asarray(x_in, np.float64).reshape(len(x_in), cfg.channels, 19, 19))
     return btl_block(cfg, k, x, _Q(W, scales_k, None)).numpy()
 
 
-def forward(cfg, W: Dict[str, np.ndarray], planes_nhwc, feats, scales=None, observe: Optional[list] = None):
-    """The INT8_FUSED engine's forward pass with `scales`, or (scales None) the fp16 plan it calibrates on with
+def forward(cfg, W: Dict[str, np.ndarray], planes_nhwc, feats, scales=None, observe: Optional[list] = None,
+            widths=WIDTHS):
+    """The fused INT8 engine's forward pass with `scales`, or (scales None) the fp16 plan it calibrates on with
     `observe` collecting the calibration maxima.  Outputs as oracle/torch_restatement.forward."""
-    assert is_served(cfg), cfg.name
+    assert is_served(cfg, widths), cfg.name
     W = fp16_weights(cfg, W)
     if scales is not None:
-        assert len(scales) == len(quantized_tensors(cfg))
+        assert len(scales) == len(quantized_tensors(cfg, widths))
     Q = _Q(W, scales, observe)
     x = tr._t(planes_nhwc, DT).permute(0, 3, 1, 2)
     gs = tr._dense(tr._t(feats, DT), W, "init_game", DT)
@@ -110,12 +119,12 @@ def forward(cfg, W: Dict[str, np.ndarray], planes_nhwc, feats, scales=None, obse
     return tfm_restatement._heads(x, W, x.permute(0, 2, 3, 1), DT)
 
 
-def minmax_scales(cfg, W, batches) -> np.ndarray:
+def minmax_scales(cfg, W, batches, widths=WIDTHS) -> np.ndarray:
     """MinMax calibration over `batches` of (planes, scalars): s_a = max over all batches / 127, engine order."""
     amax = None
     for planes, sc in batches:
         obs: list = []
-        forward(cfg, W, planes, sc, scales=None, observe=obs)
+        forward(cfg, W, planes, sc, scales=None, observe=obs, widths=widths)
         a = np.asarray(obs, np.float32)
         amax = a if amax is None else np.maximum(amax, a)
     return (amax / np.float32(127)).astype(np.float32)

@@ -16,16 +16,15 @@ Measured on one MI355X (test_blocks_teacher_forced, the ratio per layer-wise blo
 net, batch and block but the first block of test_b3c320nbt at batch 1, 0.129; heads max |d| 2.3e-6.  Whole nets, largest
 move-logit error to float64: 0.009 (test_b3c64btl2) to 0.053 (test_b3c128nbt), 0.25 - 0.34 of the bounds."""
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from conftest import ROOT  # noqa: E402
 import conv_widths_common as cw  # noqa: E402
 import int8_any_restatement as ar  # noqa: E402
+import int8_gpu_common as gc  # noqa: E402
 import trunk_emulation as te  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -56,77 +55,14 @@ def files(tmp_path_factory):
     return get
 
 
-def _flag():
-    from p3achygo_amd import engine
-    return engine.FLAG_INT8_ANY
-
-
-def _calibrated(path, batch, flags=0):
-    from p3achygo_amd import engine
-    eng = engine.HipEngine(path, batch, flags=_flag() | flags)
-    for cal in ar.calibration_batches():
-        assert len(cal) <= batch
-        eng.load_all(cal)
-        eng.int8_calibrate()
-        for i in range(len(cal)):
-            eng.GetBatch(i)
-    return eng
-
-
-_SCALES = {}
-
-
-def _scales(path):
-    """The calibrated scales of the net at `path` (one calibration per file and session)."""
-    if path not in _SCALES:
-        eng = _calibrated(path, 16)
-        _SCALES[path] = eng.int8_scales()
-        eng.close()
-    return _SCALES[path]
-
-
-def _with_scales(path, batch, flags=0):
-    from p3achygo_amd import engine
-    eng = engine.HipEngine(path, batch, flags=_flag() | flags)
-    eng.set_int8_scales(_scales(path))
-    return eng
-
-
-def _fetch(eng, slots):
-    raw = np.stack([eng.get_raw(s) for s in slots])
-    res = [eng.GetBatch(s) for s in slots]
-    return {"raw": raw,
-            "move_probs": np.stack([np.ctypeslib.as_array(r.move_probs) for r in res]).astype(np.float64),
-            "value_probs": np.stack([np.ctypeslib.as_array(r.value_probs) for r in res]).astype(np.float64)}
-
-
-def _run(eng, pos, slots=None):
-    slots = list(range(len(pos))) if slots is None else slots
-    for k, s in enumerate(slots):
-        eng.LoadBatch(s, pos[k:k + 1])
-    eng.RunInference()
-    return _fetch(eng, slots)
-
+_E = gc.Engines("FLAG_INT8_ANY", raw_f64=False)
+_flag, _calibrated, _scales, _with_scales, _fetch, _run = _E.flag, _E.calibrated, _E.scales, _E.with_scales, _E.fetch, _E.run
 
 _FAILED = []
 
 
 def _child(script, args, env_extra=None):
-    """One child process under its own time limit, nothing retried; once one failed no further one is started."""
-    if _FAILED:
-        pytest.fail("an earlier child failed: no further GPU process is started (%s)" % _FAILED[0])
-    env = {k: v for k, v in os.environ.items()
-           if k not in ("P3HIP_NO_HFUSE", "P3HIP_NO_FUSE", "P3HIP_NO_BFUSE", "P3HIP_DEBUG_STOP_BLOCK", "P3HIP_CONV_ANY")}
-    env.update(env_extra or {})
-    try:
-        r = subprocess.run([sys.executable, "-c", script % ROOT] + [str(a) for a in args], env=env, capture_output=True,
-                           text=True, timeout=CHILD_TIMEOUT)
-    except subprocess.TimeoutExpired:
-        _FAILED.append("time limit")
-        raise
-    if r.returncode != 0:
-        _FAILED.append("exit %d" % r.returncode)
-    assert r.returncode == 0, r.stderr[-3000:]
+    gc.child(script, args, _FAILED, CHILD_TIMEOUT, env_extra)
 
 
 # ---- 1. blocks, teacher-forced ---------------------------------------------------------------------------------------

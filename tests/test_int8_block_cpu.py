@@ -1,7 +1,7 @@
 """Fused INT8 blocks of the C = 256 btl trunks (P3HIP_FLAG_INT8_FUSED), without a GPU: the quantized tensors of the
 served configs, the architecture check at create, the CPU emulation's own error against the float64 goldens
 (tests/int8_block_restatement.py), the teacher-forced block criterion of the GPU test on stand-ins, and the compiled
-resources of the block kernel (csrc/block_i8.hip)."""
+resources of the block kernel (csrc/block_i8.hip, k_block_i8 at geometry <256,128>)."""
 import os
 import re
 import subprocess
@@ -153,30 +153,37 @@ def test_block_criterion_separates_a_faithful_engine_from_one_with_wrong_scales(
 
 
 def _resources():
+    """name -> (VGPRs, scratch bytes, LDS bytes, MFMAs, scratch instructions) of every k_block_i8 of geometry G256 (the
+    mangled name carries the geometry struct) in the unit, from the kernel descriptors the build's compiler writes."""
     r = subprocess.run(["hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S",
                         os.path.join(CSRC, "block_i8.hip"), "-o", "-"], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     asm = r.stdout
     out = {}
-    for m in re.finditer(r"^\s*\.amdhsa_kernel\s+(\S*k_block_i8\S*)\s*$", asm, re.M):
+    for m in re.finditer(r"^\s*\.amdhsa_kernel\s+(\S*k_block_i8\S*G256\S*)\s*$", asm, re.M):
         name = m.group(1)
         desc = asm[m.start():asm.index(".end_amdhsa_kernel", m.start())]
         vg = int(re.search(r"\.amdhsa_next_free_vgpr\s+(\d+)", desc).group(1))
         scratch = int(re.search(r"\.amdhsa_private_segment_fixed_size\s+(\d+)", desc).group(1))
+        lds = int(re.search(r"\.amdhsa_group_segment_fixed_size\s+(\d+)", desc).group(1))
         start = re.search(r"^" + re.escape(name) + r":", asm, re.M).start()
         body = asm[start:asm.index(".Lfunc_end", start)]
-        out[name] = (vg, scratch, body.count("v_mfma_i32_16x16x64_i8"), "scratch_" in body)
+        out[name] = (vg, scratch, lds, body.count("v_mfma_i32_16x16x64_i8"), "scratch_" in body)
     return out
 
 
 def test_block_kernel_fits_two_waves_per_simd_without_scratch():
     res = _resources()
     assert len(res) == 3, sorted(res)               # one, two and three inner layers
-    for name, (vg, scratch, mfma, uses_scratch) in res.items():
+    for name, (vg, scratch, lds, mfma, uses_scratch) in res.items():
         assert scratch == 0 and not uses_scratch, name
         # one 512-thread workgroup per CU = two waves per SIMD: at most 256 VGPRs (arch + acc) a wave
         assert vg <= 256, (name, vg)
+        assert lds == 0, (name, lds)                # 112,896 B do not fit a static array: all of it is dynamic LDS
         assert mfma > 0, name
     src = open(os.path.join(CSRC, "block_i8.hip")).read()
-    assert re.search(r"static_assert\(kLdsBytes <= 160 \* 1024", src)   # the two images within the CU's LDS
-    assert "constexpr int kLdsBytes = 2 * kImageBytes;" in src
+    # the CU's workgroups (one at this geometry) within its LDS, and the LDS both images of a position
+    assert re.search(r"static_assert\(G::kWgPerCu \* kLdsBytes <= 160 \* 1024", src)
+    assert "constexpr int kLdsBytes = (C / 16) * kGroupBytes;" in src and "constexpr int kImgB = (CB / 16) * kGroupBytes;" in src
+    assert "static_assert(C == 2 * CB" in src       # so kLdsBytes is two images of kImgB
+    assert re.search(r"struct G256 \{ static constexpr int C = 256, CB = 128, kWaves = 8, kWgPerCu = 1; \};", src)

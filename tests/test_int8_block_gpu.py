@@ -18,6 +18,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from conftest import ROOT, load_golden  # noqa: E402
 import int8_block_restatement as br  # noqa: E402
+import int8_gpu_common as gc  # noqa: E402
 import trunk_emulation as te  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -27,73 +28,9 @@ BLOCK_JOBS = [("test_b3c256btl1", 1), ("test_b5c256btl2_i2", 37), ("test_b10c256
 RATIO_BOUND = 0.5
 
 
-def _flag():
-    from p3achygo_amd import engine
-    return engine.FLAG_INT8_FUSED
-
-
-def _calibrated(path, batch, flags=0):
-    from p3achygo_amd import engine
-    eng = engine.HipEngine(path, batch, flags=_flag() | flags)
-    for cal in br.calibration_batches():
-        assert len(cal) <= batch
-        eng.load_all(cal)
-        eng.int8_calibrate()
-        for i in range(len(cal)):
-            eng.GetBatch(i)
-    return eng
-
-
-_SCALES = {}
-
-
-def _scales(path):
-    """The calibrated scales of the net at `path` (one calibration per file and session)."""
-    if path not in _SCALES:
-        eng = _calibrated(path, 16)
-        _SCALES[path] = eng.int8_scales()
-        eng.close()
-    return _SCALES[path]
-
-
-def _with_scales(path, batch, flags=0):
-    from p3achygo_amd import engine
-    eng = engine.HipEngine(path, batch, flags=_flag() | flags)
-    eng.set_int8_scales(_scales(path))
-    return eng
-
-
-def _fetch(eng, slots):
-    raw = np.stack([eng.get_raw(s) for s in slots])
-    res = [eng.GetBatch(s) for s in slots]
-    return {"raw": raw.astype(np.float64),
-            "move_probs": np.stack([np.ctypeslib.as_array(r.move_probs) for r in res]).astype(np.float64),
-            "value_probs": np.stack([np.ctypeslib.as_array(r.value_probs) for r in res]).astype(np.float64)}
-
-
-def _run(eng, pos, slots=None):
-    """outputs of `pos` loaded at `slots` (default 0..n-1) as arrays like the goldens"""
-    slots = list(range(len(pos))) if slots is None else slots
-    for k, s in enumerate(slots):
-        eng.LoadBatch(s, pos[k:k + 1])
-    eng.RunInference()
-    return _fetch(eng, slots)
-
-
-def _weights(name, peak=0.0):
-    from p3achygo_amd import netspec
-    cfg = netspec.CONFIGS[name]
-    W = netspec.generate_weights(cfg, randomize=True)
-    return cfg, (netspec.peak_policy(W, peak) if peak else W)
-
-
-def _oracle(path, pos):
-    from oracle import oracle
-    net = oracle.OracleNet(path)
-    res, raw = net.forward_features(pos)
-    return net, {"raw": np.asarray(raw, np.float64),
-                 "move_probs": np.stack([np.ctypeslib.as_array(r.move_probs) for r in res]).astype(np.float64),
-                 "value_probs": np.stack([np.ctypeslib.as_array(r.value_probs) for r in res]).astype(np.float64)}
+_E = gc.Engines("FLAG_INT8_FUSED", raw_f64=True)
+_flag, _calibrated, _scales, _with_scales, _fetch, _run = _E.flag, _E.calibrated, _E.scales, _E.with_scales, _E.fetch, _E.run
+_weights, _oracle, _job_batch = gc.weights, gc.oracle_outputs, gc.job_batch
 
 
 @pytest.mark.parametrize("name", br.SERVED)
@@ -152,18 +89,6 @@ for key in d["keys"]:
         eng.close()
 np.savez(sys.argv[2], **out)
 """
-
-
-def _job_batch(name, batch):
-    """Positions of a job: the fixture's first positions scattered among seeded fill; the compared slots."""
-    from p3achygo_amd import features
-    _, gpos = load_golden(name)
-    special = gpos[:min(4, batch)]
-    pos = features.random_positions(batch, seed=43, n_games=16, max_moves=300, komis=(7.5, -7.5, 0.5))
-    at = [int(s) for s in np.linspace(0, batch - 1, len(special)).round()] if batch > 1 else [0]
-    pos[at] = special[:len(at)]
-    slots = sorted(set(at) | set(range(5, batch, 97)) | {batch - 1})
-    return pos, np.asarray(slots)
 
 
 @pytest.mark.parametrize("name,batch", BLOCK_JOBS)

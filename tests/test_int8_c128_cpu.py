@@ -1,7 +1,7 @@
 """Fused INT8 blocks of the C = 128 / C_b = 64 btl trunks (P3HIP_FLAG_INT8_C128), without a GPU: the flag, the
 architecture check at create, the quantized tensors of the served configs, the CPU emulation's own error against the
 float64 goldens (tests/int8_block_c128.py), the teacher-forced block criterion of the GPU test on stand-ins at this
-width, and the compiled resources of the block kernel (csrc/block_i8_c128.hip)."""
+width, and the compiled resources of the block kernel (csrc/block_i8.hip, k_block_i8 at geometry <128,64>)."""
 import itertools
 import os
 import re
@@ -168,14 +168,14 @@ def test_block_criterion_separates_a_faithful_engine_from_one_with_wrong_scales(
 
 
 def _resources():
-    """name -> (VGPRs, scratch bytes, LDS bytes, MFMAs, scratch instructions) of every k_block_i8 in the unit, from the
-    kernel descriptors the build's compiler writes."""
+    """name -> (VGPRs, scratch bytes, LDS bytes, MFMAs, scratch instructions) of every k_block_i8 of geometry G128 (the
+    mangled name carries the geometry struct) in the unit, from the kernel descriptors the build's compiler writes."""
     r = subprocess.run(["hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S",
-                        os.path.join(CSRC, "block_i8_c128.hip"), "-o", "-"], capture_output=True, text=True)
+                        os.path.join(CSRC, "block_i8.hip"), "-o", "-"], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     asm = r.stdout
     out = {}
-    for m in re.finditer(r"^\s*\.amdhsa_kernel\s+(\S*k_block_i8\S*)\s*$", asm, re.M):
+    for m in re.finditer(r"^\s*\.amdhsa_kernel\s+(\S*k_block_i8\S*G128\S*)\s*$", asm, re.M):
         name = m.group(1)
         desc = asm[m.start():asm.index(".end_amdhsa_kernel", m.start())]
         vg = int(re.search(r"\.amdhsa_next_free_vgpr\s+(\d+)", desc).group(1))
@@ -195,8 +195,14 @@ def test_block_kernel_keeps_two_workgroups_per_cu_and_no_scratch():
         # two 256-thread workgroups per CU = two waves per SIMD: at most 256 VGPRs (arch + acc) a wave
         assert vg <= 256, (name, vg)
         # ... and half of the CU's 160 KiB of LDS each; the image is a static array, so this is all the kernel uses
-        assert 0 < lds <= 81920, (name, lds)
+        assert lds == 56448 and lds <= 81920, (name, lds)
         assert mfma > 0, name
-    src = open(os.path.join(CSRC, "block_i8_c128.hip")).read()
-    assert "__shared__" in src and "extern __shared__" not in src   # no dynamic LDS on top of the descriptor's
-    assert re.search(r"dim3\(kWgC128\), 0, s, a\)", src)
+    src = open(os.path.join(CSRC, "block_i8.hip")).read()
+    # no dynamic LDS on top of the descriptor's: a geometry whose LDS fits a static array takes the static one in the
+    # kernel and passes 0 dynamic bytes at launch, 256 threads a workgroup
+    assert re.search(r"if constexpr \(kBytes <= kStaticLdsMax\) \{\s*__shared__ [^;]*\bsmem\[kBytes\];\s*return smem;", src)
+    assert "constexpr int kDynLds = kLdsBytes <= kStaticLdsMax ? 0 : kLdsBytes;" in src
+    assert re.search(r"dim3\(64 \* G::kWaves\), kDynLds, s, a\)", src)
+    assert "constexpr int kStaticLdsMax = 64 * 1024;" in src
+    assert re.search(r"struct G128 \{ static constexpr int C = 128, CB = 64, kWaves = 4, kWgPerCu = 2; \};", src)
+    assert re.search(r"static_assert\(G::kWgPerCu \* kLdsBytes <= 160 \* 1024", src)   # two workgroups within the CU's LDS

@@ -20,17 +20,16 @@ the btl nets, 0.005 - 0.311 on the nbt nets (the largest: the second block of te
 the bounds."""
 import ctypes
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from conftest import ROOT  # noqa: E402
 import conv_widths_common as cw  # noqa: E402
 import int8_any_restatement as ar  # noqa: E402
 import int8_conv3_restatement as c3  # noqa: E402
+import int8_gpu_common as gc  # noqa: E402
 import trunk_emulation as te  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -88,77 +87,14 @@ def second_position_batch(cfg, n_cu):
     return cap // ncp + 1
 
 
-def _flag():
-    from p3achygo_amd import engine
-    return engine.FLAG_INT8_CONV3
-
-
-def _calibrated(path, batch, flags=None):
-    from p3achygo_amd import engine
-    eng = engine.HipEngine(path, batch, flags=_flag() if flags is None else flags)
-    for cal in c3.calibration_batches():
-        assert len(cal) <= batch
-        eng.load_all(cal)
-        eng.int8_calibrate()
-        for i in range(len(cal)):
-            eng.GetBatch(i)
-    return eng
-
-
-_SCALES = {}
-
-
-def _scales(path):
-    """The calibrated scales of the net at `path` (one calibration per file and session)."""
-    if path not in _SCALES:
-        eng = _calibrated(path, 16)
-        _SCALES[path] = eng.int8_scales()
-        eng.close()
-    return _SCALES[path]
-
-
-def _with_scales(path, batch, flags=0):
-    from p3achygo_amd import engine
-    eng = engine.HipEngine(path, batch, flags=_flag() | flags)
-    eng.set_int8_scales(_scales(path))
-    return eng
-
-
-def _fetch(eng, slots):
-    raw = np.stack([eng.get_raw(s) for s in slots])
-    res = [eng.GetBatch(s) for s in slots]
-    return {"raw": raw,
-            "move_probs": np.stack([np.ctypeslib.as_array(r.move_probs) for r in res]).astype(np.float64),
-            "value_probs": np.stack([np.ctypeslib.as_array(r.value_probs) for r in res]).astype(np.float64)}
-
-
-def _run(eng, pos, slots=None):
-    slots = list(range(len(pos))) if slots is None else slots
-    for k, s in enumerate(slots):
-        eng.LoadBatch(s, pos[k:k + 1])
-    eng.RunInference()
-    return _fetch(eng, slots)
-
+_E = gc.Engines("FLAG_INT8_CONV3", raw_f64=False)
+_flag, _calibrated, _scales, _with_scales, _fetch, _run = _E.flag, _E.calibrated, _E.scales, _E.with_scales, _E.fetch, _E.run
 
 _FAILED = []
 
 
 def _child(script, args, env_extra=None):
-    """One child process under its own time limit, nothing retried; once one failed no further one is started."""
-    if _FAILED:
-        pytest.fail("an earlier child failed: no further GPU process is started (%s)" % _FAILED[0])
-    env = {k: v for k, v in os.environ.items()
-           if k not in ("P3HIP_NO_HFUSE", "P3HIP_NO_FUSE", "P3HIP_NO_BFUSE", "P3HIP_DEBUG_STOP_BLOCK", "P3HIP_CONV_ANY")}
-    env.update(env_extra or {})
-    try:
-        r = subprocess.run([sys.executable, "-c", script % ROOT] + [str(a) for a in args], env=env, capture_output=True,
-                           text=True, timeout=CHILD_TIMEOUT)
-    except subprocess.TimeoutExpired:
-        _FAILED.append("time limit")
-        raise
-    if r.returncode != 0:
-        _FAILED.append("exit %d" % r.returncode)
-    assert r.returncode == 0, r.stderr[-3000:]
+    gc.child(script, args, _FAILED, CHILD_TIMEOUT, env_extra)
 
 
 # ---- 1. blocks, teacher-forced ---------------------------------------------------------------------------------------
@@ -433,7 +369,7 @@ def test_calibrated_scales_match_the_emulation_and_repeat_bit_for_bit(built, fil
     # the engine calibrates on its fp16 plan: equal within a few fp16 roundings of the maxima (tests/test_int8_any_gpu.py)
     np.testing.assert_allclose(sa, want, rtol=4e-3, atol=0)
     # the runtime-width nets: the 3x3 entries of the INT8_ANY engine's scales, bit for bit
-    e = _calibrated(files(name), 16, flags=engine.FLAG_INT8_ANY)
+    e = _calibrated(files(name), 16, flags=engine.FLAG_INT8_ANY, own=False)
     se = e.int8_scales()
     e.close()
     every = ar.quantized_tensors(cfg)

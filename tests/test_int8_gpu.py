@@ -13,6 +13,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from conftest import load_golden  # noqa: E402
+import int8_gpu_common as gc  # noqa: E402
 import int8_restatement as ir  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -20,45 +21,9 @@ pytestmark = pytest.mark.gpu
 GOLDEN = ("test_b3c384btl3", "test_b3c384nbt", "test_b3c192classic", "b14c384btl3", "b10c384nbt")
 
 
-def _calibrated(path, batch, flags=0):
-    from p3achygo_amd import engine
-    eng = engine.HipEngine(path, batch, flags=engine.FLAG_INT8 | flags)
-    for cal in ir.calibration_batches():
-        assert len(cal) <= batch
-        eng.load_all(cal)
-        eng.int8_calibrate()
-        for i in range(len(cal)):
-            eng.GetBatch(i)
-    return eng
-
-
-def _run(eng, pos, slots=None):
-    """outputs of `pos` loaded at `slots` (default 0..n-1) as arrays like the goldens"""
-    slots = list(range(len(pos))) if slots is None else slots
-    for k, s in enumerate(slots):
-        eng.LoadBatch(s, pos[k:k + 1])
-    eng.RunInference()
-    raw = np.stack([eng.get_raw(s) for s in slots])
-    res = [eng.GetBatch(s) for s in slots]
-    return {"raw": raw.astype(np.float64),
-            "move_probs": np.stack([np.ctypeslib.as_array(r.move_probs) for r in res]).astype(np.float64),
-            "value_probs": np.stack([np.ctypeslib.as_array(r.value_probs) for r in res]).astype(np.float64)}
-
-
-def _weights(name, peak=0.0):
-    from p3achygo_amd import netspec
-    cfg = netspec.CONFIGS[name]
-    W = netspec.generate_weights(cfg, randomize=True)
-    return cfg, (netspec.peak_policy(W, peak) if peak else W)
-
-
-def _oracle(path, pos):
-    from oracle import oracle
-    net = oracle.OracleNet(path)
-    res, raw = net.forward_features(pos)
-    return net, {"raw": np.asarray(raw, np.float64),
-                 "move_probs": np.stack([np.ctypeslib.as_array(r.move_probs) for r in res]).astype(np.float64),
-                 "value_probs": np.stack([np.ctypeslib.as_array(r.value_probs) for r in res]).astype(np.float64)}
+_E = gc.Engines("FLAG_INT8", raw_f64=True)
+_calibrated, _run = _E.calibrated, _E.run
+_weights, _oracle = gc.weights, gc.oracle_outputs
 
 
 @pytest.mark.parametrize("name", GOLDEN)

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Are the kernels of two builds the same code?  CPU only.
 
-    tools/kernel_text_diff.py OLD NEW [--rename REGEX=REPL ...] [--show N]
+    tools/kernel_text_diff.py OLD [OLD ...] NEW [--rename REGEX=REPL ...] [--show N]
 
 OLD and NEW are AMDGPU assembly files (.s), or .hip files, which are compiled with
     hipcc -O3 -std=c++17 --offload-arch=gfx950 --cuda-device-only -S
+Several OLD files pool their kernels, so that two files can be held against the one that replaces them.
 Kernels are paired by symbol.  --rename rewrites symbols (of both files, re.sub) before pairing, so that an experimental
 instantiation can be held against the kernel it should equal, e.g. a 64-token instantiation of a split kernel:
     --rename '15k_tfm_qkv_split(ILi\\d+ELi\\d+E)Li4E=9k_tfm_qkv\\1'
@@ -62,7 +63,7 @@ def kernels(asm):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("old")
+    ap.add_argument("old", nargs="+")
     ap.add_argument("new")
     ap.add_argument("--rename", action="append", default=[], metavar="REGEX=REPL")
     ap.add_argument("--show", type=int, default=0, metavar="N", help="print the first N differing lines of a kernel")
@@ -78,7 +79,13 @@ def main():
         return out
 
     with tempfile.TemporaryDirectory() as tmp:
-        old, new = renamed(kernels(assembly(args.old, tmp))), renamed(kernels(assembly(args.new, tmp)))
+        old = {}
+        for path in args.old:
+            ks = renamed(kernels(assembly(path, tmp)))
+            if set(ks) & set(old):
+                sys.exit("%s: kernels already seen in an earlier OLD: %s" % (path, ", ".join(sorted(set(ks) & set(old)))))
+            old.update(ks)
+        new = renamed(kernels(assembly(args.new, tmp)))
     same = differs = figures = 0
     for sym in sorted(set(old) & set(new)):
         (to, fo), (tn, fn) = old[sym], new[sym]
