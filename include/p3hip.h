@@ -101,6 +101,30 @@ typedef struct p3hip_engine p3hip_engine;
 #define P3HIP_FLAG_LAUNCH_GRAPH 8u  /* a run over the full static batch replays ONE captured launch graph, as
                                        TrtEngineImpl::RunInference does (trt_engine.cc:260-303); runs over fewer slots
                                        (compaction, cache hits) are launched kernel by kernel.  Same kernels, same results */
+#define P3HIP_FLAG_LAUNCH_GRAPH_ANY 131072u /* a captured launch graph for runs of every size.  Implies
+                                       P3HIP_FLAG_LAUNCH_GRAPH; both together are this flag.  The engine keeps a table of
+                                       graphs keyed by what a capture bakes into kernel arguments and grids: the slot count of
+                                       the pass, its forward rows (the slots, slots x k with P3HIP_FLAG_SYMMETRY_AVG, the
+                                       staged table's sum with P3HIP_FLAG_SYMMETRY_SLOT), the feature buffer it reads and
+                                       its result target.  The first pass of a key goes out kernel by kernel, the second
+                                       is captured and launched, later ones replay; a replay runs the launches of the
+                                       kernel-by-kernel pass with the same arguments, so every bit is the same.  What the
+                                       kernels read from device memory (features, the slot symmetry table, INT8 scales) may
+                                       change between replays.  The table holds P3HIP_GRAPH_CACHE graphs (environment at
+                                       p3hip_create: 1..1024, default 64; p3hip_create returns NULL for any other value)
+                                       and gives up the one replayed longest ago; p3hip_set_symmetries drops them all.
+                                       Calibration passes and the passes of an engine stopped by P3HIP_DEBUG_STOP_BLOCK stay
+                                       kernel by kernel.  A capture that fails drops the table and the engine launches
+                                       kernel by kernel for good.  Composes with everything P3HIP_FLAG_LAUNCH_GRAPH composes
+                                       with: every plan, both low-latency flags, both symmetry flags, P3HIP_FLAG_AUX,
+                                       P3HIP_FLAG_RUN_ALL_SLOTS, P3HIP_FLAG_SHARED_DEVICE, the NN cache, p3hip_score and
+                                       p3hip_loss.  p3hip_forward_resident and p3hip_run read different result targets and
+                                       hold a graph each.  A/B switches, read at p3hip_create: P3HIP_GRAPH_MIN_SEEN (a key is
+                                       captured on its n-th sighting, 2..64, default 2) and P3HIP_GRAPH_MAX_ROWS (partial
+                                       passes of more forward rows are never captured; default 0, no limit).  Measured
+                                       against P3HIP_FLAG_LAUNCH_GRAPH alone (README.md): 0.972-1.009x
+                                       of its p3hip_run time on partial runs of the low-latency plans, 1.002x in the worst
+                                       case for the table.  See p3hip_graph_state and p3hip_graph_stats below */
 #define P3HIP_FLAG_INT8 16u         /* calibrated INT8 inference (TensorRT's INT8 engine with a MinMax calibrator,
                                        python/trt_convert.py, cc/nn/engine/trt_calibrator.h): the convs of the layer-wise
                                        blocks run on int8 inputs and weights.  Layer-wise trunks
@@ -190,7 +214,8 @@ typedef struct p3hip_engine p3hip_engine;
                                        P3HIP_FLAG_AUX compose as with P3HIP_FLAG_SYMMETRY_AVG.  With
                                        P3HIP_FLAG_LAUNCH_GRAPH a run over the full static batch whose slots all have one
                                        symmetry (whichever) replays the graph; a run with an averaged slot goes out kernel by
-                                       kernel.  Not built: the aux record, a graph for runs with averaged slots, and on the
+                                       kernel.  Not built: the aux record, ~~a graph for runs with averaged slots~~ (built:
+                                       P3HIP_FLAG_LAUNCH_GRAPH_ANY keys its graphs by the forward rows), and on the
                                        host side root masks in self-play (the eval hosts have them: player keys
                                        nn_device_symmetry and nn_root_symmetry_mask) */
 
@@ -619,6 +644,17 @@ int p3hip_debug_edge_split(int npos, int c_pad, int n_cu, int* stem, int* dense,
 /* P3HIP_FLAG_LAUNCH_GRAPH: 1 once the full-batch forward pass has been captured and is being replayed,
  * 0 before (or without the flag), -1 when the capture failed and the engine fell back to plain launches. */
 int p3hip_graph_state(const p3hip_engine* e);
+/* P3HIP_FLAG_LAUNCH_GRAPH_ANY: p3hip_graph_state answers 0 while no graph is held, 1 once any is, -1 after a failed capture.
+ * p3hip_graph_stats fills out[0..4] with the graphs held now and, since p3hip_create, the captures, the replays, the forward
+ * passes launched kernel by kernel and the graphs given up for a newer one (evictions; graphs dropped all at once by
+ * p3hip_set_symmetries are not counted).  An engine with P3HIP_FLAG_LAUNCH_GRAPH alone reports its single graph (no
+ * evictions).  Returns 0, or 1 (and zeroes) on an engine without either flag. */
+int p3hip_graph_stats(const p3hip_engine* e, uint64_t out[5]);
+/* Test hook, no device: feeds n keys (npos[i], total[i]; feature buffer and result target fixed) through the policy of a
+ * P3HIP_FLAG_LAUNCH_GRAPH_ANY engine's table (csrc/graph_table.h) at the given capacity (1..1024).  action[i]: 0 launched
+ * kernel by kernel, 1 captured and launched, 2 replayed; evicted[i]: the step whose graph step i's capture gave up, or
+ * -1.  Returns 0, or 1 for a bad argument. */
+int p3hip_debug_graph_table(const int* npos, const int* total, int n, int capacity, int* action, int* evicted);
 /* Diagnostics of the hand-scheduled block kernel k_blockw (engines created with P3HIP_BLOCKW_DIAG in the environment
  * run its _diag twin, which stamps s_memtime at its section boundaries): copies up to n 64-bit stamps of the last
  * forward pass, [workgroup 0..7][block 0..15][wave 0..3][24], to out.  Returns 0, or 1 when there are none. */

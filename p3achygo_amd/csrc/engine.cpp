@@ -215,7 +215,33 @@ const DeviceBuffer kDeviceBuffers[] = {
 extern "C" {
 
 const char* p3hip_create_error(void) { return g_create_error.c_str(); }
-int p3hip_graph_state(const p3hip_engine* e) { return e->graph_failed ? -1 : (e->graph_exec ? 1 : 0); }
+int p3hip_graph_state(const p3hip_engine* e) {
+  return e->graph_failed ? -1 : (e->graph_exec || e->graph_table.held() > 0 ? 1 : 0);
+}
+
+int p3hip_graph_stats(const p3hip_engine* e, uint64_t out[5]) {
+  for (int i = 0; i < 5; ++i) out[i] = 0;
+  if (!(e->flags & (P3HIP_FLAG_LAUNCH_GRAPH | P3HIP_FLAG_LAUNCH_GRAPH_ANY))) return 1;
+  if (e->graph_any()) {
+    const gt::Table& t = e->graph_table;
+    out[0] = (uint64_t)t.held(); out[1] = t.captures(); out[2] = t.replays(); out[3] = t.launches(); out[4] = t.evictions();
+  } else {
+    out[0] = e->graph_exec ? 1 : 0; out[1] = e->graph_captures; out[2] = e->graph_replays; out[3] = e->graph_launched;
+  }
+  return 0;
+}
+
+int p3hip_debug_graph_table(const int* npos, const int* total, int n, int capacity, int* action, int* evicted) {
+  if (!npos || !total || !action || !evicted || n < 0 || capacity < gt::kMinCapacity || capacity > gt::kMaxCapacity) return 1;
+  gt::Table table(capacity);
+  static const char feats = 0, res = 0;   // the buffer and the target of every key: any two fixed addresses
+  for (int i = 0; i < n; ++i) {
+    const gt::Step s = table.see(gt::Key{npos[i], total[i], &feats, &res}, i);
+    action[i] = (int)s.action;
+    evicted[i] = (int)s.evicted_tag;
+  }
+  return 0;
+}
 
 p3hip_engine* p3hip_create(const char* weights_path, int batch_size, int version,
                            int device_ordinal, uint32_t flags) {
@@ -275,6 +301,10 @@ p3hip_engine* p3hip_create_rows(const char* weights_path, int batch_size, int ve
   e->device = device_ordinal;
   e->flags = flags;
   e->opt = Options::from_env();
+  if (e->graph_any()) {   // (a P3HIP_GRAPH_CACHE outside 1..1024: build_plan refuses below)
+    e->graph_table = gt::Table(e->opt.graph_cache, e->opt.graph_min_seen);
+    e->graph_slots.resize((size_t)e->opt.graph_cache);
+  }
   e->sym = sym;
   e->sym_slot = sym_slot;
   e->rows = sym ? p3::kNumSyms * batch_size : sym_slot ? symmetry_rows : batch_size;
@@ -1087,7 +1117,8 @@ int p3hip_set_symmetries(p3hip_engine* e, uint32_t mask) {
   if (!e->bind()) return 1;
   // the captured graph holds the old list in its kernel arguments: drop it.  The next full run goes out kernel by
   // kernel (a new k means new row counts, whose launchers may meet kernels for the first time), the one after is captured
-  if ((e->graph_exec || e->graph) && !e->check(hipStreamSynchronize(e->stream), "sync")) return 1;
+  // (P3HIP_FLAG_LAUNCH_GRAPH_ANY: every graph of the table and every sighting, so each key starts again the same way)
+  if ((e->graph_exec || e->graph || e->graph_table.held() > 0) && !e->check(hipStreamSynchronize(e->stream), "sync")) return 1;
   drop_graph(e);
   e->graph_warm = false;
   e->sym_mask = mask;

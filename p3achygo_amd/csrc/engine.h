@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/p3hip.h"
+#include "graph_table.h"
 #include "heads_aux.h"
 #include "kernels.h"
 #include "plan.h"
@@ -29,6 +30,12 @@ struct Pass {
   float* out = nullptr;   // the rows the heads write: d_out, or d_cout for the copies of a symmetry pass
   float* res = nullptr;   // d_res: the result records a second time, dense (HeadsArgs::res); null: not written
   int* timed = nullptr;   // p3hip_time_trunk_kernel: launches timed so far, event pairs e->blk_ev[2 i, 2 i + 1]
+};
+
+// P3HIP_FLAG_LAUNCH_GRAPH_ANY: one captured pass of the engine's table (p3hip_engine::graph_slots)
+struct GraphSlot {
+  hipGraph_t graph = nullptr;
+  hipGraphExec_t exec = nullptr;
 };
 
 }  // namespace eng
@@ -52,6 +59,14 @@ struct p3hip_engine {
   hipGraphExec_t graph_exec = nullptr;
   bool graph_failed = false, graph_warm = false;
   eng::Pass graph_pass;   // the pass the graph was captured for (kernel arguments are baked in): its feats and res are the key
+  uint64_t graph_captures = 0, graph_replays = 0, graph_launched = 0;   // p3hip_graph_stats of that one graph
+  // P3HIP_FLAG_LAUNCH_GRAPH_ANY: a graph per key (slots, forward rows, feature buffer, result
+  // target).  graph_table (graph_table.h) decides what a pass does and hands out the slots of graph_slots, which holds
+  // the graphs; graph_seq counts the passes the table saw (the tags of its entries)
+  gt::Table graph_table;
+  std::vector<eng::GraphSlot> graph_slots;
+  long graph_seq = 0;
+  bool graph_any() const { return (flags & P3HIP_FLAG_LAUNCH_GRAPH_ANY) != 0; }
   // p3hip_time_trunk_kernel: event pairs around the timed launches of a forward pass
   std::vector<hipEvent_t> blk_ev;
 

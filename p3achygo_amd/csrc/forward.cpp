@@ -696,6 +696,65 @@ bool enqueue_sym(p3hip_engine* e, const Pass& p) {
   return e->check(p3::launch_sym_reduce(r, e->stream), "launch k_sym_reduce");
 }
 
+// Captures `enqueue` on the engine's stream, one linear chain, and instantiates it.  False (nothing was executed, nothing
+// is left behind, HIP's error state is cleared): the capture did not come about.
+template <class Enqueue>
+bool capture_pass(p3hip_engine* e, Enqueue&& enqueue, hipGraph_t* graph, hipGraphExec_t* exec) {
+  *graph = nullptr;
+  *exec = nullptr;
+  if (hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  const bool ok = enqueue();
+  const hipError_t ce = hipStreamEndCapture(e->stream, graph);
+  if (!ok || ce != hipSuccess || !*graph || hipGraphInstantiate(exec, *graph, nullptr, nullptr, 0) != hipSuccess) {
+    if (*graph) hipGraphDestroy(*graph);
+    *graph = nullptr;
+    *exec = nullptr;
+    (void)hipGetLastError();
+    return false;
+  }
+  return true;
+}
+
+void destroy_slot(GraphSlot& s) {
+  if (s.exec) hipGraphExecDestroy(s.exec);
+  if (s.graph) hipGraphDestroy(s.graph);
+  s = GraphSlot{};
+}
+
+// The pass of a P3HIP_FLAG_LAUNCH_GRAPH_ANY engine: the table says whether its key is launched, captured or replayed.
+// e->last_npos: the forward rows, set by run_pass.
+template <class Enqueue>
+bool run_pass_any(p3hip_engine* e, const Pass& p, Enqueue&& enqueue) {
+  // calibration passes run other kernels (the fp16 plan + absmax), a stopped engine is a debugging aid, and a pass
+  // without rows (P3HIP_FLAG_SYMMETRY_SLOT: more slots than the staged table) only fetches its error
+  // P3HIP_GRAPH_MAX_ROWS: a partial pass of more forward rows is not worth a graph
+  const bool too_long = e->opt.graph_max_rows > 0 && p.npos != e->batch && e->last_npos > e->opt.graph_max_rows;
+  if (e->graph_failed || e->calibrating || e->opt.stop_block >= 0 || e->last_npos < 1 || too_long) {
+    e->graph_table.count_launch();
+    return enqueue();
+  }
+  const gt::Step step = e->graph_table.see(gt::Key{p.npos, e->last_npos, p.feats, p.res}, e->graph_seq++);
+  if (step.action == gt::kLaunch) return enqueue();
+  GraphSlot& slot = e->graph_slots[step.slot];
+  if (step.action == gt::kReplay) return e->check(hipGraphLaunch(slot.exec, e->stream), "hipGraphLaunch");
+  if (slot.exec) {
+    // the table gave up the graph replayed longest ago for this one: nothing of it may be in flight when it goes
+    if (!e->check(hipStreamSynchronize(e->stream), "sync")) return false;
+    destroy_slot(slot);
+  }
+  if (!capture_pass(e, enqueue, &slot.graph, &slot.exec)) {
+    e->graph_failed = true;
+    if (hipStreamSynchronize(e->stream) != hipSuccess) (void)hipGetLastError();
+    drop_graph(e);
+    e->graph_table.count_launch();
+    return enqueue();   // nothing was executed by the capture
+  }
+  return e->check(hipGraphLaunch(slot.exec, e->stream), "hipGraphLaunch");
+}
+
 }  // namespace
 
 // The forward pass of a run (with P3HIP_FLAG_SYMMETRY_AVG: expand, forward and reduce): one captured graph for the full
@@ -704,50 +763,47 @@ bool enqueue_sym(p3hip_engine* e, const Pass& p) {
 // The first full-batch run goes out kernel by kernel (the launchers set their kernels' LDS attributes on first use,
 // which a capture must not see), the second is captured, the rest replay.  A capture that fails falls back to the
 // launches for good.  Calibration runs (the fp16 plan + absmax) go kernel by kernel.
+// P3HIP_FLAG_LAUNCH_GRAPH_ANY: a graph per key instead, run_pass_any above.
 bool run_pass(p3hip_engine* e, const Pass& p) {
   e->last_npos = e->sym_slot ? std::max(sym_rows_of(e, p.npos), 0) : p.npos * (e->sym ? e->sym_k : 1);
   auto enqueue = [&] { return e->any_sym() ? enqueue_sym(e, p) : enqueue_forward(e, p); };
-  if (!(e->flags & P3HIP_FLAG_LAUNCH_GRAPH) || p.npos != e->batch || e->graph_failed || e->calibrating) return enqueue();
+  if (e->graph_any()) return run_pass_any(e, p, enqueue);
+  auto launch = [&] { ++e->graph_launched; return enqueue(); };
+  if (!(e->flags & P3HIP_FLAG_LAUNCH_GRAPH) || p.npos != e->batch || e->graph_failed || e->calibrating) return launch();
   // P3HIP_FLAG_SYMMETRY_SLOT: the graph's grids are those of batch forward rows, every slot under one symmetry (the
   // kernels read which from the table in device memory, so it may change from replay to replay); a run with an
   // averaged slot has more rows and goes out kernel by kernel
-  if (e->sym_slot && e->last_npos != e->batch) return enqueue();
+  if (e->sym_slot && e->last_npos != e->batch) return launch();
   // The capture bakes every kernel argument in: the feature buffer the pass reads (run_cached's passes read the cache's
   // gathered copy) and whether it writes d_res.  The graph serves the pass it was captured for; any other goes out
   // kernel by kernel.
   if (e->graph_exec) {
-    if (p.feats != e->graph_pass.feats || p.res != e->graph_pass.res) return enqueue();
+    if (p.feats != e->graph_pass.feats || p.res != e->graph_pass.res) return launch();
+    ++e->graph_replays;
     return e->check(hipGraphLaunch(e->graph_exec, e->stream), "hipGraphLaunch");
   }
   if (!e->graph_warm) {
     e->graph_warm = true;
-    return enqueue();
+    return launch();
   }
-  if (hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
+  if (!capture_pass(e, enqueue, &e->graph, &e->graph_exec)) {
     e->graph_failed = true;
-    (void)hipGetLastError();
-    return enqueue();
+    return launch();   // nothing was executed by the capture
   }
-  const bool ok = enqueue();
-  hipGraph_t g = nullptr;
-  const hipError_t ce = hipStreamEndCapture(e->stream, &g);
-  if (!ok || ce != hipSuccess || !g || hipGraphInstantiate(&e->graph_exec, g, nullptr, nullptr, 0) != hipSuccess) {
-    if (g) hipGraphDestroy(g);
-    e->graph_exec = nullptr;
-    e->graph_failed = true;
-    (void)hipGetLastError();
-    return enqueue();   // nothing was executed by the capture
-  }
-  e->graph = g;
   e->graph_pass = p;
+  ++e->graph_captures;
   return e->check(hipGraphLaunch(e->graph_exec, e->stream), "hipGraphLaunch");
 }
 
+// Destroys every graph the engine holds; with P3HIP_FLAG_LAUNCH_GRAPH_ANY the table's entries and sightings go too (the
+// counters stay).  The caller has drained the stream.
 void drop_graph(p3hip_engine* e) {
   if (e->graph_exec) hipGraphExecDestroy(e->graph_exec);
   if (e->graph) hipGraphDestroy(e->graph);
   e->graph_exec = nullptr;
   e->graph = nullptr;
+  for (GraphSlot& s : e->graph_slots) destroy_slot(s);
+  e->graph_table.clear();
 }
 
 }  // namespace eng

@@ -13,6 +13,7 @@
 #include "conv_split.h"
 #include "conv_wino.h"
 #include "edge_split.h"
+#include "graph_table.h"
 #include "lconv_i8.h"
 #include "transformer.h"
 #include "transformer_f32.h"
@@ -62,6 +63,13 @@ Options Options::from_env() {
       o.edge_bad = true;
     }
   }
+  o.graph_cache = gt::capacity_from(getenv("P3HIP_GRAPH_CACHE"));
+  if (o.graph_cache == 0) {
+    o.graph_cache = gt::kDefaultCapacity;
+    o.graph_cache_bad = true;
+  }
+  o.graph_min_seen = std::min(std::max(num("P3HIP_GRAPH_MIN_SEEN", gt::kMinSeen), gt::kMinSeen), 64);
+  o.graph_max_rows = std::max(num("P3HIP_GRAPH_MAX_ROWS", gt::kDefaultMaxRows), 0);
   return o;
 }
 
@@ -284,6 +292,8 @@ PlanChoice choose_plan(const WeightFile& wf, uint32_t flags, const Options& opt,
        "P3HIP_FLAG_FP32_TFM serves the transformer trunks only (" P3HIP_TRANSFORMER_SET "); the conv trunks have "
        "P3HIP_FLAG_FP32"},
       {!r.clash.empty(), r.clash},
+      {(flags & P3HIP_FLAG_LAUNCH_GRAPH_ANY) && opt.graph_cache_bad,
+       "P3HIP_FLAG_LAUNCH_GRAPH_ANY: P3HIP_GRAPH_CACHE must be a whole number of graphs from 1 to 1024 (default 64)"},
       {k == Request::LowLatency && !t.tfm_file && opt.split_bad,
        "P3HIP_FLAG_LOW_LATENCY: P3HIP_SPLIT must be \"S,T\" with S row strips of 1, 2 or 4 and output tiles of T = 16, 32 "
        "or 64 channels"},

@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "graph_table.h"
 #include "heads_aux.h"
 #include "kernels.h"
 #include "weights.h"
@@ -48,6 +49,14 @@ struct Options {
   // variable is set to something else, which fails the creation of such an engine
   int edge_s = 0, edge_d = 0, edge_h = 0;
   bool edge_bad = false;
+  // P3HIP_GRAPH_CACHE (P3HIP_FLAG_LAUNCH_GRAPH_ANY engines): the graphs the engine's table holds, 1..1024 (graph_table.h).
+  // graph_cache_bad: set to anything else, which fails the creation of such an engine
+  int graph_cache = 64;
+  bool graph_cache_bad = false;
+  // P3HIP_GRAPH_MIN_SEEN, P3HIP_GRAPH_MAX_ROWS (the same engines; A/B runs, tools/gpu_graph_any_ab.py): a key is captured on
+  // its n-th sighting (2..64, never the first: graph_table.h), and only a pass of at most so many forward rows is (0: no
+  // limit; a pass over the full static batch always is).  Out of range: the nearest bound.  Defaults: graph_table.h
+  int graph_min_seen = gt::kMinSeen, graph_max_rows = gt::kDefaultMaxRows;
   static Options from_env();
 };
 

@@ -40,11 +40,16 @@ EXPORTS = [
     "p3hip_debug_split", "p3hip_debug_pack_sconv", "p3hip_debug_tfm_split", "p3hip_debug_edge_split",
     "p3hip_debug_poison", "p3hip_debug_poison_table",
     "p3hip_debug_pack_wconv", "p3hip_debug_wconv_grid",
+    "p3hip_graph_stats", "p3hip_debug_graph_table",
 ]
 
 FLAG_RUN_ALL_SLOTS = 2
 FLAG_SHARED_DEVICE = 4
 FLAG_LAUNCH_GRAPH = 8
+# a captured graph for runs of every size: a table of graphs keyed by slots, forward rows, feature buffer and result target;
+# implies FLAG_LAUNCH_GRAPH (include/p3hip.h)
+FLAG_LAUNCH_GRAPH_ANY = 131072
+GRAPH_STATS = ("held", "captures", "replays", "launched", "evictions")
 FLAG_INT8 = 16   # calibrated INT8 convs in the layer-wise blocks (include/p3hip.h)
 FLAG_INT8_FUSED = 64   # calibrated INT8 of the C = 256 btl trunks, one fused int8 block kernel per block (section 9)
 FLAG_INT8_C128 = 128   # the same for the C = 128 / C_b = 64 btl trunks (b12c128btl3): k_block_i8<128,64>, two workgroups per CU
@@ -504,6 +509,16 @@ class HipEngine:
         self._L.p3hip_graph_state.argtypes = [C.c_void_p]
         return int(self._L.p3hip_graph_state(self._h))
 
+    def graph_stats(self) -> dict:
+        """p3hip_graph_stats: the graphs held now, and since the engine was created the captures, the replays, the forward
+        passes launched kernel by kernel and the evictions (GRAPH_STATS).  FLAG_LAUNCH_GRAPH_ANY: of the engine's table;
+        FLAG_LAUNCH_GRAPH alone: of its one graph.  EngineError on an engine with neither flag."""
+        self._L.p3hip_graph_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        out = (C.c_uint64 * 5)()
+        if self._L.p3hip_graph_stats(self._h, out) != 0:
+            raise EngineError("graph_stats: the engine was created without FLAG_LAUNCH_GRAPH or FLAG_LAUNCH_GRAPH_ANY")
+        return dict(zip(GRAPH_STATS, (int(v) for v in out)))
+
     def flops_per_position(self):
         t, c = C.c_double(0), C.c_double(0)
         self._L.p3hip_flops_per_position(self._h, C.byref(t), C.byref(c))
@@ -543,6 +558,24 @@ def debug_plan(path: str, flags: int = 0):
     if name is None:
         raise EngineError("p3hip_create: " + L.p3hip_create_error().decode())
     return name.decode(), n_q.value, dig.value
+
+
+def debug_graph_table(keys, capacity: int = 64):
+    """What a FLAG_LAUNCH_GRAPH_ANY engine's table (csrc/graph_table.h) does with a sequence of passes, feature buffer and
+    result target fixed: p3hip_debug_graph_table, no device needed.  keys: (slots, forward rows) pairs, or slot counts
+    alone (rows = slots).  Returns (actions, evicted): per pass 0 launched kernel by kernel, 1 captured and launched, 2
+    replayed, and the index of the pass whose graph its capture gave up, or -1.  ValueError for a bad argument."""
+    L = lib()
+    L.p3hip_debug_graph_table.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    pairs = [(k, k) if np.isscalar(k) else tuple(k) for k in keys]
+    npos = np.array([p[0] for p in pairs], np.int32)
+    total = np.array([p[1] for p in pairs], np.int32)
+    action = np.full(len(pairs), -1, np.int32)
+    evicted = np.full(len(pairs), -2, np.int32)
+    if L.p3hip_debug_graph_table(npos.ctypes.data, total.ctypes.data, len(pairs), int(capacity), action.ctypes.data,
+                                 evicted.ctypes.data) != 0:
+        raise ValueError("p3hip_debug_graph_table: bad argument")
+    return action.tolist(), evicted.tolist()
 
 
 def debug_poison_table() -> dict:

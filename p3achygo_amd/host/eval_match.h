@@ -104,6 +104,9 @@ struct EvalPlayerConfig {   // PlayerSearchConfig (player_config.h:20-108), same
   // extension: the player's engine runs the 3x3 convs of a layer-wise conv trunk as F(2x2, 3x3) Winograd
   // (P3HIP_FLAG_WINOGRAD).  A trunk the plan does not serve ends the match with the engine's message.
   int nn_winograd = 0;
+  // extension: the player's engine replays a captured launch graph for runs of every size (P3HIP_FLAG_LAUNCH_GRAPH_ANY): a
+  // player with a few search threads has a different number of pending slots each run.  Same results.
+  int nn_graph_any = 0;
   // extension: the player's engine takes a symmetry set per slot (P3HIP_FLAG_SYMMETRY_SLOT): every evaluation's random
   // symmetry goes to the engine as the slot's mask, features are loaded un-rotated and results come back un-rotated.
   // The games are those of host rotation.
@@ -261,6 +264,13 @@ inline bool ParsePlayerConfigStream(std::istream& in, EvalPlayerConfig* cfg, std
           return false;
         }
         cfg->nn_winograd = val == "1";
+      }
+      else if (key == "nn_graph_any") {
+        if (val != "0" && val != "1") {
+          if (err) *err = "nn_graph_any must be 0 or 1: " + line;
+          return false;
+        }
+        cfg->nn_graph_any = val == "1";
       }
       else if (key == "nn_device_symmetry") {
         if (val != "0" && val != "1") {

@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -98,6 +99,10 @@ struct HashEvaluator final : Evaluator {
   void Get(int slot, p3hip_result& r) override { r = results[(size_t)slot]; }
 };
 
+// p3hip_graph_stats of every HipEvaluator closed so far, summed: graphs held at the close, captures, replays, passes launched
+// kernel by kernel, evictions (p3host_graph_stats reads and clears them)
+inline std::atomic<uint64_t> g_closed_graph_stats[5];
+
 // The HIP engine, bound through its C ABI exactly as a foreign host would bind it.
 struct HipEvaluator final : Evaluator {
   void* lib = nullptr;
@@ -117,6 +122,7 @@ struct HipEvaluator final : Evaluator {
   decltype(&p3hip_set_symmetries) set_symmetries = nullptr;
   decltype(&p3hip_create_rows) create_rows = nullptr;
   decltype(&p3hip_set_slot_symmetries) set_slot_symmetries = nullptr;
+  decltype(&p3hip_graph_stats) graph_stats = nullptr;
   bool slot_symmetries = false;   // opened with P3HIP_FLAG_SYMMETRY_SLOT
   std::string err;
 
@@ -139,6 +145,7 @@ struct HipEvaluator final : Evaluator {
     set_symmetries = (decltype(set_symmetries))dlsym(lib, "p3hip_set_symmetries");
     create_rows = (decltype(create_rows))dlsym(lib, "p3hip_create_rows");
     set_slot_symmetries = (decltype(set_slot_symmetries))dlsym(lib, "p3hip_set_slot_symmetries");
+    graph_stats = (decltype(graph_stats))dlsym(lib, "p3hip_graph_stats");
     if (!create || !destroy || !load || !run || !get) { err = "missing p3hip symbols"; return false; }
     if (flags & P3HIP_FLAG_SYMMETRY_SLOT) {
       if (!create_rows || !set_slot_symmetries) {
@@ -161,6 +168,10 @@ struct HipEvaluator final : Evaluator {
     return true;
   }
   ~HipEvaluator() override {
+    // an engine opened with a launch-graph flag leaves its counts behind for p3host_graph_stats
+    uint64_t gs[5];
+    if (eng && graph_stats && graph_stats(eng, gs) == 0)
+      for (int i = 0; i < 5; ++i) g_closed_graph_stats[i].fetch_add(gs[i], std::memory_order_relaxed);
     if (eng) destroy(eng);
     if (lib) dlclose(lib);
   }

@@ -788,6 +788,7 @@ float g_use_seen_state_prob = 0.5f, g_sel_mult_base = 0.0f, g_sel_mult_scale = 1
 float g_bias_cache_lambda = 0.0f, g_bias_cache_alpha = 0.8f;
 bool g_early_stopping = false;
 bool g_device_symmetry = false;
+bool g_graph_any = false;
 std::string g_calibration_file;
 long g_last_bias_pruned = 0;
 double g_last_bias_adj = 0;
@@ -828,6 +829,14 @@ void p3host_selfplay_set_early_stopping(int enabled) { g_early_stopping = enable
 // with P3HIP_FLAG_SYMMETRY_SLOT and as many rows as slots) and neither rotate features nor results on the host; games,
 // records and search results are the host path's.  Off by default; no effect on the null and hash evaluators.
 void p3host_selfplay_set_device_symmetry(int enabled) { g_device_symmetry = enabled != 0; }
+// Subsequent self-play runs over an engine library open the game groups' engines with P3HIP_FLAG_LAUNCH_GRAPH_ANY: a run of
+// any size replays a captured graph from its third sighting on.  Off by default; no effect on the null and hash evaluators.
+void p3host_selfplay_set_graph_any(int enabled) { g_graph_any = enabled != 0; }
+// p3hip_graph_stats summed over the engines that the runs and matches since the last call opened and closed (engines with a
+// launch-graph flag only): graphs held at the close, captures, replays, passes launched kernel by kernel, evictions
+void p3host_graph_stats(uint64_t out[5]) {
+  for (int i = 0; i < 5; ++i) out[i] = g_closed_graph_stats[i].exchange(0);
+}
 // bias-cache entries pruned / sum of |root adjustment| over the moves of the last run or game
 long p3host_selfplay_last_bias_pruned() { return g_last_bias_pruned; }
 double p3host_selfplay_last_bias_adj() { return g_last_bias_adj; }
@@ -966,8 +975,8 @@ int p3host_selfplay_run(const char* engine_lib, const char* weights, int device,
         auto* e = new HipEvaluator();
         halves[h].lanes[l]->eval.reset(e);
         // one engine per lane, all on this GPU (device symmetry: one copy per slot, so as many rows as slots)
-        if (!e->Open(engine_lib, weights, ng, device, P3HIP_FLAG_SHARED_DEVICE | (dev_sym ? P3HIP_FLAG_SYMMETRY_SLOT : 0u),
-                     dev_sym ? ng : 0)) {
+        if (!e->Open(engine_lib, weights, ng, device, P3HIP_FLAG_SHARED_DEVICE | (dev_sym ? P3HIP_FLAG_SYMMETRY_SLOT : 0u) |
+                         (g_graph_any ? P3HIP_FLAG_LAUNCH_GRAPH_ANY : 0u), dev_sym ? ng : 0)) {
           if (err) snprintf(err, 256, "%s", e->err.c_str());
           return 1;
         }
@@ -1665,7 +1674,8 @@ int p3host_eval_match(const char* engine_lib, const char* cur_weights, const cha
       ev[e].reset(h);
       const uint32_t flags = P3HIP_FLAG_SHARED_DEVICE |   // the two players' passes run concurrently
                              (pc[e].nn_fp32 ? P3HIP_FLAG_FP32_ANY : 0u) | (pc[e].nn_low_latency ? P3HIP_FLAG_LOW_LATENCY_ANY : 0u) |
-                             (pc[e].nn_winograd ? P3HIP_FLAG_WINOGRAD : 0u);
+                             (pc[e].nn_winograd ? P3HIP_FLAG_WINOGRAD : 0u) |
+                             (pc[e].nn_graph_any ? P3HIP_FLAG_LAUNCH_GRAPH_ANY : 0u);
       if (!OpenEvalEngine(h, engine_lib, e == 0 ? cur_weights : cand_weights, slots, num_games, device, flags, pc[e])) {
         if (err) snprintf(err, 256, "%s", h->err.c_str());
         return 1;
@@ -1836,7 +1846,8 @@ int p3host_eval_match_threads(const char* engine_lib, const char* cur_weights, c
       // nn_device_symmetry / nn_root_symmetry_mask: the engine rotates, a search's root visit under the root mask
       const uint32_t flags = P3HIP_FLAG_SHARED_DEVICE |
                              (pc[e].nn_fp32 ? P3HIP_FLAG_FP32_ANY : 0u) | (pc[e].nn_low_latency ? P3HIP_FLAG_LOW_LATENCY_ANY : 0u) |
-                             (pc[e].nn_winograd ? P3HIP_FLAG_WINOGRAD : 0u);
+                             (pc[e].nn_winograd ? P3HIP_FLAG_WINOGRAD : 0u) |
+                             (pc[e].nn_graph_any ? P3HIP_FLAG_LAUNCH_GRAPH_ANY : 0u);
       if (!OpenEvalEngine(h, engine_lib, e == 0 ? cur_weights : cand_weights, batch, num_games, device, flags, pc[e])) {
         if (err) snprintf(err, 256, "%s", h->err.c_str());
         return 1;
@@ -2005,6 +2016,15 @@ int p3host_parse_player_winograd(const char* path, int* winograd, char* err) {
   std::string e;
   if (!ParsePlayerConfig(path, &c, &e)) { if (err) snprintf(err, 256, "%s", e.c_str()); return 1; }
   *winograd = c.nn_winograd;
+  return 0;
+}
+
+// the nn_graph_any of a player config file (tests): 0 and the value, or 1 with the parser's message
+int p3host_parse_player_graph_any(const char* path, int* graph_any, char* err) {
+  EvalPlayerConfig c;
+  std::string e;
+  if (!ParsePlayerConfig(path, &c, &e)) { if (err) snprintf(err, 256, "%s", e.c_str()); return 1; }
+  *graph_any = c.nn_graph_any;
   return 0;
 }
 

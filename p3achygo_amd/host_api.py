@@ -248,6 +248,26 @@ def set_device_symmetry(enabled) -> None:
     L.p3host_selfplay_set_device_symmetry(int(bool(enabled)))
 
 
+def set_graph_any(enabled) -> None:
+    """Subsequent self-play runs over an engine library open the game groups' engines with P3HIP_FLAG_LAUNCH_GRAPH_ANY
+    (include/p3hip.h): a run of any size replays a captured launch graph from its third sighting on.  Same results.
+    Off by default."""
+    L = lib()
+    L.p3host_selfplay_set_graph_any.argtypes = [C.c_int]
+    L.p3host_selfplay_set_graph_any(int(bool(enabled)))
+
+
+def graph_stats() -> dict:
+    """p3hip_graph_stats summed over the engines that the self-play runs and eval matches since the last call opened with a
+    launch-graph flag: graphs held when they closed, captures, replays, passes launched kernel by kernel, evictions."""
+    L = lib()
+    out = (C.c_uint64 * 5)()
+    L.p3host_graph_stats.argtypes = [C.POINTER(C.c_uint64)]
+    L.p3host_graph_stats.restype = None
+    L.p3host_graph_stats(out)
+    return dict(zip(("held", "captures", "replays", "launched", "evictions"), (int(v) for v in out)))
+
+
 def set_early_stopping(enabled: bool) -> None:
     """--early_stopping_enabled of subsequent self-play runs (selfplay/main.cc:68; off by default)."""
     L = lib()
