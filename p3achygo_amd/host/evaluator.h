@@ -10,6 +10,7 @@
 #include <atomic>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -216,5 +217,20 @@ struct HipEvaluator final : Evaluator {
     if (int rc = get_own(eng, slot, out)) Fatal("get_ownership", slot, rc);
   }
 };
+
+// The evaluator that an `engine_lib` argument names: NULL or "" the NullEvaluator, "hash" the HashEvaluator of
+// `hash_slots` slots (tests; 0 = the caller does not serve it), anything else a HipEvaluator that `open` opens with the
+// caller's flags and rows.  Null with the engine's message in `err` (256 bytes) when that fails.
+template <class Open>
+std::unique_ptr<Evaluator> MakeEvaluator(const char* engine_lib, int hash_slots, char* err, Open&& open) {
+  if (!engine_lib || !engine_lib[0]) return std::make_unique<NullEvaluator>();
+  if (hash_slots > 0 && !std::strcmp(engine_lib, "hash")) return std::make_unique<HashEvaluator>(hash_slots);
+  auto h = std::make_unique<HipEvaluator>();
+  if (!open(*h)) {
+    if (err) snprintf(err, 256, "%s", h->err.c_str());
+    return nullptr;
+  }
+  return h;
+}
 
 }  // namespace p3

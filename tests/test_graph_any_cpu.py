@@ -168,9 +168,12 @@ def test_hosts_pass_the_flag(built, tmp_path):
         p.write_text(text)
         assert H.p3host_parse_player_graph_any(str(p).encode(), C.byref(val), err) == 1, text
         assert err.value.decode().startswith("nn_graph_any must be 0 or 1"), err.value
+    # the match drivers' flags are written once (EvalEngineFlags) and reach both engine-opening sites through one helper
+    src = open(os.path.join(ROOT, "p3achygo_amd", "host", "eval_match.cc")).read()
+    assert src.count("nn_graph_any ? P3HIP_FLAG_LAUNCH_GRAPH_ANY : 0u") == 1
+    assert src.count("EvalEngineFlags(c)") == 1 and src.count("= MakeEvalEvaluator(") == 2
     src = open(os.path.join(ROOT, "p3achygo_amd", "host", "selfplay.cc")).read()
-    assert src.count("nn_graph_any ? P3HIP_FLAG_LAUNCH_GRAPH_ANY : 0u") == 2
-    assert src.count("g_graph_any ? P3HIP_FLAG_LAUNCH_GRAPH_ANY : 0u") == 1
+    assert src.count("opt_.graph_any ? P3HIP_FLAG_LAUNCH_GRAPH_ANY : 0u") == 1
     host_api.set_graph_any(1)       # the switch exists and takes both values; off again for whoever runs next
     host_api.set_graph_any(0)
 

@@ -205,8 +205,10 @@ def test_chooser_honours_the_override(built, env):
 
 def test_player_key_maps_to_both_bits():
     """nn_low_latency: 1 of an eval player asks for the low-latency plan whatever the net's trunk"""
-    src = open(os.path.join(ROOT, "p3achygo_amd", "host", "selfplay.cc")).read()
-    assert len(re.findall(r"nn_low_latency \? P3HIP_FLAG_LOW_LATENCY_ANY : 0u", src)) == 2
+    src = open(os.path.join(ROOT, "p3achygo_amd", "host", "eval_match.cc")).read()
+    # written once (EvalEngineFlags), and both engine-opening sites of the match drivers go through it
+    assert len(re.findall(r"nn_low_latency \? P3HIP_FLAG_LOW_LATENCY_ANY : 0u", src)) == 1
+    assert src.count("EvalEngineFlags(c)") == 1 and src.count("= MakeEvalEvaluator(") == 2
     assert not re.search(r"nn_low_latency \? P3HIP_FLAG_LOW_LATENCY :", src)
 
 

@@ -118,8 +118,10 @@ def test_nn_fp32_parses(built, tmp_path):
     for text, want in (("n: 16\n", 0), ("n: 16\nnn_fp32: 1\n", 1), ("n: 16\nnn_fp32: 0\n", 0)):
         p.write_text(text)
         assert H.p3host_parse_player_fp32(str(p).encode(), C.byref(val), err) == 0 and val.value == want, text
-    src = open(os.path.join(ROOT, "p3achygo_amd", "host", "selfplay.cc")).read()
-    assert src.count("nn_fp32 ? P3HIP_FLAG_FP32_ANY") == 2 and "nn_fp32 ? P3HIP_FLAG_FP32 " not in src
+    # written once (EvalEngineFlags), and both engine-opening sites of the match drivers go through it
+    src = open(os.path.join(ROOT, "p3achygo_amd", "host", "eval_match.cc")).read()
+    assert src.count("nn_fp32 ? P3HIP_FLAG_FP32_ANY") == 1 and "nn_fp32 ? P3HIP_FLAG_FP32 " not in src
+    assert src.count("EvalEngineFlags(c)") == 1 and src.count("= MakeEvalEvaluator(") == 2
 
 
 # ---- the twin ----------------------------------------------------------------------------------------------------------

@@ -253,5 +253,7 @@ def test_player_key_nn_winograd(built, tmp_path):
         p.write_text(text)
         assert H.p3host_parse_player_winograd(str(p).encode(), C.byref(val), err) == 1, text
         assert err.value.decode().startswith("nn_winograd must be 0 or 1"), err.value
-    src = open(os.path.join(ROOT, "p3achygo_amd", "host", "selfplay.cc")).read()
-    assert src.count("nn_winograd ? P3HIP_FLAG_WINOGRAD : 0u") == 2
+    # written once (EvalEngineFlags), and both engine-opening sites of the match drivers go through it
+    src = open(os.path.join(ROOT, "p3achygo_amd", "host", "eval_match.cc")).read()
+    assert src.count("nn_winograd ? P3HIP_FLAG_WINOGRAD : 0u") == 1
+    assert src.count("EvalEngineFlags(c)") == 1 and src.count("= MakeEvalEvaluator(") == 2
